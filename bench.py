@@ -7,7 +7,13 @@ batch of 64 synthetic image<->text pairs per rank: CLIP forward with the HIP att
 that fills every layer's gradient slab, the fused relevancy chain for both towers (all 12+12 layers,
 ``start_layer=0``).  Rank 0 prints ONE JSON line.  Inputs are resident in HBM before the timed region.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the ``--steps`` steps and prints the line (``metric``, ``value``, ``unit``,
+``ms_per_step``, ...; ``roofline_step`` is derived from ``ms_per_step``).  ``--dump-outputs DIR`` writes what the last timed step
+returned (``R_text``, ``R_image`` of rank 0) as ``DIR/<name>.npy`` in float32; inputs and weights are seeded, so two builds can be
+compared output for output.  Everything that takes runs of its own -- the variant rates, the chain-kernel roofline (HIP events,
+rocprofv3 child passes), the cfg 1 / 3 / 4 / 5 legs and the CPU baselines -- runs only with ``--full``.
+
+Extra objects in the line (``--full``):
   roofline      -- the chain kernel (text-tower instantiation, the longer one): algorithmic bytes / HIP-event time
                    measured on the stream the kernel runs on, against the 8 TB/s HBM peak
   roofline_step -- the WHOLE step against what really bounds it: the exact-fp32 matrix FLOPs the step executes (body
@@ -85,9 +91,19 @@ CFG5_BATCH = 128
 CFG5_MODEL = "ViT-L/14@336"
 
 
+def dump_outputs(directory, arrays):
+    """``--dump-outputs``: each array as ``directory/<name>.npy`` in float32 (called after the timed region)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), t.detach().float().cpu().numpy())
+    log("outputs written to %s: %s" % (directory, ", ".join(sorted(arrays))))
+
+
 def main_cfg5(args):
     """Optional leg (``--workload cfg5``; NOT the driver's default): BASELINE.json config 5's shape on this GPU -- CLIP
-    ViT-L/14@336 with the bf16 body of ``clip_model.CLIP.set_body_dtype``, batch 128 per GPU, all layers, eager."""
+    ViT-L/14@336 with the bf16 body of ``clip_model.CLIP.set_body_dtype``, batch 128 per GPU, all layers, eager.
+    The stand-alone timing of the attention-backward pair (``roofline``) runs with ``--full`` only."""
     rank, local_rank, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the hot path has no CPU fallback")
@@ -113,6 +129,7 @@ def main_cfg5(args):
             packed[:, :n_img] = R_image
             packed[:, n_img:] = R_text.reshape(CFG5_BATCH, -1)
             dist.all_gather_into_tensor(gathered, packed)
+        return R_text, R_image
 
     def sync():
         if world > 1:
@@ -125,7 +142,7 @@ def main_cfg5(args):
     torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        R_text, R_image = step()
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -133,24 +150,29 @@ def main_cfg5(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"R_text": R_text, "R_image": R_image})
     fl = bench_legs.cfg5_step_flops(CFG5_BATCH)
-    # our dominant kernel pair of this step: the bf16 attention backward of one image-tower layer (stand-alone launches)
-    us = kernel_time_us(attn_layer, 5, torch.cuda.current_stream())
+    roofline = None
+    if args.full:
+        # our dominant kernel pair of this step: the bf16 attention backward of one image-tower layer (stand-alone launches)
+        us = kernel_time_us(attn_layer, 5, torch.cuda.current_stream())
+        roofline = {"bound": "mfma", "kernel": "attn_bwd_q_v3_kernel + attn_bwd_kv_v4_kernel (one image-tower layer, "
+                                               "row-relevancy mode)", "achieved": round(attn_flops / us / 1e6, 1),
+                    "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(attn_flops / us / 1e6 / BF16_MFMA_PEAK_TFLOPS, 4),
+                    "traffic": None, "us_per_launch": round(us, 1),
+                    "note": "see profiles/ (newest rNN_cfg5_probe.txt) for the SQ counters of this pair"}
     if rank == 0:
         print(json.dumps({
             "metric": "relevancy maps/sec (fwd+bwd+rollout), CLIP ViT-L/14@336", "value": round(world * CFG5_BATCH / (ms * 1e-3), 2),
             "unit": "maps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "full": args.full,
             "config": {"workload": "BASELINE config 5 shape: CLIP ViT-L/14@336 (577 image tokens) image<->text relevancy, batch=128 "
                                    "per GPU, all 24+12 layers; bf16 body (GEMMs + image attention on the bf16 matrix cores, fp32 "
                                    "accumulation / LayerNorm / softmax / relevancy); random-init weights, synthetic inputs; eager",
                        "global_batch": world * CFG5_BATCH, "parallelism": "dp%d (independent batches, all-gather of maps)" % world,
                        "resident_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)},
-            "roofline": {"bound": "mfma", "kernel": "attn_bwd_q_v3_kernel + attn_bwd_kv_v4_kernel (one image-tower layer, "
-                                                    "row-relevancy mode)", "achieved": round(attn_flops / us / 1e6, 1),
-                         "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(attn_flops / us / 1e6 / BF16_MFMA_PEAK_TFLOPS, 4),
-                         "traffic": None, "us_per_launch": round(us, 1),
-                         "note": "see profiles/ (newest rNN_cfg5_probe.txt) for the SQ counters of this pair"},
+            "roofline": roofline,
             "roofline_step": {"bound": "mfma", "achieved": round(fl["total"] / (ms * 1e-3) / 1e12, 1), "peak": BF16_MFMA_PEAK_TFLOPS,
                               "unit": "TFLOP/s", "frac": round(fl["total"] / (ms * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS, 4),
                               "flop_per_step": fl},
@@ -457,15 +479,21 @@ _T0 = time.perf_counter()
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)     # ~1.4 s timed region
+    ap.add_argument("--steps", type=int, default=None,
+                    help="number of timed steps (default 100 for cfg2, ~1.2 s; 5 for --workload cfg5, 120 ms per step)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: the variant rates, the chain-kernel roofline "
+                         "(HIP events, rocprofv3 child passes), the cfg 1 / 3 / 4 / 5 legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the variant rates (eager, distinct images, last layer, trimmed): what the rocprofv3 "
-                         "kernel-split run uses, so that the trace holds headline steps only")
+                    help="with --full: skip the variant rates (eager, distinct images, last layer, trimmed), the roofline and "
+                         "the config legs (a plain run without --full is headline-only)")
     ap.add_argument("--no-config-legs", action="store_true",
-                    help="skip the cfg 1 / 3 / 4 / 5 legs (tools/bench_legs.py) reported under \"configs\"")
-    ap.add_argument("--legs", default=None, help="comma-separated subset of the config legs, e.g. cfg3,cfg5")
+                    help="with --full: skip the cfg 1 / 3 / 4 / 5 legs (tools/bench_legs.py) reported under \"configs\"")
+    ap.add_argument("--legs", default=None, help="with --full: comma-separated subset of the config legs, e.g. cfg3,cfg5")
     ap.add_argument("--cpu-baseline-worker", nargs=2, type=int, metavar=("BATCH", "REPS"), help=argparse.SUPPRESS)
     ap.add_argument("--cpu-leg-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--chain-worker", nargs=2, type=int, metavar=("BATCH", "LAUNCHES"), help=argparse.SUPPRESS)
@@ -475,6 +503,12 @@ def main():
     ap.add_argument("--workload", default="cfg2", choices=("cfg2", "cfg5"),
                     help="cfg2 (default, BASELINE.json's metric configuration) or the optional cfg-5 shape (ViT-L/14@336 bf16 body)")
     args = ap.parse_args()
+    if args.legs and not args.full:
+        ap.error("--legs selects config legs of a --full run")
+    if args.steps is None:
+        args.steps = 5 if args.workload == "cfg5" else 100
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_worker:
         cpu_baseline_worker(*args.cpu_baseline_worker)
         return
@@ -485,8 +519,6 @@ def main():
         chain_worker(*args.chain_worker)
         return
     if args.workload == "cfg5":
-        if args.steps == 100:
-            args.steps = 5          # 120 ms per step
         main_cfg5(args)
         return
 
@@ -559,7 +591,7 @@ def main():
     log("timed region")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        R_text, R_image = step()
     sync()
     elapsed = time.perf_counter() - t0
     if dist_on:
@@ -570,6 +602,9 @@ def main():
     value = world * BATCH / (elapsed / args.steps)
 
     log("timed region done: %.3f ms/step" % ms_per_step)
+    if args.dump_outputs and rank == 0:     # the graph's output buffers, as the last replay left them
+        dump_outputs(args.dump_outputs, {"R_text": R_text, "R_image": R_image})
+    extras = args.full and not args.headline_only
 
     def rate(fn, reps):
         for _ in range(2):
@@ -582,7 +617,7 @@ def main():
         return BATCH / ((time.perf_counter() - t0) / reps)
 
     variants = None
-    if not args.headline_only:
+    if extras:
         reps = min(args.steps, 30)
         eager = rate(lambda: ce.interpret(image, texts, model, device, 0, 0), reps)
         # ---- variants, reported beside the headline (all eager unless noted)
@@ -624,7 +659,7 @@ def main():
             torch.cuda.synchronize()
 
     roofline = None
-    if not args.headline_only:
+    if extras:
         # ---- roofline of the chain kernel, HIP events on the launch stream, buffers as the last step left them
         vis, txt = model.visual.transformer, model.transformer
         stream = torch.cuda.current_stream()
@@ -783,7 +818,7 @@ def main():
                      "kernel_time_split_source": os.path.relpath(split_file, ROOT) if split_file else None}
 
     configs = None
-    if world == 1 and not args.headline_only and not args.no_config_legs:
+    if world == 1 and extras and not args.no_config_legs:
         # the other BASELINE.json configurations, each a bounded leg of its own (tools/bench_legs.py); the headline's graph
         # and slabs are released first (cfg 5 wants ~12 GB)
         import gc
@@ -807,7 +842,7 @@ def main():
             "metric": "relevancy maps/sec (fwd+bwd+rollout), CLIP ViT-B/32", "value": round(value, 2),
             "unit": "maps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": "CLIP ViT-B/32 image<->text relevancy, batch=64 fp32 per GPU, all 12+12 layers "
                                    "(start_layer=0); random-init weights, synthetic image + token ids",
                        "global_batch": world * BATCH, "parallelism": "dp%d (independent batches, all-gather of maps)" % world,
@@ -824,7 +859,7 @@ def main():
             "roofline_step": roofline_step,
             "configs": configs,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log("cpu baseline (child process, <= 240 s)")
             line["cpu_baseline"] = cpu_baseline()
             log("cpu baseline done")

@@ -11,7 +11,7 @@ timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -12 | tee $OUT/pytest_
 cp gpurun_out/parity_errors.json $OUT/parity.json 2>/dev/null
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/smoke.txt
 fi
-timeout 900 python bench.py --steps 100 --warmup 5 > $OUT/bench.json 2> $OUT/bench.log; tail -2 $OUT/bench.log; cut -c1-400 $OUT/bench.json
+timeout 900 python bench.py --steps 100 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.log; tail -2 $OUT/bench.log; cut -c1-400 $OUT/bench.json
 # kernel trace of headline steps only (2 capture warm-ups + 3 warm-up replays + 20 timed replays = 25 steps in the trace)
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --headline-only > $OUT/bench_traced.json 2> $OUT/trace.log
 python tools/prof_summary.py $OUT/trace/bench_results.db "" --by-grid > $OUT/kernel_stats.txt 2>&1; grep mmx $OUT/kernel_stats.txt | cut -c1-200
@@ -20,9 +20,9 @@ timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OU
 timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --headline-only > /dev/null 2> $OUT/pmc_write.log
 python tools/pmc_summary.py $OUT/pmc_fetch/bench_counter_collection.csv mmx:: > $OUT/pmc_fetch.txt; python tools/pmc_summary.py $OUT/pmc_write/bench_counter_collection.csv mmx:: > $OUT/pmc_write.txt
 cat $OUT/pmc_fetch.txt $OUT/pmc_write.txt
-# trace of the DEFAULT command's legs (headline + variants + the stand-alone chain launches the roofline is measured on + the
+# trace of the --full command's legs (headline + variants + the stand-alone chain launches the roofline is measured on + the
 # cfg 1 / 3 / 4 / 5 legs): the chain kernels' min / avg there include the 2 x 21 stand-alone launches
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace_full -o bench -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2> $OUT/trace_full.log
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace_full -o bench -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > /dev/null 2> $OUT/trace_full.log
 python tools/prof_summary.py $OUT/trace_full/bench_results.db "self_chain" --by-grid > $OUT/chain_kernel_trace.txt 2>&1; cat $OUT/chain_kernel_trace.txt | cut -c1-200
 python tools/prof_summary.py $OUT/trace_full/bench_results.db "" --by-grid 2>&1 | grep -E "kernel  |mmx" | head -70 | cut -c1-200 > $OUT/cfg_legs.txt
 # round 4: the bi-modal schedule kernel (one workgroup per sample vs two-phase) and the LRP route's cost

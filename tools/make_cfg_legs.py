@@ -40,7 +40,7 @@ if c5.get("ms"):
                % (c5["ms"], c5["rate"], c5.get("variant_trim_text_padding", {}).get("ms", "?"), tag))
 table = os.path.join(src, "cfg_legs.txt")
 if os.path.exists(table):
-    out += ["#", "# ---- kernels of the DEFAULT command's legs (rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline;",
+    out += ["#", "# ---- kernels of the --full command's legs (rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline;",
             "#      headline + variants + the four legs in one process; tools/prof_summary.py --by-grid, our kernels only):"]
     out += open(table).read().splitlines()
 dst = os.path.join(ROOT, "profiles", "%s_cfg_legs.txt" % tag)
