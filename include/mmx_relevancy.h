@@ -400,6 +400,30 @@ int mmx_attn_capture_bwd_rowrel(const void* q_dev, const void* k_dev, const void
                                 int need_dqkv, const void* rel_in_dev, void* rel_out_dev,
                                 void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Row-relevancy mode on the EXACT-fp32 kernels (ViT `generate_relevance` / CLIP `interpret` over a batch of distinct images:
+ * both need only row 0 of R): the same row update as mmx_attn_capture_bwd_rowrel with the products on
+ * v_mfma_f32_16x16x4_f32, as in mmx_attn_capture_bwd_ex.  N <= 128: the whole-head kernel reduces one partial row per head;
+ * longer sequences: the streaming query-side kernel, one partial row per (head, 64-row tile); both summed in a fixed order
+ * (deterministic).  dq / dk / dv are bit-identical to mmx_attn_capture_bwd_ex on the same arguments; clamp(NaN, 0) = NaN as in
+ * mmx_avg_heads_vecmat.  Same arguments as mmx_attn_capture_bwd_rowrel; `slab_dtype` must be MMX_F32 (no flags); Nq == Nk;
+ * `dprobs_dev` may be NULL, except with need_dqkv on the streaming path (its key side reads dP back): MMX_EINVAL there. */
+size_t mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(int B, int H, int Nq, int Nk);
+int mmx_attn_capture_bwd_rowrel_f32(const void* q_dev, const void* k_dev, const void* v_dev,
+                                    int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                                    int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                    int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                                    const void* probs_dev, int64_t probs_sb, int slab_dtype,
+                                    const void* do_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                                    const void* fwd_o_dev, int64_t fo_sb, int64_t fo_sh, int64_t fo_sn,
+                                    void* dprobs_dev,
+                                    void* dq_dev, void* dk_dev, void* dv_dev,
+                                    int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
+                                    int64_t dk_sb, int64_t dk_sh, int64_t dk_sn,
+                                    int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
+                                    int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                                    int need_dqkv, const void* rel_in_dev, void* rel_out_dev,
+                                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2-DETR: the decoder half of DETR's rule schedule for ROWS of R_q_i -- rules 5, 6, 7 and 10 with
  * eq. 8-9 and the NaN policy of DETR/modules/ExplanationGenerator.py:19-53 (rule functions), :120-140 (handle_co_attn_*) --

@@ -5,6 +5,7 @@ Reference entry points mirrored here:
     -- CLIP_explainability.ipynb cell 6 (batched: one image, B texts) -> ``(text_relevance [B,Nt,Nt], image_relevance [B,Ni-1])``
   * ``interpret_single(image, text, model, device, index=None)``
     -- CLIP/example.py:8-32 (one image, K texts, explains ``logits_per_image[0, index]``) -> ``image_relevance [Ni-1]``
+    (``clip_example.interpret`` under the reference's name); ``interpret_batch`` runs it over B distinct images in one pass
   * ``text_scores(text_encoding, R_text)`` -- notebook cell 8:5-7 post-processing (on device)
 
 What is different under the hood (results agree to fp32 rounding, see tests/test_gpu_clip.py):
@@ -225,6 +226,34 @@ def interpret_single(image, text, model, device, index=None):
                                  [vb.grads[l] for l in range(vis.layers)], 1)[0]
     R[0, 0] = 0
     return R[0, 1:]
+
+
+def interpret_batch(images, texts, model, device, index=None):
+    """Zero-shot explanation of B DISTINCT images against C class prompts in one pass -> ``image_relevance [B, Ni-1]``.
+
+    Row b equals ``interpret_single(images[b:b+1], texts, model, device, index=index[b])`` (CLIP/example.py:8-32, one image
+    per call).  ``index``: int tensor ``[B]`` of prompt indices, or ``None`` for each image's arg-max prompt (picked on the
+    device).  The C prompts are encoded ONCE, forward only: the gradient of ``logits_per_image[b, c]`` with respect to image
+    b depends on text feature c only, so the text tower runs no backward.  The image tower runs at batch B and carries row 0
+    of its relevancy matrix through its backward (``Transformer.backward_tape(rel_row=...)``: the exact-fp32 row mode of the
+    capture op on an fp32 body -- whole-head kernel at N <= 128, streaming kernels beyond; no gradient slabs are written)."""
+    B = images.shape[0]
+    with torch.no_grad():
+        txt_feat, _ = model.encode_text_tape(texts, first_grad_layer=model.transformer.layers)   # no tape kept: no backward
+        img_feat, img_state = model.visual.forward_tape(images.type(model.dtype), first_grad_layer=0, grads=False)
+    with torch.enable_grad():
+        image_features = img_feat.detach().requires_grad_(True)
+        logits_per_image, _ = model.logits(image_features, txt_feat.detach())
+        if index is None:
+            idx = logits_per_image.detach().argmax(-1)
+        else:
+            idx = torch.as_tensor(index, device=logits_per_image.device).reshape(-1)
+            if idx.numel() != B:
+                raise ValueError("interpret_batch: %d indices for %d images" % (idx.numel(), B))
+        one_hot = torch.zeros_like(logits_per_image).scatter_(1, idx.reshape(B, 1).long(), 1.0)
+        torch.autograd.backward(logits_per_image, grad_tensors=one_hot, inputs=[image_features])
+    row = model.visual.backward_tape(img_state, image_features.grad, 0, cls_row=True)
+    return row[:, 1:]
 
 
 def text_scores(text_encoding, R_text):

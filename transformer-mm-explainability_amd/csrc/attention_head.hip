@@ -409,7 +409,10 @@ __global__ __launch_bounds__(1024) void attn_fwd_head_kernel(const AttnFwdArgs a
 
 // ------------------------------------------------------------------------------------------------------- backward
 // (NTK >= 7 keeps 100+ live registers per lane: those instantiations are capped at 8 waves so that they get 256 VGPRs)
-template <int DP, int NTK, bool IOH = false>
+// REL (row-relevancy mode, mmx_attn_capture_bwd_rowrel_f32; see AttnBwdArgs::rel_v): phase A's dP and P registers also give this
+// head's partial row  part[k] = sum_q rel_v[b][q] * clamp(dP * P, 0)[q][k]  -> rel_part[b][h][k]: the 16 rows of a wave on DPP
+// (group16_sum), the waves in LDS in wave order (deterministic).  dQ / dK / dV are computed exactly as without it.
+template <int DP, int NTK, bool IOH = false, bool REL = false>
 __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(const AttnBwdArgs a) {
     constexpr int LSA = DP + 8, LSB = DP + 4, KK = DP / 16, NPk = NTK * 16, SS = NPk + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -445,6 +448,8 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
 #pragma unroll
     for (int t = 0; t < NTK; ++t) preg[t] = load_chunk(prow, t * 16 + 4 * g, a.Nk, qv);
     const float* vb = a.v + b * a.vs.sb + h * a.vs.sh;
+    float vq = 0.f;     // REL: this row's weight, loaded with the other operands (retired by the staging barrier)
+    if constexpr (REL) vq = a.rel_v[static_cast<int64_t>(b) * a.Nq + (qv ? q : a.Nq - 1)];
     if (a.need_dqkv) {
         load_rows16<DP>(qreg, a.q + b * a.qs.sb + h * a.qs.sh, a.qs.sn, q, a.Nq, a.D, g, q_first ? a.scale : 1.f);
         stage_pair<DP, 4>(Vs, LSA, vb, a.vs.sn, Ks, LSB, a.k + b * a.ks.sb + h * a.ks.sh, a.ks.sn, a.Nk, NPk, a.D, tid,
@@ -455,6 +460,9 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     MMX_TL_MARK();                                                   // 1: V / K staged (this wave's part)
     lds_barrier();
     MMX_TL_MARK();                                                   // 2: after the first barrier
+    // REL: consume the weight here, where the staging has retired its load: used after the dP stores, it cost a vmcnt(0) on them
+    float w = REL && qv ? vq : 0.f;
+    if constexpr (REL) asm volatile("" : "+v"(w));   // (pins the select here: the compiler sinks it to its use otherwise)
 
     // ---- phase A: dP^T tiles, dP -> slab, delta, dS (all in registers: acc[t][r] <-> [q][key = 16t + 4g + r])
     f32x4 acc[NTK];
@@ -466,9 +474,28 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     float dot = 0.f;
 #pragma unroll
     for (int t = 0; t < NTK; ++t) {
-        store_chunk(dprow, t * 16 + 4 * g, a.Nk, qv, acc[t]);      // the captured attention gradient
+        if (!REL || a.dprobs) store_chunk(dprow, t * 16 + 4 * g, a.Nk, qv, acc[t]);      // the captured attention gradient
 #pragma unroll
         for (int r = 0; r < 4; ++r) dot += acc[t][r] * preg[t][r];
+    }
+    if constexpr (REL) {
+        // rows past Nq hold dO = 0 and P = 0 (their products are zeros) and weigh 0; the load is clamped, not branched
+        float* relw = reinterpret_cast<float*>(live_tab + 16);   // [NTQ][NPk] per-wave partial rows
+#pragma unroll
+        for (int t = 0; t < NTK; ++t) {
+            f32x4 c;
+#pragma unroll
+            // dP * P as fma(dP, P, +0): the same value (up to the sign of a zero), but not a product the compiler can share with
+            // delta's fma chain above -- sharing it split that chain into mul + add and moved dQ / dK by an ulp
+            for (int r = 0; r < 4; ++r) c[r] = group16_sum(w * relu_nan(__builtin_fmaf(acc[t][r], preg[t][r], 0.f)));
+            if (c16 == 0) *reinterpret_cast<f32x4*>(relw + wave * NPk + t * 16 + 4 * g) = c;
+        }
+        lds_barrier();
+        for (int k = tid; k < a.Nk; k += nthreads) {
+            float sum = 0.f;
+            for (int w2 = 0; w2 < NTQ; ++w2) sum += relw[w2 * NPk + k];
+            a.rel_part[head * a.Nk + k] = sum;
+        }
     }
     if (!a.need_dqkv) return;
     // key tiles whose probabilities are exact zeros for every row of this strip (with_tile_count): bit t of `live`, wave-uniform; published
@@ -595,10 +622,11 @@ void attn_head_enable(int on) { g_attn_head = on & 1; g_attn_head_stagger = on >
 
 static size_t fwd_head_lds(int DP, int NTK) { return sizeof(float) * NTK * 16 * (2 * DP + 12); }
 
-static size_t bwd_head_lds(int DP, int NTK, int NTQ) {
+static size_t bwd_head_lds(int DP, int NTK, int NTQ, bool rel = false) {
     const size_t ab = static_cast<size_t>(NTK) * 16 * (2 * DP + 12);
     const size_t c = static_cast<size_t>(NTQ) * 16 * (NTK * 16 + 4 + DP + 4);
-    return sizeof(float) * ((ab > c ? ab : c) + static_cast<size_t>(NTQ));      // + the strips' live-tile words
+    // + the strips' live-tile words (REL: 16 words, then the [NTQ][16 NTK] partial rows)
+    return sizeof(float) * ((ab > c ? ab : c) + (rel ? 16 + static_cast<size_t>(NTQ) * NTK * 16 : static_cast<size_t>(NTQ)));
 }
 
 template <typename K, typename A>
@@ -633,21 +661,21 @@ static int fwd_head_dispatch(const AttnFwdArgs& a, int NTK, int threads, size_t 
     return MMX_ENOTSUP;
 }
 
-#define MMX_HEAD_CASE_IO(DPV, N, IO)                                                                          \
+#define MMX_HEAD_CASE_IO(DPV, N, IO, RL)                                                                      \
     case N:                                                                                                    \
-        return launch_head(attn_bwd_head_kernel<DPV, N, IO>, a, threads, lds, s, "attn_bwd_head_kernel")
+        return launch_head(attn_bwd_head_kernel<DPV, N, IO, RL>, a, threads, lds, s, "attn_bwd_head_kernel")
 
-template <int DP, bool IOH>
+template <int DP, bool IOH, bool REL = false>
 static int bwd_head_dispatch(const AttnBwdArgs& a, int NTK, int threads, size_t lds, hipStream_t s) {
     switch (NTK) {
-        MMX_HEAD_CASE_IO(DP, 1, IOH);
-        MMX_HEAD_CASE_IO(DP, 2, IOH);
-        MMX_HEAD_CASE_IO(DP, 3, IOH);
-        MMX_HEAD_CASE_IO(DP, 4, IOH);
-        MMX_HEAD_CASE_IO(DP, 5, IOH);
-        MMX_HEAD_CASE_IO(DP, 6, IOH);
-        MMX_HEAD_CASE_IO(DP, 7, IOH);
-        MMX_HEAD_CASE_IO(DP, 8, IOH);
+        MMX_HEAD_CASE_IO(DP, 1, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 2, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 3, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 4, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 5, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 6, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 7, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 8, IOH, REL);
     }
     return MMX_ENOTSUP;
 }
@@ -685,8 +713,15 @@ int attn_bwd_head_try(const AttnBwdArgs& a_in, hipStream_t s, int* rc_out) {
         return 0;
     if (a.io_bf16 && a.need_dqkv && (!io_ok(a.dq, a.dqs) || !io_ok(a.dk, a.dks) || !io_ok(a.dv, a.dvs))) return 0;
     const int DP = a.D <= 32 ? 32 : 64, NTK = (a.Nk + 15) / 16, NTQ = (a.Nq + 15) / 16, threads = 64 * NTQ;
-    const size_t lds = bwd_head_lds(DP, NTK, NTQ);
+    const bool rel = a.rel_v != nullptr;
+    const size_t lds = bwd_head_lds(DP, NTK, NTQ, rel);
     if (lds > 160 * 1024 || (NTK >= 7 && NTQ > 8)) return 0;
+    if (rel && (a.io_bf16 || a.Nq != a.Nk)) return 0;
+    if (rel) {
+        *rc_out = DP == 32 ? bwd_head_dispatch<32, false, true>(a, NTK, threads, lds, s) : bwd_head_dispatch<64, false, true>(a, NTK, threads, lds, s);
+        if (*rc_out == MMX_OK) *rc_out = rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);
+        return 1;
+    }
     if (a.io_bf16)
         *rc_out = DP == 32 ? bwd_head_dispatch<32, true>(a, NTK, threads, lds, s) : bwd_head_dispatch<64, true>(a, NTK, threads, lds, s);
     else

@@ -411,6 +411,11 @@ static size_t rowrel_part_bytes(int B, int H, int Nq, int Nk) {
     return (sizeof(float) * static_cast<size_t>(B) * H * nrt * Nk + 255) / 256 * 256;
 }
 
+extern "C" size_t mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(int B, int H, int Nq, int Nk) {
+    // delta | partial relevancy rows (one per (head, 64-row tile) on the streaming path; the whole-head kernel uses H of them)
+    return rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk);
+}
+
 extern "C" size_t mmx_attn_capture_bwd_rowrel_workspace_bytes(int B, int H, int Nq, int Nk) {
     // delta | partial relevancy rows | bf16 images of the shared operands (third-generation kernels, attention_bf16_v3.hip)
     return rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk) + mmx::attn_bwd_bf16_v3_prep_bytes(H, Nk);
@@ -425,12 +430,21 @@ static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev
                                        int64_t dq_sn, int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t dv_sb,
                                        int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D, float scale,
                                        int scale_mode, int need_dqkv, void* workspace_dev, size_t workspace_bytes,
-                                       void* stream, const void* rel_in_dev, void* rel_out_dev) {
+                                       void* stream, const void* rel_in_dev, void* rel_out_dev, bool rel_f32 = false) {
     const bool rel = rel_in_dev != nullptr;
     MMX_CHECK_ARG(v_dev && probs_dev && do_dev && (dprobs_dev || rel), "mmx_attn_capture_bwd: null pointer");
     const int io_bf16 = (slab_dtype & MMX_ATTN_IO_BF16) ? 1 : 0;
     // (MMX_ATTN_IO_BF16 without MMX_ATTN_MMA_BF16: exact-fp32 arithmetic on a bf16 gradient stream -- the whole-head kernels only)
-    if (rel) {
+    if (rel && rel_f32) {
+        MMX_CHECK_ARG(rel_out_dev && Nq == Nk, "mmx_attn_capture_bwd_rowrel_f32: needs rel_out and self-attention (Nq == Nk)");
+        MMX_CHECK_ARG(slab_dtype == MMX_F32, "mmx_attn_capture_bwd_rowrel_f32: fp32 slabs and exact-fp32 kernels only (dtype %d)",
+                      slab_dtype);
+        if (!workspace_dev || workspace_bytes < mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk)) {
+            set_error("mmx_attn_capture_bwd_rowrel_f32: workspace %zu < %zu", workspace_bytes,
+                      mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk));
+            return MMX_EWORKSPACE;
+        }
+    } else if (rel) {
         MMX_CHECK_ARG(rel_out_dev && Nq == Nk, "mmx_attn_capture_bwd_rowrel: needs rel_out and self-attention (Nq == Nk)");
         MMX_CHECK_ARG(slab_dtype & MMX_ATTN_MMA_BF16, "mmx_attn_capture_bwd_rowrel: MMX_ATTN_MMA_BF16 kernels only");
         if (!workspace_dev || workspace_bytes < mmx_attn_capture_bwd_rowrel_workspace_bytes(B, H, Nq, Nk)) {
@@ -472,6 +486,17 @@ static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev
     a.rel_part = rel ? reinterpret_cast<float*>(static_cast<char*>(workspace_dev) + rowrel_delta_bytes(B, H, Nq)) : nullptr;
     a.rel_out = static_cast<float*>(rel_out_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (rel && rel_f32) {
+        if (attn_bwd_head_try(a, s, &rc)) return rc;    // N <= 128: one partial row per head
+        // the exact-fp32 key-side streaming kernel reads dP back from the slab (the row is extra work, not another schedule)
+        MMX_CHECK_ARG(dprobs_dev || !need_dqkv, "mmx_attn_capture_bwd_rowrel_f32: this shape runs the streaming kernels, whose "
+                      "key side reads dP back: need_dqkv needs a dprobs slab");
+        if (!attn_bwd_stream_try(a, s, &rc)) {
+            set_error("mmx_attn_capture_bwd_rowrel_f32: needs head_dim %% 4 == 0 (<= 64) and 16-byte aligned views");
+            return MMX_ENOTSUP;
+        }
+        return rc;      // (the path that ran has also launched rel_row_update over the partial rows it made)
+    }
     if (rel) {
         const size_t used = rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk);
         if (attn_bwd_bf16_v3_try(a, static_cast<char*>(workspace_dev) + used, workspace_bytes - used, s, &rc)) return rc;
@@ -540,4 +565,22 @@ extern "C" int mmx_attn_capture_bwd_rowrel(const void* q_dev, const void* k_dev,
                          slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
                          dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
                          scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev);
+}
+
+extern "C" int mmx_attn_capture_bwd_rowrel_f32(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
+                                               int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                               int64_t v_sb, int64_t v_sh, int64_t v_sn, const void* probs_dev,
+                                               int64_t probs_sb, int slab_dtype, const void* do_dev, int64_t o_sb,
+                                               int64_t o_sh, int64_t o_sn, const void* fwd_o_dev, int64_t fo_sb,
+                                               int64_t fo_sh, int64_t fo_sn, void* dprobs_dev, void* dq_dev, void* dk_dev,
+                                               void* dv_dev, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn, int64_t dk_sb,
+                                               int64_t dk_sh, int64_t dk_sn, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
+                                               int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                                               int need_dqkv, const void* rel_in_dev, void* rel_out_dev,
+                                               void* workspace_dev, size_t workspace_bytes, void* stream) {
+    MMX_CHECK_ARG(rel_in_dev && rel_out_dev, "mmx_attn_capture_bwd_rowrel_f32: null relevancy row");
+    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
+                         slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
+                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
+                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev, true);
 }

@@ -980,6 +980,25 @@ int launch_bwd_bf16(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
     return rc;
 }
 
+// exact-fp32 kernels in row-relevancy mode (mmx_attn_capture_bwd_rowrel_f32): the query-side kernel with REL, the key-side
+// kernel as without it; fp32 slabs only
+int launch_bwd_rel_f32(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
+    const bool small_d = a.D <= 32;
+    constexpr size_t kRel = sizeof(float) * 16 * kTile;
+    int rc = small_d ? launch_stream(attn_bwd_q_stream_kernel<32, MMX_F32, false, true>, a, gq, stream_lds_bytes<32>(2) + kRel, s,
+                                     "attn_bwd_q_stream_kernel<32, rel>")
+                     : launch_stream(attn_bwd_q_stream_kernel<64, MMX_F32, false, true>, a, gq, stream_lds_bytes<64>(2) + kRel, s,
+                                     "attn_bwd_q_stream_kernel<64, rel>");
+    if (rc == MMX_OK && a.need_dqkv) {
+        rc = small_d ? launch_stream(attn_bwd_kv_stream_kernel<32, MMX_F32, false>, a, gk, stream_lds_bytes<32>(2), s,
+                                     "attn_bwd_kv_stream_kernel<32>")
+                     : launch_stream(attn_bwd_kv_stream_kernel<64, MMX_F32, false>, a, gk, stream_lds_bytes<64>(2), s,
+                                     "attn_bwd_kv_stream_kernel<64>");
+    }
+    if (rc) return rc;
+    return rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H * ((a.Nq + kRows - 1) / kRows), a.Nk, 1.0f / a.H, s);
+}
+
 template <int DT>
 int launch_bwd_dt(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
     if (!a.mma_bf16) return launch_bwd_mm<DT, false>(a, gq, gk, s);
@@ -1020,11 +1039,16 @@ int attn_fwd_stream_try(const AttnFwdArgs& a, hipStream_t s, int* rc_out) {
 
 int attn_bwd_stream_try(const AttnBwdArgs& a, hipStream_t s, int* rc_out) {
     if ((!g_attn_stream && a.slab_dt == MMX_F32 && !a.mma_bf16) || a.D % 4 || a.D > 64) return 0;
-    if ((a.rel_v || a.io_bf16) && !a.mma_bf16) return 0;
+    if (a.io_bf16 && !a.mma_bf16) return 0;
+    if (a.rel_v && !a.mma_bf16 && a.slab_dt != MMX_F32) return 0;
     if (a.mma_bf16 && attn_bwd_bf16_try(a, s, rc_out)) return 1;      // second-generation bf16 kernels (attention_bf16.hip)
     if (!aligned16(a.v, a.vs) || !aligned16(a.dout, a.os)) return 0;
     if (a.need_dqkv && (!aligned16(a.q, a.qs) || !aligned16(a.k, a.ks))) return 0;
     dim3 gq(((a.Nq + kRows - 1) / kRows) * a.H * a.B), gk(((a.Nk + kRows - 1) / kRows) * a.H * a.B);
+    if (a.rel_v && !a.mma_bf16) {
+        *rc_out = launch_bwd_rel_f32(a, gq, gk, s);
+        return 1;
+    }
     switch (a.slab_dt) {
         case MMX_F32: *rc_out = launch_bwd_dt<MMX_F32>(a, gq, gk, s); break;
         case MMX_F16: *rc_out = launch_bwd_dt<MMX_F16>(a, gq, gk, s); break;

@@ -871,8 +871,10 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
     ``batch``: shared-forward mode -- q/k/v/probs come from ONE forward (batch 1) and are broadcast (stride 0) over the
     ``batch`` upstream gradients in ``d_o``; dq/dk/dv/dprobs are per sample.
     ``o``: the forward's output (same layout as ``q``), optional: saves the long-sequence kernels a sweep over the keys.
-    ``rel_row`` (``[B, N]`` fp32; row-relevancy mode, ``mmx_attn_capture_bwd_rowrel``): returns
-    ``(dq, dk, dv, rel_row + rel_row . mean_h clamp(dP * P, 0))``; ``dprobs_out`` may then be ``None`` (dP is not stored)."""
+    ``rel_row`` (``[B, N]`` fp32; row-relevancy mode, ``mmx_attn_capture_bwd_rowrel`` with ``mma_bf16=True``,
+    ``mmx_attn_capture_bwd_rowrel_f32`` on the exact-fp32 kernels otherwise): returns
+    ``(dq, dk, dv, rel_row + rel_row . mean_h clamp(dP * P, 0))``; ``dprobs_out`` may then be ``None`` (dP is not stored;
+    exact fp32 beyond the whole-head shapes with ``need_dqkv``: the key-side kernel reads dP back, from a scratch slab)."""
     _dev(q, k, v, probs, d_o, dprobs_out, rel_row)
     if probs.dtype not in _DTYPES or (dprobs_out is not None and probs.dtype != dprobs_out.dtype):
         raise MMXError("attn_capture_bwd: probs / dprobs slabs must share one of fp32 / fp16 / bf16")
@@ -913,6 +915,27 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
     zero3 = (0, 0, 0)
     if o is not None and (o.dtype != torch.float32 or o.stride(-1) != 1):
         o = None                                               # only a hint: fall back to the two-sweep form
+    if rel_row is not None and not mma_bf16:
+        if rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (B, Nq) or Nq != Nk or probs.dtype != torch.float32:
+            raise MMXError("attn_capture_bwd: exact-fp32 rel_row needs fp32 [B, N] rows and fp32 slabs of a self-attention")
+        if io_bf16:
+            raise MMXError("attn_capture_bwd: exact-fp32 rel_row needs an fp32 d_o")
+        rel_row = rel_row.contiguous()
+        rel_out = torch.empty_like(rel_row)
+        dprobs = dprobs_out
+        if dprobs is None and need_dqkv and not head_kernel_shape(Nq, Nk, D, probs.dtype):
+            dprobs = _workspace(4 * B * H * Nq * Nk, q.device, "attn_rowrel_dp").view(torch.float32)
+        need = lib().mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk)
+        ws = _workspace(need, q.device, "attn_bwd")
+        check(lib().mmx_attn_capture_bwd_rowrel_f32(
+            _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
+            _p(probs), probs_sb, _DTYPES[probs.dtype], _p(d_o), *_bhnd_strides(d_o, layout),
+            _p(o), *(_bhnd_strides(o, layout) if o is not None else zero3), _p(dprobs), _p(dq), _p(dk), _p(dv),
+            *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
+            *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
+            B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(rel_row), _p(rel_out), _p(ws), need, _stream()),
+            "mmx_attn_capture_bwd_rowrel_f32")
+        return dq, dk, dv, rel_out
     if rel_row is not None:
         if not mma_bf16 or rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (B, Nq) or Nq != Nk:
             raise MMXError("attn_capture_bwd: rel_row must be fp32 [B, N] of a self-attention, with mma_bf16=True")

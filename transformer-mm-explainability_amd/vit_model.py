@@ -129,12 +129,12 @@ class VisionTransformer(nn.Module):
         bf16 MFMA with fp32 accumulation and results, see ``clip_model.Transformer._gemm``)."""
         return ops.backward_gemm(x, weight, getattr(self, "backward_gemm_dtype", torch.float32))
 
-    def _slabs(self, batch, n_tokens, device, shared=False):
+    def _slabs(self, batch, n_tokens, device, shared=False, grads=True):
         b = self.buffers_
         dtype = getattr(self, "capture_dtype", torch.float32)   # torch.float16 / bfloat16: half-size slabs (N >= ~128)
-        if b is None or not b.matches(self.depth, batch, self.num_heads, n_tokens, n_tokens, device, shared, dtype):
+        if b is None or not b.matches(self.depth, batch, self.num_heads, n_tokens, n_tokens, device, shared, dtype, grads):
             self.buffers_ = b = CaptureBuffers(self.depth, batch, self.num_heads, n_tokens, n_tokens, device=device,
-                                               shared_probs=shared, dtype=dtype)
+                                               shared_probs=shared, dtype=dtype, grads=grads)
         return b
 
     def _embed(self, x):
@@ -155,8 +155,17 @@ class VisionTransformer(nn.Module):
     def forward_shared(self, x, n_targets):
         """One forward at batch 1 that keeps what the batched backward needs.  Returns ``(logits [1, C], state)``."""
         x = self._embed(x)
-        N, E = x.shape[1], x.shape[2]
-        buf = self._slabs(n_targets, N, x.device, shared=True)
+        return self._tape_forward(x, self._slabs(n_targets, x.shape[1], x.device, shared=True))
+
+    @torch.no_grad()
+    def forward_tape(self, x, grads=True):
+        """``forward_shared`` over B DISTINCT images (per-sample activations and probability slabs).  ``grads=False``:
+        probabilities-only slabs, for ``backward_tape(..., rel_row=...)``, which stores no dP.  Returns ``(logits [B, C], state)``."""
+        x = self._embed(x)
+        return self._tape_forward(x, self._slabs(x.shape[0], x.shape[1], x.device, grads=grads))
+
+    def _tape_forward(self, x, buf):
+        B, N, E = x.shape
         tape = []
         # every LayerNorm but the first is fused with the residual add that produces its input (ops.add_layernorm: one pass
         # writes the sum, the normalised rows and their statistics)
@@ -164,14 +173,14 @@ class VisionTransformer(nn.Module):
         _, h1, mean1, rstd1 = ops.add_layernorm(x, None, first.weight, first.bias, first.eps)
         for l, blk in enumerate(self.blocks):
             at = blk.attn
-            qkv = at.qkv(h1).view(1, N, 3, at.num_heads, at.head_dim)
+            qkv = at.qkv(h1).view(B, N, 3, at.num_heads, at.head_dim)
             o = ops.attn_capture_fwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buf.probs[l], 1.0 / at.scale,
                                      _lib.SCALE_SCORES, None, layout="bnhd")
-            x1, h2, mean2, rstd2 = ops.add_layernorm(x, at.proj(o.view(1, N, E)), blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+            x1, h2, mean2, rstd2 = ops.add_layernorm(x, at.proj(o.view(B, N, E)), blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
             m = blk.mlp.fc1(h2)
             mlp_out = blk.mlp.fc2(F.gelu(m))
             tape.append((x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o))
-            at.attention_map, at.attn_gradients = buf.probs[l], buf.grads[l]
+            at.attention_map, at.attn_gradients = buf.probs[l], (buf.grads[l] if buf.grads is not None else None)
             nxt = self.blocks[l + 1].norm1 if l + 1 < self.depth else self.norm
             x, h1, mean1, rstd1 = ops.add_layernorm(x1, mlp_out, nxt.weight, nxt.bias, nxt.eps)
         return self.head(h1[:, 0]), (tape, x, mean1, rstd1)
@@ -209,6 +218,45 @@ class VisionTransformer(nn.Module):
                 break
             d_h1 = self._gemm(dqkv.view(K, N, 3 * E), at.qkv.weight)
             dx = ops.layernorm_bwd_add(d_h1, x, mean1, rstd1, blk.norm1.weight, d_x1)
+
+    @torch.no_grad()
+    def backward_tape(self, state, d_logits, rel_row=None, on_layer_done=None):
+        """``backward_shared`` over the B distinct images of ``forward_tape``: ``d_logits [B, C]``, one upstream gradient per
+        image.  Without ``rel_row``: fills ``grads`` of every block.  ``rel_row [B, N]`` (fp32): the row-relevancy mode --
+        every layer's capture backward also carries ``x <- x + x . mean_h clamp(dP * P, 0)`` top-down (exact fp32, no dP
+        stored) and the final row is returned.  ``on_layer_done(l)`` as in ``backward_shared``."""
+        tape, x_last, mean, rstd = state
+        B = d_logits.shape[0]
+        N, E = x_last.shape[1], x_last.shape[2]
+        d_f = torch.zeros(B, N, E, dtype=torch.float32, device=d_logits.device)
+        d_f[:, 0, :] = torch.matmul(d_logits, self.head.weight)
+        dx = ops.layernorm_bwd_add(d_f, x_last, mean, rstd, self.norm.weight)
+        buf = self.buffers_
+        row = rel_row
+        for l in range(self.depth - 1, -1, -1):
+            blk = self.blocks[l]
+            at = blk.attn
+            x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o_fwd = tape[l]
+            d_a = self._gemm(dx, blk.mlp.fc2.weight)
+            d_m = torch.ops.aten.gelu_backward(d_a, m)
+            d_h2 = self._gemm(d_m, blk.mlp.fc1.weight)
+            d_x1 = ops.layernorm_bwd_add(d_h2, x1, mean2, rstd2, blk.norm2.weight, dx)
+            d_o = self._gemm(d_x1, at.proj.weight).view(B, N, at.num_heads, at.head_dim)
+            need = l > 0
+            dqkv = torch.empty(B, N, 3, at.num_heads, at.head_dim, dtype=torch.float32, device=dx.device) if need else None
+            out = (dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2]) if need else None
+            grads = buf.grads[l] if buf.grads is not None else None
+            res = ops.attn_capture_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buf.probs[l], d_o, grads, 1.0 / at.scale,
+                                       _lib.SCALE_SCORES, need_dqkv=need, layout="bnhd", out=out, o=o_fwd, rel_row=row)
+            if row is not None:
+                row = res[3]
+            if on_layer_done is not None:
+                on_layer_done(l)
+            if not need:
+                break
+            d_h1 = self._gemm(dqkv.view(B, N, 3 * E), at.qkv.weight)
+            dx = ops.layernorm_bwd_add(d_h1, x, mean1, rstd1, blk.norm1.weight, d_x1)
+        return row
 
 
 def vit_base_patch16_224(num_classes=1000, **kw):
@@ -302,3 +350,51 @@ class GraphedRelevance:
             self.indices.copy_(torch.as_tensor(indices, device=self.indices.device).reshape(-1))
         self.graph.replay()
         return self.output
+
+
+def generate_relevance_batch(model, images, indices=None):
+    """Relevancy maps of B DISTINCT images, each for its own class, in one batch-B forward and backward: ``[B, N-1]``.
+
+    Row b equals ``generate_relevance(model, images[b:b+1], index=indices[b])`` (notebook cell 7, one image per call).
+    ``indices=None``: each image's arg-max class, picked on the device (no host sync: capturable).  Row 0 of R is carried
+    top-down through the backward by the capture op's exact-fp32 row-relevancy mode (``mmx_attn_capture_bwd_rowrel_f32``):
+    no dP slab is kept and no head-averaged matrix exists."""
+    B = images.shape[0]
+    logits, state = model.forward_tape(images, grads=False)
+    if indices is None:
+        idx = logits.argmax(-1)
+    else:
+        idx = torch.as_tensor(indices, device=images.device).reshape(-1)
+        if idx.numel() != B:
+            raise ValueError("generate_relevance_batch: %d indices for %d images" % (idx.numel(), B))
+    d_logits = torch.zeros(B, logits.shape[-1], dtype=torch.float32, device=images.device)
+    d_logits.scatter_(1, idx.reshape(B, 1), 1.0)
+    N = model.buffers_.probs.shape[-1]
+    row = torch.zeros(B, N, dtype=torch.float32, device=images.device)
+    row[:, 0] = 1.0
+    return model.backward_tape(state, d_logits, rel_row=row)[:, 1:]
+
+
+class GraphedRelevanceBatch(GraphedRelevance):
+    """``generate_relevance_batch`` captured once into a hipGraph and replayed (the batch size and image shape are fixed at
+    construction; ``indices=None``: arg-max classes, chosen on the device).
+
+        run = GraphedRelevanceBatch(model, images, indices=labels)
+        maps = run(next_images, next_labels)                           # [B, N-1], the graph's output buffer
+    """
+
+    def __init__(self, model, input, indices=None, warmup=3):
+        self.input = input.clone()
+        self.indices = None if indices is None else torch.as_tensor(indices, device=input.device).reshape(-1).clone()
+        call = lambda: generate_relevance_batch(model, self.input, self.indices)   # noqa: E731
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                call()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(self.graph):
+            self.output = call()
+        self.buffers = model.buffers_       # the slabs the graph reads and writes stay alive with it
+        self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
