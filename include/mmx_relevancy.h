@@ -424,6 +424,32 @@ int mmx_attn_capture_bwd_rowrel_f32(const void* q_dev, const void* k_dev, const 
                                     int need_dqkv, const void* rel_in_dev, void* rel_out_dev,
                                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Grouped row mode: K targets per image over a batch of M = n_images distinct images in one call (CLIP/example.py:8-32 with the
+ * top-K prompts of every image; CLIP_explainability.ipynb cell 6, caption i against image i, with K captions per image; the ViT
+ * notebook's two classes per image).  `B` is the TARGET count T = M * K, in K-major order: target t explains image t % M.
+ * Per IMAGE (batch index t % M, with their given batch strides): q, k, v, probs (probs_sb) and the forward's O (fwd_o_dev).
+ * Per TARGET (batch t): do, dq / dk / dv, dprobs (where written) and rel_in / rel_out.  Every target computes exactly what
+ * mmx_attn_capture_bwd_rowrel_f32 computes on per-target copies of its image's operands (bit-identical, NaN policy included);
+ * an image's K targets run next to each other on one XCD (its P / K / V come from L2).  Same arguments as that entry plus
+ * `n_images`; MMX_EINVAL when n_images < 1 or B % n_images != 0 (checked before any HIP call), otherwise the same refusals
+ * (MMX_EINVAL / MMX_ENOTSUP / MMX_EWORKSPACE) for the same reasons.  The workspace is per target: query it with B = T. */
+size_t mmx_attn_capture_bwd_rowrel_f32_grouped_workspace_bytes(int B, int H, int Nq, int Nk);
+int mmx_attn_capture_bwd_rowrel_f32_grouped(const void* q_dev, const void* k_dev, const void* v_dev,
+                                            int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                                            int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                            int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                                            const void* probs_dev, int64_t probs_sb, int slab_dtype,
+                                            const void* do_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                                            const void* fwd_o_dev, int64_t fo_sb, int64_t fo_sh, int64_t fo_sn,
+                                            void* dprobs_dev,
+                                            void* dq_dev, void* dk_dev, void* dv_dev,
+                                            int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
+                                            int64_t dk_sb, int64_t dk_sh, int64_t dk_sn,
+                                            int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
+                                            int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                                            int need_dqkv, const void* rel_in_dev, void* rel_out_dev, int n_images,
+                                            void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2-DETR: the decoder half of DETR's rule schedule for ROWS of R_q_i -- rules 5, 6, 7 and 10 with
  * eq. 8-9 and the NaN policy of DETR/modules/ExplanationGenerator.py:19-53 (rule functions), :120-140 (handle_co_attn_*) --

@@ -72,6 +72,10 @@ _PROTOTYPES = {
                                              _i64, _i64, _vp, _vp, _vp, _vp]
                                         + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mmx_attn_capture_bwd_rowrel_f32_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mmx_attn_capture_bwd_rowrel_f32_grouped": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp,
+                                                     _i64, _i64, _i64, _vp, _vp, _vp, _vp]
+                                                + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "mmx_attn_capture_bwd_rowrel_f32_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mmx_attn_capture_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
     "mmx_attn_capture_bwd": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
                              + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),

@@ -5,7 +5,9 @@ Reference entry points mirrored here:
     -- CLIP_explainability.ipynb cell 6 (batched: one image, B texts) -> ``(text_relevance [B,Nt,Nt], image_relevance [B,Ni-1])``
   * ``interpret_single(image, text, model, device, index=None)``
     -- CLIP/example.py:8-32 (one image, K texts, explains ``logits_per_image[0, index]``) -> ``image_relevance [Ni-1]``
-    (``clip_example.interpret`` under the reference's name); ``interpret_batch`` runs it over B distinct images in one pass
+    (``clip_example.interpret`` under the reference's name); ``interpret_batch`` runs it over B distinct images in one pass,
+    ``interpret_batch_multi`` with the top-K prompts of every image
+  * ``interpret_grouped(images, texts, model, device)`` -- cell 6 with K captions per image (caption i against image i // K)
   * ``text_scores(text_encoding, R_text)`` -- notebook cell 8:5-7 post-processing (on device)
 
 What is different under the hood (results agree to fp32 rounding, see tests/test_gpu_clip.py):
@@ -254,6 +256,96 @@ def interpret_batch(images, texts, model, device, index=None):
         torch.autograd.backward(logits_per_image, grad_tensors=one_hot, inputs=[image_features])
     row = model.visual.backward_tape(img_state, image_features.grad, 0, cls_row=True)
     return row[:, 1:]
+
+
+def _fp32_clip(model, who):
+    """The grouped row mode runs the exact-fp32 kernels only: refuse a bf16 / fp16 body by name."""
+    for name, tower in (("image", model.visual.transformer), ("text", model.transformer)):
+        for what in ("forward_gemm_dtype", "backward_gemm_dtype", "capture_dtype"):
+            dt = getattr(tower, what, torch.float32)
+            if dt != torch.float32:
+                raise ops.MMXError("%s: fp32 bodies only (the exact-fp32 grouped row mode); the %s tower's %s is %s"
+                                   % (who, name, what, str(dt).replace("torch.", "")))
+    if model.dtype != torch.float32:
+        raise ops.MMXError("%s: fp32 bodies only; the parameters are %s" % (who, str(model.dtype).replace("torch.", "")))
+
+
+def _k_major_rows(rows, K, M):
+    """``[K*M, ...]`` target rows in K-major order -> ``[M, K, ...]`` (image-major, what the caller passed)."""
+    return rows.view(K, M, *rows.shape[1:]).transpose(0, 1)
+
+
+def interpret_batch_multi(images, texts, model, device, index=None, top_k=None):
+    """Zero-shot explanation of B DISTINCT images against C class prompts, K prompts per image, in one pass ->
+    ``image_relevance [B, K, Ni-1]``.
+
+    Entry ``[b, k]`` equals ``interpret_batch(images, texts, model, device, index=index[:, k])[b]`` (CLIP/example.py:8-32 per
+    image and prompt).  ``index``: ``[B, K]`` prompt indices; ``None``: each image's ``top_k`` best prompts (default 1), picked
+    on the device with ``topk``.  The C prompts are encoded once, forward only, and the image tower runs ONE forward at batch B;
+    its backward carries the B*K class-token rows through the capture op's grouped row mode (an image's K targets share its
+    forward operands).  fp32 bodies only."""
+    _fp32_clip(model, "interpret_batch_multi")
+    B = images.shape[0]
+    if index is not None:
+        idx = torch.as_tensor(index, device=images.device)
+        if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] < 1:
+            raise ValueError("interpret_batch_multi: index must be [B, K] = [%d, K], got %s" % (B, tuple(idx.shape)))
+        K = idx.shape[1]
+    else:
+        K = 1 if top_k is None else int(top_k)
+        if K < 1:
+            raise ValueError("interpret_batch_multi: top_k must be >= 1")
+    if K == 1:
+        return interpret_batch(images, texts, model, device, None if index is None else idx.reshape(B)).unsqueeze(1)
+    with torch.no_grad():
+        txt_feat, _ = model.encode_text_tape(texts, first_grad_layer=model.transformer.layers)   # no tape kept: no backward
+        img_feat, img_state = model.visual.forward_tape(images.type(model.dtype), first_grad_layer=0, grads=False)
+    T = K * B
+    with torch.enable_grad():
+        # one leaf row per TARGET, K-major (t = k * B + b): each gets the gradient of its own logit only
+        image_features = img_feat.detach().repeat(K, 1).requires_grad_(True)
+        logits_per_image, _ = model.logits(image_features, txt_feat.detach())
+        if index is None:
+            idx = logits_per_image.detach()[:B].topk(K, dim=-1).indices
+        one_hot = torch.zeros_like(logits_per_image).scatter_(1, idx.t().reshape(T, 1).long(), 1.0)
+        torch.autograd.backward(logits_per_image, grad_tensors=one_hot, inputs=[image_features])
+    row = model.visual.backward_tape(img_state, image_features.grad, 0, cls_row=True, targets_per_image=K)
+    return _k_major_rows(row, K, B)[:, :, 1:].contiguous()
+
+
+def interpret_grouped(images, texts, model, device, start_layer=-1, start_layer_text=-1):
+    """CLIP_explainability.ipynb cell 6 with K captions per image: ``images [M, 3, R, R]``, ``texts [M*K, context]``; caption i
+    is explained against image ``i // K`` -> ``(R_text [M*K, context, context], R_image [M*K, Ni-1])``.
+
+    The same as ``interpret(images.repeat_interleave(K, 0), texts, model, device, start_layer, start_layer_text,
+    share_image_forward=False)``: the text tower runs per caption (its backward and its causal relevancy chain, as there); the
+    image tower runs ONE forward at batch M and the grouped row-mode backward over the M*K captions (row 0 of R only, the only
+    row returned).  ``start_layer`` / ``start_layer_text`` keep their ``interpret`` meaning.  fp32 bodies only."""
+    _fp32_clip(model, "interpret_grouped")
+    M, T = images.shape[0], texts.shape[0]
+    if M < 1 or T % M:
+        raise ValueError("interpret_grouped: %d captions are not a whole number per image over %d images" % (T, M))
+    K = T // M
+    sl = model.visual.transformer.layers - 1 if start_layer == -1 else start_layer
+    slt = model.transformer.layers - 1 if start_layer_text == -1 else start_layer_text
+    img_feat, img_state = model.visual.forward_tape(images.type(model.dtype), None, sl, grads=False)
+    txt_feat, txt_state = model.encode_text_tape(texts, None, slt)
+    with torch.enable_grad():
+        # caption order: leaf row i holds image i // K (the reference's repeated images, cell 6:3)
+        image_features = img_feat.detach().repeat_interleave(K, 0).requires_grad_(True)
+        text_features = txt_feat.detach().requires_grad_(True)
+        logits_per_image, _ = model.logits(image_features, text_features)
+        eye = torch.eye(T, dtype=torch.float32, device=texts.device)           # one_hot = sum_i logits_per_image[i, i]
+        torch.autograd.backward(logits_per_image, grad_tensors=eye, inputs=[image_features, text_features])
+    # caption m*K + k -> target k*M + m (K-major, what the grouped backward addresses)
+    d_img = _k_major_rows(image_features.grad, M, K).reshape(T, -1)
+    row = model.visual.backward_tape(img_state, d_img, sl, cls_row=True, targets_per_image=K)
+    image_relevance = _k_major_rows(row, K, M).reshape(T, -1)[:, 1:]
+    model.backward_text_tape(txt_state, text_features.grad, slt)
+    txt = model.transformer
+    R_text = _plan(txt.buffers, slt, txt.layers, T, False, getattr(txt, "half_chain", False),
+                   causal=_is_causal_tower(txt)).launch()
+    return R_text, image_relevance
 
 
 def text_scores(text_encoding, R_text):

@@ -249,7 +249,7 @@ class Transformer(nn.Module):
         return self.forward_tape(x, batch)
 
     @torch.no_grad()
-    def backward_tape(self, tape, dy, first_grad_layer=0, dy_rows=None, rel_row=None, dy_row_values=None):
+    def backward_tape(self, tape, dy, first_grad_layer=0, dy_rows=None, rel_row=None, dy_row_values=None, targets_per_image=1):
         """``dy``: ``[B, N, E]`` upstream gradients w.r.t. the tower output; fills ``buffers.grads`` of every block
         ``>= first_grad_layer``.
 
@@ -264,7 +264,11 @@ class Transformer(nn.Module):
         vector-Jacobian products are row-wise, so they then run on those B rows instead of B*N (3 of the 4 GEMMs of
         that block); below the top block's attention the gradient is dense and everything runs in full.
         ``dy_row_values`` (``[B, E]``, with ``dy_rows``): those rows themselves -- ``dy`` may then be ``None`` (no dense zero
-        tensor is built just to be gathered from again)."""
+        tensor is built just to be gathered from again).
+
+        ``targets_per_image=K`` (fp32 body, row mode only): the tape holds M distinct samples and the B = K*M upstream gradients
+        are K per sample in K-major order (target t explains sample t % M).  The elementwise steps broadcast the per-sample
+        activations (modulo kernels); the capture op runs its grouped row mode (``ops.attn_capture_bwd(images=M)``)."""
         if dy is None:
             if dy_rows is None or dy_row_values is None:
                 raise ValueError("backward_tape: dy=None needs dy_rows and dy_row_values")
@@ -278,6 +282,7 @@ class Transformer(nn.Module):
         dx = dy
         top_rows = None                      # (rows, d_x1 of those rows): the top block's residual gradient, added after LN1'
         mma = bool(getattr(self, "attention_mma_bf16", False)) and N > 128
+        grouped = int(targets_per_image) > 1
         # bf16 body on the streaming kernels: the gradients BETWEEN the GEMMs are bf16 (what the bf16 GEMMs produce and
         # consume; the elementwise kernels and the attention backward read / write bf16 directly -- no conversion
         # passes), the residual gradient stream (dx, d_x1) stays fp32
@@ -288,18 +293,24 @@ class Transformer(nn.Module):
         head = self.resblocks[0].attn
         att16 = stream16 and (mma or (self.capture_dtype == torch.float32 and
                                       ops.head_kernel_shape(N, N, head.head_dim) and head.head_dim % 8 == 0))
+        if grouped and (rel_row is None or stream16 or mma or B % int(targets_per_image)):
+            raise ValueError("backward_tape: targets_per_image=%d needs an fp32 body in the row mode and a multiple of it "
+                             "upstream gradients (got %d)" % (int(targets_per_image), B))
         dx_h = None
         for l in range(top, first_grad_layer - 1, -1):
             blk = self.resblocks[l]
             at = blk.attn
             x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o_fwd = tape[l][:9]
-            shared = x.shape[0] != B
+            shared = x.shape[0] != B and not grouped
+            if grouped and x.shape[0] * int(targets_per_image) != B:
+                raise ValueError("backward_tape: %d upstream gradients for %d samples x %d targets"
+                                 % (B, x.shape[0], int(targets_per_image)))
             if len(tape[l]) > 9 and (l != top or dy_rows is None):
                 raise ValueError("backward_tape: the forward kept only the output rows of the top block (out_rows): "
                                  "pass the same rows as dy_rows")
             if l == top and dy_rows is not None:
                 g = dy_row_values if dy_row_values is not None else dy[torch.arange(B, device=dy_rows.device), dy_rows]
-                d_x1_r, d_o = self._top_block_rows(blk, tape[l], g, dy_rows, shared, N)
+                d_x1_r, d_o = self._top_block_rows(blk, tape[l], g, dy_rows, shared, N, x.shape[0] if grouped else None)
                 d_x1, top_rows = None, (dy_rows, d_x1_r)
                 if att16:
                     d_o = d_o.to(torch.bfloat16)
@@ -328,7 +339,8 @@ class Transformer(nn.Module):
             res = ops.attn_capture_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buffers.probs[l], d_o,
                                        buffers.grads[l] if buffers.grads is not None else None,
                                        at.head_dim ** -0.5, _lib.SCALE_Q_FIRST, need_dqkv=need, layout="bnhd", out=out,
-                                       batch=B if shared else None, o=o_fwd, mma_bf16=mma, rel_row=rel_row)
+                                       batch=B if shared else None, o=o_fwd, mma_bf16=mma, rel_row=rel_row,
+                                       images=x.shape[0] if grouped else None)
             if rel_row is not None:
                 rel_row = res[3]
             if not need:
@@ -347,13 +359,16 @@ class Transformer(nn.Module):
                     dx_h = dx.to(torch.bfloat16)
         return rel_row
 
-    def _top_block_rows(self, blk, entry, g, rows, shared, N):
+    def _top_block_rows(self, blk, entry, g, rows, shared, N, images=None):
         """MLP / ``out_proj`` backward of the top block on the one row per sample that carries a gradient (``g [B, E]``).
-        Returns ``(d_x1 rows [B, E], d_o dense [B, N, E])`` -- the attention backward wants every row of ``d_o``, zero elsewhere."""
+        Returns ``(d_x1 rows [B, E], d_o dense [B, N, E])`` -- the attention backward wants every row of ``d_o``, zero elsewhere.
+        ``images``: grouped mode, target b reads sample b % images of the tape."""
         x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o_fwd = entry[:9]
         B = g.shape[0]
         ar = torch.arange(B, device=g.device)
         src = torch.zeros_like(rows) if shared else ar                     # sample index into the (shared) tape
+        if images is not None:
+            src = ar % images
         if len(entry) > 9:                                                   # forward_tape(out_rows=...): rows only on the tape
             m_r, x1_r, mean2_r, rstd2_r = m[src], x1[src], mean2.reshape(-1)[src], rstd2.reshape(-1)[src]
         else:
@@ -446,12 +461,16 @@ class VisualTransformer(nn.Module):
         return self.forward_tape(image, batch)
 
     @torch.no_grad()
-    def backward_tape(self, state, d_features, first_grad_layer=0, cls_row=False):
+    def backward_tape(self, state, d_features, first_grad_layer=0, cls_row=False, targets_per_image=1):
         """``d_features [B, output_dim]``: per-sample upstream gradients of the image features.
         ``cls_row=True``: row-relevancy mode (``Transformer.backward_tape``): returns row 0 (the class token's) of the
-        tower's relevancy matrix, ``[B, N]``, instead of filling gradient slabs."""
+        tower's relevancy matrix, ``[B, N]``, instead of filling gradient slabs.
+        ``targets_per_image=K`` (with ``cls_row``, fp32 body): ``d_features`` is ``[K*M, output_dim]`` over the M images of the
+        forward, K-major (target t explains image t % M); returns ``[K*M, N]`` in the same order."""
         tape, y_shape, cls, mean, rstd = state
         B = d_features.shape[0]
+        if int(targets_per_image) > 1 and not cls_row:
+            raise ValueError("backward_tape: targets_per_image needs cls_row=True (the grouped mode is a row mode)")
         d_f = torch.matmul(d_features, self.proj.t())
         # LayerNorm' against the (shared) class-token rows' statistics; only the class token feeds the features
         d_cls = ops.layernorm_bwd_add(d_f, cls, mean, rstd, self.ln_post.weight)
@@ -461,7 +480,7 @@ class VisualTransformer(nn.Module):
             rel_row[:, 0] = 1.0                                              # e_0: row 0 of the identity R starts from
         return self.transformer.backward_tape(tape, None, first_grad_layer,
                                               dy_rows=torch.zeros(B, dtype=torch.long, device=d_f.device), rel_row=rel_row,
-                                              dy_row_values=d_cls)
+                                              dy_row_values=d_cls, targets_per_image=targets_per_image)
 
     def backward_shared(self, state, d_features, first_grad_layer=0):
         return self.backward_tape(state, d_features, first_grad_layer)

@@ -44,6 +44,10 @@ struct AttnBwdArgs {
     // gradient stream between the bf16 GEMMs of a bf16 body); strides stay in elements.  q / k / v / o / delta: fp32.
     int io_bf16;
     int tile_skip = 0;  // whole-head kernels: skip the products of all-zero probability tiles (attention_head.hip, with_tile_count)
+    // Grouped row mode (mmx_attn_capture_bwd_rowrel_f32_grouped; exact-fp32 row-relevancy mode only): the B targets are K = grp_k
+    // per image over M = B / K images, K-major -- target t explains image t % M.  q / k / v / probs / o are per IMAGE (batch index
+    // t % M with their own batch strides); dout, dq / dk / dv, dprobs, delta and the relevancy rows are per TARGET.  0: off.
+    int grp_k = 0;
 };
 
 int attn_fwd_head_try(const AttnFwdArgs& a, hipStream_t s, int* rc_out);    // attention_head.hip (register-resident)

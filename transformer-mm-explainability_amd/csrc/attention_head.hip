@@ -412,7 +412,10 @@ __global__ __launch_bounds__(1024) void attn_fwd_head_kernel(const AttnFwdArgs a
 // REL (row-relevancy mode, mmx_attn_capture_bwd_rowrel_f32; see AttnBwdArgs::rel_v): phase A's dP and P registers also give this
 // head's partial row  part[k] = sum_q rel_v[b][q] * clamp(dP * P, 0)[q][k]  -> rel_part[b][h][k]: the 16 rows of a wave on DPP
 // (group16_sum), the waves in LDS in wave order (deterministic).  dQ / dK / dV are computed exactly as without it.
-template <int DP, int NTK, bool IOH = false, bool REL = false>
+// GRP (grouped row mode, with REL; AttnBwdArgs::grp_k): b is the target, bi its image (Q / K / V / P); the workgroups run in the
+// logical order (image, head, target of the image), XCD-contiguous, so an image-head's K targets are neighbours on one XCD and
+// read its P / K / V / Q through L2.  Every target does the arithmetic of the per-sample kernel on the same operand values.
+template <int DP, int NTK, bool IOH = false, bool REL = false, bool GRP = false>
 __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(const AttnBwdArgs a) {
     constexpr int LSA = DP + 8, LSB = DP + 4, KK = DP / 16, NPk = NTK * 16, SS = NPk + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -427,7 +430,10 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     const int kC = NPq * (SS + LSB);
     unsigned* live_tab = reinterpret_cast<unsigned*>(smem + (kAB > kC ? kAB : kC));
 
-    const int h = blockIdx.x, b = blockIdx.y;
+    const int wg = GRP ? xcd_contiguous_id(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y) : 0;
+    const int h = GRP ? (wg / a.grp_k) % a.H : blockIdx.x;
+    const int bi = GRP ? wg / (a.grp_k * a.H) : blockIdx.y;
+    const int b = GRP ? (wg % a.grp_k) * (a.B / a.grp_k) + bi : bi;
     const int c16 = lane & 15, g = lane >> 4;
     const bool q_first = (a.scale_mode == MMX_SCALE_Q_FIRST);
     const int q = wave * 16 + c16;
@@ -444,15 +450,15 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
                              a.D, g);
     else
         load_rows16<DP>(doreg, a.dout + b * a.os.sb + h * a.os.sh, a.os.sn, q, a.Nq, a.D, g, 1.f);
-    const float* prow = a.probs + b * a.probs_sb + (static_cast<int64_t>(h) * a.Nq + (qv ? q : 0)) * a.Nk;
+    const float* prow = a.probs + bi * a.probs_sb + (static_cast<int64_t>(h) * a.Nq + (qv ? q : 0)) * a.Nk;
 #pragma unroll
     for (int t = 0; t < NTK; ++t) preg[t] = load_chunk(prow, t * 16 + 4 * g, a.Nk, qv);
-    const float* vb = a.v + b * a.vs.sb + h * a.vs.sh;
+    const float* vb = a.v + bi * a.vs.sb + h * a.vs.sh;
     float vq = 0.f;     // REL: this row's weight, loaded with the other operands (retired by the staging barrier)
     if constexpr (REL) vq = a.rel_v[static_cast<int64_t>(b) * a.Nq + (qv ? q : a.Nq - 1)];
     if (a.need_dqkv) {
-        load_rows16<DP>(qreg, a.q + b * a.qs.sb + h * a.qs.sh, a.qs.sn, q, a.Nq, a.D, g, q_first ? a.scale : 1.f);
-        stage_pair<DP, 4>(Vs, LSA, vb, a.vs.sn, Ks, LSB, a.k + b * a.ks.sb + h * a.ks.sh, a.ks.sn, a.Nk, NPk, a.D, tid,
+        load_rows16<DP>(qreg, a.q + bi * a.qs.sb + h * a.qs.sh, a.qs.sn, q, a.Nq, a.D, g, q_first ? a.scale : 1.f);
+        stage_pair<DP, 4>(Vs, LSA, vb, a.vs.sn, Ks, LSB, a.k + bi * a.ks.sb + h * a.ks.sh, a.ks.sn, a.Nk, NPk, a.D, tid,
                           nthreads);
     } else {
         stage_one<DP, 4>(Vs, LSA, vb, a.vs.sn, a.Nk, NPk, a.D, tid, nthreads);
@@ -661,21 +667,21 @@ static int fwd_head_dispatch(const AttnFwdArgs& a, int NTK, int threads, size_t 
     return MMX_ENOTSUP;
 }
 
-#define MMX_HEAD_CASE_IO(DPV, N, IO, RL)                                                                      \
+#define MMX_HEAD_CASE_IO(DPV, N, IO, RL, GR)                                                                  \
     case N:                                                                                                    \
-        return launch_head(attn_bwd_head_kernel<DPV, N, IO, RL>, a, threads, lds, s, "attn_bwd_head_kernel")
+        return launch_head(attn_bwd_head_kernel<DPV, N, IO, RL, GR>, a, threads, lds, s, "attn_bwd_head_kernel")
 
-template <int DP, bool IOH, bool REL = false>
+template <int DP, bool IOH, bool REL = false, bool GRP = false>
 static int bwd_head_dispatch(const AttnBwdArgs& a, int NTK, int threads, size_t lds, hipStream_t s) {
     switch (NTK) {
-        MMX_HEAD_CASE_IO(DP, 1, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 2, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 3, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 4, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 5, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 6, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 7, IOH, REL);
-        MMX_HEAD_CASE_IO(DP, 8, IOH, REL);
+        MMX_HEAD_CASE_IO(DP, 1, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 2, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 3, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 4, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 5, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 6, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 7, IOH, REL, GRP);
+        MMX_HEAD_CASE_IO(DP, 8, IOH, REL, GRP);
     }
     return MMX_ENOTSUP;
 }
@@ -717,6 +723,13 @@ int attn_bwd_head_try(const AttnBwdArgs& a_in, hipStream_t s, int* rc_out) {
     const size_t lds = bwd_head_lds(DP, NTK, NTQ, rel);
     if (lds > 160 * 1024 || (NTK >= 7 && NTQ > 8)) return 0;
     if (rel && (a.io_bf16 || a.Nq != a.Nk)) return 0;
+    if (rel && a.grp_k) {
+        // grouped row mode: the same grid, one workgroup per (target, head), in the order the kernel decodes
+        *rc_out = DP == 32 ? bwd_head_dispatch<32, false, true, true>(a, NTK, threads, lds, s)
+                           : bwd_head_dispatch<64, false, true, true>(a, NTK, threads, lds, s);
+        if (*rc_out == MMX_OK) *rc_out = rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);
+        return 1;
+    }
     if (rel) {
         *rc_out = DP == 32 ? bwd_head_dispatch<32, false, true>(a, NTK, threads, lds, s) : bwd_head_dispatch<64, false, true>(a, NTK, threads, lds, s);
         if (*rc_out == MMX_OK) *rc_out = rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);

@@ -416,6 +416,11 @@ extern "C" size_t mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(int B, int H, 
     return rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk);
 }
 
+extern "C" size_t mmx_attn_capture_bwd_rowrel_f32_grouped_workspace_bytes(int B, int H, int Nq, int Nk) {
+    // per TARGET, as the per-sample mode: B is the target count
+    return mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk);
+}
+
 extern "C" size_t mmx_attn_capture_bwd_rowrel_workspace_bytes(int B, int H, int Nq, int Nk) {
     // delta | partial relevancy rows | bf16 images of the shared operands (third-generation kernels, attention_bf16_v3.hip)
     return rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk) + mmx::attn_bwd_bf16_v3_prep_bytes(H, Nk);
@@ -430,7 +435,8 @@ static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev
                                        int64_t dq_sn, int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t dv_sb,
                                        int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D, float scale,
                                        int scale_mode, int need_dqkv, void* workspace_dev, size_t workspace_bytes,
-                                       void* stream, const void* rel_in_dev, void* rel_out_dev, bool rel_f32 = false) {
+                                       void* stream, const void* rel_in_dev, void* rel_out_dev, bool rel_f32 = false,
+                                       int grp_k = 0) {
     const bool rel = rel_in_dev != nullptr;
     MMX_CHECK_ARG(v_dev && probs_dev && do_dev && (dprobs_dev || rel), "mmx_attn_capture_bwd: null pointer");
     const int io_bf16 = (slab_dtype & MMX_ATTN_IO_BF16) ? 1 : 0;
@@ -485,6 +491,7 @@ static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev
     a.rel_v = static_cast<const float*>(rel_in_dev);
     a.rel_part = rel ? reinterpret_cast<float*>(static_cast<char*>(workspace_dev) + rowrel_delta_bytes(B, H, Nq)) : nullptr;
     a.rel_out = static_cast<float*>(rel_out_dev);
+    a.grp_k = grp_k;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (rel && rel_f32) {
         if (attn_bwd_head_try(a, s, &rc)) return rc;    // N <= 128: one partial row per head
@@ -583,4 +590,28 @@ extern "C" int mmx_attn_capture_bwd_rowrel_f32(const void* q_dev, const void* k_
                          slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
                          dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
                          scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev, true);
+}
+
+extern "C" int mmx_attn_capture_bwd_rowrel_f32_grouped(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
+                                                       int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                                                       int64_t v_sb, int64_t v_sh, int64_t v_sn, const void* probs_dev,
+                                                       int64_t probs_sb, int slab_dtype, const void* do_dev, int64_t o_sb,
+                                                       int64_t o_sh, int64_t o_sn, const void* fwd_o_dev, int64_t fo_sb,
+                                                       int64_t fo_sh, int64_t fo_sn, void* dprobs_dev, void* dq_dev,
+                                                       void* dk_dev, void* dv_dev, int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
+                                                       int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t dv_sb,
+                                                       int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D,
+                                                       float scale, int scale_mode, int need_dqkv, const void* rel_in_dev,
+                                                       void* rel_out_dev, int n_images, void* workspace_dev,
+                                                       size_t workspace_bytes, void* stream) {
+    MMX_CHECK_ARG(rel_in_dev && rel_out_dev, "mmx_attn_capture_bwd_rowrel_f32_grouped: null relevancy row");
+    MMX_CHECK_ARG(n_images >= 1 && B >= 1 && B % n_images == 0,
+                  "mmx_attn_capture_bwd_rowrel_f32_grouped: %d targets are not a whole number per image over %d images", B,
+                  n_images);
+    // one target per image: the per-sample mode itself (same kernels, same order)
+    const int grp_k = B / n_images > 1 ? B / n_images : 0;
+    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
+                         slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
+                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
+                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev, true, grp_k);
 }

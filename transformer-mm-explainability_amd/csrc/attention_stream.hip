@@ -568,7 +568,10 @@ __global__ __launch_bounds__(kThreads, 1) void attn_fwd_split_kernel(const AttnF
 // REL (row-relevancy mode, see AttnBwdArgs::rel_v): the product the relevancy rules need from this layer -- one ROW of
 // R + A_bar.R, i.e. v.A_bar with A_bar = mean_h clamp(dP * P, 0) -- is reduced here from the dP / P values the sweep
 // already holds, so dP is neither stored nor re-read and no A_bar matrix exists.
-template <int DP, int DT, bool MM, bool REL = false, bool IOH = false>
+// GRP (grouped row mode, AttnBwdArgs::grp_k): b is the target, bi its image (the forward's operands); the logical order is
+// (image, head, target of the image, row tile), so an image-head's K targets run next to each other on one XCD and share its
+// P / K / V through L2.  Without GRP, bi == b and the order is the one above.
+template <int DP, int DT, bool MM, bool REL = false, bool IOH = false, bool GRP = false>
 __global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_bwd_q_stream_kernel(const AttnBwdArgs a) {
     typedef typename slab_elem<DT>::type slab_t;
     constexpr int LS = DP + 4, NB = DP / 16;
@@ -579,10 +582,12 @@ __global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_bwd_q_stream_
     float* Sw = Ks + kTile * LS + wave * 16 * kPS;
     const int nrt = (a.Nq + kRows - 1) / kRows;           // 1-D grid, XCD-contiguous logical order (see forward)
     const int wg = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    const int h = (wg / nrt) % a.H, b = wg / (nrt * a.H);
+    const int h = GRP ? (wg / (nrt * a.grp_k)) % a.H : (wg / nrt) % a.H;
+    const int bi = GRP ? wg / (nrt * a.grp_k * a.H) : wg / (nrt * a.H);
+    const int b = GRP ? ((wg / nrt) % a.grp_k) * (a.B / a.grp_k) + bi : bi;
     const int rw = (wg % nrt) * kRows + wave * 16;
-    const float* kb = a.need_dqkv ? a.k + b * a.ks.sb + h * a.ks.sh : nullptr;
-    const float* vb = a.v + b * a.vs.sb + h * a.vs.sh;
+    const float* kb = a.need_dqkv ? a.k + bi * a.ks.sb + h * a.ks.sh : nullptr;
+    const float* vb = a.v + bi * a.vs.sb + h * a.vs.sh;
     const float* dob = a.dout + b * a.os.sb + h * a.os.sh;
     const bool q_first = (a.scale_mode == MMX_SCALE_Q_FIRST);
     const int64_t head = static_cast<int64_t>(b) * a.H + h;
@@ -607,7 +612,7 @@ __global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_bwd_q_stream_
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         rows[r] = rw + 4 * g + r;
-        prow[r] = reinterpret_cast<const slab_t*>(a.probs) + b * a.probs_sb +
+        prow[r] = reinterpret_cast<const slab_t*>(a.probs) + bi * a.probs_sb +
                   (static_cast<int64_t>(h) * a.Nq + min(rows[r], a.Nq - 1)) * a.Nk + i;
         dpout[r] = (rows[r] < a.Nq && a.dprobs) ? reinterpret_cast<slab_t*>(a.dprobs) + (head * a.Nq + rows[r]) * a.Nk + i
                                                 : nullptr;
@@ -650,7 +655,7 @@ __global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_bwd_q_stream_
         // delta = rowsum(P * dP) = rowsum(dO * O)  (sum_k P_k (dO . V_k) = dO . sum_k P_k V_k): with the forward's O at
         // hand no sweep over the keys is needed.  Lane (row i, slot g) holds dO[row i][its d's]; the four slots of a
         // row are added with two cross-row shuffles, then the C-layout rows 4g + r pick their value up.
-        const float* ob = a.o + b * a.oos.sb + h * a.oos.sh;
+        const float* ob = a.o + bi * a.oos.sb + h * a.oos.sh;
         f32x4 oa[NB];
         load_a_rows<DP>(oa, ob, a.oos.sn, min(rw + i, a.Nq - 1), a.D, g, 1.f);
         float part = 0.f;
@@ -770,7 +775,7 @@ __global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_bwd_q_stream_
 // 16 rb + 4 g + s of key column j0 + i -- 16 consecutive keys per row segment, no LDS staging.
 // MM (bf16 MFMA): dP of the tile is RECOMPUTED (dO tile from LDS . this wave's V rows held in registers -- two bf16
 // MFMAs per 16 queries) instead of being read back from the slab the query-side kernel just wrote: one N^2 read less.
-template <int DP, int DT, bool MM, bool IOH = false>
+template <int DP, int DT, bool MM, bool IOH = false, bool GRP = false>
 __global__ __launch_bounds__(kThreads) void attn_bwd_kv_stream_kernel(const AttnBwdArgs a) {
     typedef typename slab_elem<DT>::type slab_t;
     constexpr int LS = DP + 4, NB = DP / 16;
@@ -781,16 +786,19 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_kv_stream_kernel(const Attn
     float* dl = dOs + kTile * LS;                             // [64] delta of the staged query rows
     const int nkt = (a.Nk + kRows - 1) / kRows;           // 1-D grid, XCD-contiguous: a head's key tiles share Q / dO
     const int wg = xcd_contiguous_id(blockIdx.x, gridDim.x);
-    const int h = (wg / nkt) % a.H, b = wg / (nkt * a.H);
+    // (GRP: b the target, bi its image -- the logical order of the query side)
+    const int h = GRP ? (wg / (nkt * a.grp_k)) % a.H : (wg / nkt) % a.H;
+    const int bi = GRP ? wg / (nkt * a.grp_k * a.H) : wg / (nkt * a.H);
+    const int b = GRP ? ((wg / nkt) % a.grp_k) * (a.B / a.grp_k) + bi : bi;
     const int kw = (wg % nkt) * kRows + wave * 16;          // first key of this wave
     const int key = kw + i;
     const bool key_ok = key < a.Nk;
     const int keyc = min(key, a.Nk - 1);
-    const float* qb = a.q + b * a.qs.sb + h * a.qs.sh;
+    const float* qb = a.q + bi * a.qs.sb + h * a.qs.sh;
     const float* dob = a.dout + b * a.os.sb + h * a.os.sh;
     const bool q_first = (a.scale_mode == MMX_SCALE_Q_FIRST);
     const int64_t head = static_cast<int64_t>(b) * a.H + h;
-    const slab_t* pcol = reinterpret_cast<const slab_t*>(a.probs) + b * a.probs_sb + static_cast<int64_t>(h) * a.Nq * a.Nk + keyc;
+    const slab_t* pcol = reinterpret_cast<const slab_t*>(a.probs) + bi * a.probs_sb + static_cast<int64_t>(h) * a.Nq * a.Nk + keyc;
     const slab_t* dpcol = reinterpret_cast<const slab_t*>(a.dprobs) + head * a.Nq * a.Nk + keyc;
 
     f32x4 kacc[NB], vacc[NB];
@@ -800,7 +808,7 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_kv_stream_kernel(const Attn
     bf16x8 v_pk[DP / 32];
     if constexpr (MM) {
         f32x4 va[NB];
-        load_a_rows<DP>(va, a.v + b * a.vs.sb + h * a.vs.sh, a.vs.sn, keyc, a.D, g, 1.f);
+        load_a_rows<DP>(va, a.v + bi * a.vs.sb + h * a.vs.sh, a.vs.sn, keyc, a.D, g, 1.f);
         pack_a_rows<DP>(v_pk, va);
     }
 
@@ -982,19 +990,26 @@ int launch_bwd_bf16(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
 
 // exact-fp32 kernels in row-relevancy mode (mmx_attn_capture_bwd_rowrel_f32): the query-side kernel with REL, the key-side
 // kernel as without it; fp32 slabs only
-int launch_bwd_rel_f32(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
+template <bool GRP>
+static int launch_bwd_rel_f32_kernels(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
     const bool small_d = a.D <= 32;
     constexpr size_t kRel = sizeof(float) * 16 * kTile;
-    int rc = small_d ? launch_stream(attn_bwd_q_stream_kernel<32, MMX_F32, false, true>, a, gq, stream_lds_bytes<32>(2) + kRel, s,
-                                     "attn_bwd_q_stream_kernel<32, rel>")
-                     : launch_stream(attn_bwd_q_stream_kernel<64, MMX_F32, false, true>, a, gq, stream_lds_bytes<64>(2) + kRel, s,
-                                     "attn_bwd_q_stream_kernel<64, rel>");
+    int rc = small_d ? launch_stream(attn_bwd_q_stream_kernel<32, MMX_F32, false, true, false, GRP>, a, gq,
+                                     stream_lds_bytes<32>(2) + kRel, s, "attn_bwd_q_stream_kernel<32, rel>")
+                     : launch_stream(attn_bwd_q_stream_kernel<64, MMX_F32, false, true, false, GRP>, a, gq,
+                                     stream_lds_bytes<64>(2) + kRel, s, "attn_bwd_q_stream_kernel<64, rel>");
     if (rc == MMX_OK && a.need_dqkv) {
-        rc = small_d ? launch_stream(attn_bwd_kv_stream_kernel<32, MMX_F32, false>, a, gk, stream_lds_bytes<32>(2), s,
+        rc = small_d ? launch_stream(attn_bwd_kv_stream_kernel<32, MMX_F32, false, false, GRP>, a, gk, stream_lds_bytes<32>(2), s,
                                      "attn_bwd_kv_stream_kernel<32>")
-                     : launch_stream(attn_bwd_kv_stream_kernel<64, MMX_F32, false>, a, gk, stream_lds_bytes<64>(2), s,
+                     : launch_stream(attn_bwd_kv_stream_kernel<64, MMX_F32, false, false, GRP>, a, gk, stream_lds_bytes<64>(2), s,
                                      "attn_bwd_kv_stream_kernel<64>");
     }
+    return rc;
+}
+
+int launch_bwd_rel_f32(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
+    // (grouped row mode: the same kernels with per-image addressing of the forward's operands)
+    int rc = a.grp_k ? launch_bwd_rel_f32_kernels<true>(a, gq, gk, s) : launch_bwd_rel_f32_kernels<false>(a, gq, gk, s);
     if (rc) return rc;
     return rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H * ((a.Nq + kRows - 1) / kRows), a.Nk, 1.0f / a.H, s);
 }

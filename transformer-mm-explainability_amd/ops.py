@@ -281,7 +281,8 @@ def quick_gelu_fwd(x, out_dtype=torch.float32):
 
 def quick_gelu_bwd(x, dy):
     """``dy * QuickGELU'(x)`` in one pass.  ``x`` has ``dy``'s shape, or batch 1 where ``dy`` has batch B (shared-forward
-    mode: the ONE activation tensor is broadcast over the B upstream gradients inside the kernel)."""
+    mode: the ONE activation tensor is broadcast over the B upstream gradients inside the kernel), or batch M where ``dy`` has
+    batch K*M in K-major order (grouped mode: target t reads sample t % M)."""
     _dev(x, dy)
     if dy.dtype == torch.bfloat16:             # bf16 gradient stream: dy / dx bf16, x fp32 (broadcast over the batch)
         x, dy = _f32c(x), dy.contiguous()
@@ -295,7 +296,8 @@ def quick_gelu_bwd(x, dy):
     dx = torch.empty_like(dy)
     if x.shape == dy.shape:
         check(lib().mmx_quick_gelu_bwd(_p(x), _p(dy), _p(dx), x.numel(), _stream()), "mmx_quick_gelu_bwd")
-    elif x.shape[0] == 1 and x.shape[1:] == dy.shape[1:] and x.numel() % 4 == 0:
+    elif x.shape[1:] == dy.shape[1:] and dy.shape[0] % x.shape[0] == 0 and x.numel() % 4 == 0:
+        # (x of batch M < B: the targets are K-major over M samples, target t reading sample t % M)
         check(lib().mmx_quick_gelu_bwd_bcast(_p(x), _p(dy), _p(dx), dy.numel(), x.numel(), _stream()),
               "mmx_quick_gelu_bwd_bcast")
     else:
@@ -864,8 +866,60 @@ def head_kernel_shape(n_q, n_k, head_dim, slab_dtype=torch.float32):
     return lds <= 160 * 1024 and not (ntk >= 7 and ntq > 8)
 
 
+def _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode, need_dqkv, layout, out, o, mma_bf16,
+                              rel_row, images):
+    """``attn_capture_bwd(images=M)``: the grouped row mode (per-image forward operands, per-target everything else)."""
+    if rel_row is None or mma_bf16:
+        raise MMXError("attn_capture_bwd: images= is the grouped exact-fp32 row mode: it needs rel_row and mma_bf16=False")
+    if layout == "bnhd":
+        M, Nq, H, D = q.shape
+        Nk = k.shape[1]
+    else:
+        M, H, Nq, D = q.shape
+        Nk = k.shape[2]
+    T = d_o.shape[0]
+    if images != M or probs.shape[0] != M or images < 1 or T % images:
+        raise MMXError("attn_capture_bwd: images=%d needs q/k/v/probs of batch %d and a d_o batch that is a multiple of it "
+                       "(q batch %d, probs batch %d, d_o batch %d)" % (images, images, M, probs.shape[0], T))
+    if rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (T, Nq) or Nq != Nk or probs.dtype != torch.float32:
+        raise MMXError("attn_capture_bwd: grouped rel_row needs fp32 [T, N] rows and fp32 slabs of a self-attention")
+    if d_o.dtype != torch.float32:
+        raise MMXError("attn_capture_bwd: grouped rel_row needs an fp32 d_o")
+    if dprobs_out is not None and (dprobs_out.dtype != torch.float32 or dprobs_out.shape[0] != T):
+        raise MMXError("attn_capture_bwd: grouped dprobs_out must be fp32 with batch %d" % T)
+    if d_o.stride(-1) != 1:
+        d_o = d_o.contiguous()
+    if probs.stride(-1) != 1 or not probs.is_contiguous():
+        raise MMXError("attn_capture_bwd: grouped probs must be a contiguous [M, H, N, N] slab")
+    dq = dk = dv = None
+    zero3 = (0, 0, 0)
+    if need_dqkv:
+        if out is not None:
+            dq, dk, dv = out
+        else:
+            dq, dk, dv = (torch.empty((T,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device) for t in (q, k, v))
+    if o is not None and (o.dtype != torch.float32 or o.stride(-1) != 1):
+        o = None                                               # only a hint: fall back to the two-sweep form
+    rel_row = rel_row.contiguous()
+    rel_out = torch.empty_like(rel_row)
+    dprobs = dprobs_out
+    if dprobs is None and need_dqkv and not head_kernel_shape(Nq, Nk, D, probs.dtype):
+        dprobs = _workspace(4 * T * H * Nq * Nk, q.device, "attn_rowrel_dp").view(torch.float32)
+    need = lib().mmx_attn_capture_bwd_rowrel_f32_grouped_workspace_bytes(T, H, Nq, Nk)
+    ws = _workspace(need, q.device, "attn_bwd")
+    check(lib().mmx_attn_capture_bwd_rowrel_f32_grouped(
+        _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
+        _p(probs), H * Nq * Nk, _DTYPES[probs.dtype], _p(d_o), *_bhnd_strides(d_o, layout),
+        _p(o), *(_bhnd_strides(o, layout) if o is not None else zero3), _p(dprobs), _p(dq), _p(dk), _p(dv),
+        *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
+        *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
+        T, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(rel_row), _p(rel_out), images, _p(ws), need,
+        _stream()), "mmx_attn_capture_bwd_rowrel_f32_grouped")
+    return dq, dk, dv, rel_out
+
+
 def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, need_dqkv=True,
-                     layout="bnhd", out=None, batch=None, o=None, mma_bf16=False, rel_row=None):
+                     layout="bnhd", out=None, batch=None, o=None, mma_bf16=False, rel_row=None, images=None):
     """Writes dP into ``dprobs_out`` and returns ``(dq, dk, dv)`` (``None`` when ``need_dqkv`` is False).
     ``out=(dq, dk, dv)`` lets the caller hand in (strided) views, e.g. of one packed dqkv tensor.
     ``batch``: shared-forward mode -- q/k/v/probs come from ONE forward (batch 1) and are broadcast (stride 0) over the
@@ -874,8 +928,14 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
     ``rel_row`` (``[B, N]`` fp32; row-relevancy mode, ``mmx_attn_capture_bwd_rowrel`` with ``mma_bf16=True``,
     ``mmx_attn_capture_bwd_rowrel_f32`` on the exact-fp32 kernels otherwise): returns
     ``(dq, dk, dv, rel_row + rel_row . mean_h clamp(dP * P, 0))``; ``dprobs_out`` may then be ``None`` (dP is not stored;
-    exact fp32 beyond the whole-head shapes with ``need_dqkv``: the key-side kernel reads dP back, from a scratch slab)."""
+    exact fp32 beyond the whole-head shapes with ``need_dqkv``: the key-side kernel reads dP back, from a scratch slab).
+    ``images=M`` (with an exact-fp32 ``rel_row``; grouped row mode, ``mmx_attn_capture_bwd_rowrel_f32_grouped``): q/k/v/probs/o
+    come from ONE forward over M distinct images (batch M); ``d_o``, ``rel_row``, dq/dk/dv and ``dprobs_out`` have batch T, a
+    multiple of M, in K-major order -- target t explains image t % M."""
     _dev(q, k, v, probs, d_o, dprobs_out, rel_row)
+    if images is not None:
+        return _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode, need_dqkv, layout, out, o,
+                                         mma_bf16, rel_row, int(images))
     if probs.dtype not in _DTYPES or (dprobs_out is not None and probs.dtype != dprobs_out.dtype):
         raise MMXError("attn_capture_bwd: probs / dprobs slabs must share one of fp32 / fp16 / bf16")
     if dprobs_out is None and rel_row is None:

@@ -220,14 +220,22 @@ class VisionTransformer(nn.Module):
             dx = ops.layernorm_bwd_add(d_h1, x, mean1, rstd1, blk.norm1.weight, d_x1)
 
     @torch.no_grad()
-    def backward_tape(self, state, d_logits, rel_row=None, on_layer_done=None):
+    def backward_tape(self, state, d_logits, rel_row=None, on_layer_done=None, targets_per_image=1):
         """``backward_shared`` over the B distinct images of ``forward_tape``: ``d_logits [B, C]``, one upstream gradient per
         image.  Without ``rel_row``: fills ``grads`` of every block.  ``rel_row [B, N]`` (fp32): the row-relevancy mode --
         every layer's capture backward also carries ``x <- x + x . mean_h clamp(dP * P, 0)`` top-down (exact fp32, no dP
-        stored) and the final row is returned.  ``on_layer_done(l)`` as in ``backward_shared``."""
+        stored) and the final row is returned.  ``on_layer_done(l)`` as in ``backward_shared``.
+
+        ``targets_per_image=K`` (row mode only): ``d_logits`` / ``rel_row`` hold K targets per image of the M-image forward,
+        ``[K*M, ...]`` in K-major order (target t explains image t % M).  The elementwise steps broadcast the per-image
+        activations (modulo kernels, a broadcast view for the erf GELU); the capture op runs its grouped row mode."""
         tape, x_last, mean, rstd = state
         B = d_logits.shape[0]
         N, E = x_last.shape[1], x_last.shape[2]
+        K, M = int(targets_per_image), x_last.shape[0]
+        if K > 1 and (rel_row is None or B != K * M):
+            raise ValueError("backward_tape: targets_per_image=%d needs the row mode and %d x %d upstream gradients (got %d)"
+                             % (K, K, M, B))
         d_f = torch.zeros(B, N, E, dtype=torch.float32, device=d_logits.device)
         d_f[:, 0, :] = torch.matmul(d_logits, self.head.weight)
         dx = ops.layernorm_bwd_add(d_f, x_last, mean, rstd, self.norm.weight)
@@ -238,7 +246,11 @@ class VisionTransformer(nn.Module):
             at = blk.attn
             x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o_fwd = tape[l]
             d_a = self._gemm(dx, blk.mlp.fc2.weight)
-            d_m = torch.ops.aten.gelu_backward(d_a, m)
+            if K > 1:           # (per-image pre-activation m [M, N, 4E], broadcast over the K target blocks)
+                F4 = m.shape[-1]
+                d_m = torch.ops.aten.gelu_backward(d_a.view(K, M, N, F4), m.expand(K, M, N, F4)).reshape(B, N, F4)
+            else:
+                d_m = torch.ops.aten.gelu_backward(d_a, m)
             d_h2 = self._gemm(d_m, blk.mlp.fc1.weight)
             d_x1 = ops.layernorm_bwd_add(d_h2, x1, mean2, rstd2, blk.norm2.weight, dx)
             d_o = self._gemm(d_x1, at.proj.weight).view(B, N, at.num_heads, at.head_dim)
@@ -247,7 +259,8 @@ class VisionTransformer(nn.Module):
             out = (dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2]) if need else None
             grads = buf.grads[l] if buf.grads is not None else None
             res = ops.attn_capture_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buf.probs[l], d_o, grads, 1.0 / at.scale,
-                                       _lib.SCALE_SCORES, need_dqkv=need, layout="bnhd", out=out, o=o_fwd, rel_row=row)
+                                       _lib.SCALE_SCORES, need_dqkv=need, layout="bnhd", out=out, o=o_fwd, rel_row=row,
+                                       images=M if K > 1 else None)
             if row is not None:
                 row = res[3]
             if on_layer_done is not None:
@@ -398,3 +411,84 @@ class GraphedRelevanceBatch(GraphedRelevance):
             self.output = call()
         self.buffers = model.buffers_       # the slabs the graph reads and writes stay alive with it
         self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
+
+
+def _fp32_body(model, who):
+    """The grouped row mode runs the exact-fp32 kernels only: refuse a bf16 / fp16 body by name."""
+    for what, dt in (("parameters", next(model.parameters()).dtype),
+                     ("backward_gemm_dtype", getattr(model, "backward_gemm_dtype", torch.float32)),
+                     ("capture_dtype", getattr(model, "capture_dtype", torch.float32))):
+        if dt != torch.float32:
+            raise _lib.MMXError("%s: fp32 bodies only (the exact-fp32 grouped row mode); this body's %s is %s"
+                                % (who, what, str(dt).replace("torch.", "")))
+
+
+def generate_relevance_batch_multi(model, images, indices=None, top_k=None):
+    """Relevancy maps of B DISTINCT images for K classes each, in one batch-B forward and one backward over the B*K targets:
+    ``[B, K, N-1]``.
+
+    Entry ``[b, k]`` equals ``generate_relevance_multi(model, images[b:b+1], indices[b])[k]`` (notebook cells 9-11 explain two
+    classes of each image, one full pass per class).  ``indices``: ``[B, K]`` class indices; ``None``: each image's ``top_k``
+    highest-scoring classes (default 1), picked on the device with ``topk`` (no host sync: capturable).  The forward runs once
+    per image; the backward carries row 0 of R for every target through the capture op's grouped exact-fp32 row mode
+    (``mmx_attn_capture_bwd_rowrel_f32_grouped``: an image's K targets share its forward operands).  fp32 bodies only."""
+    _fp32_body(model, "generate_relevance_batch_multi")
+    B = images.shape[0]
+    if indices is not None:
+        idx = torch.as_tensor(indices, device=images.device)
+        if idx.dim() != 2 or idx.shape[0] != B or idx.shape[1] < 1:
+            raise ValueError("generate_relevance_batch_multi: indices must be [B, K] = [%d, K], got %s" % (B, tuple(idx.shape)))
+        K = idx.shape[1]
+    else:
+        K = 1 if top_k is None else int(top_k)
+        if K < 1:
+            raise ValueError("generate_relevance_batch_multi: top_k must be >= 1")
+    if K == 1:
+        return generate_relevance_batch(model, images, None if indices is None else idx.reshape(B)).unsqueeze(1)
+    logits, state = model.forward_tape(images, grads=False)
+    if indices is None:
+        idx = logits.topk(K, dim=-1).indices
+    # K-major targets: t = k * B + b
+    T = K * B
+    d_logits = torch.zeros(T, logits.shape[-1], dtype=torch.float32, device=images.device)
+    d_logits.scatter_(1, idx.t().reshape(T, 1).long(), 1.0)
+    N = model.buffers_.probs.shape[-1]
+    row = torch.zeros(T, N, dtype=torch.float32, device=images.device)
+    row[:, 0] = 1.0
+    rows = model.backward_tape(state, d_logits, rel_row=row, targets_per_image=K)
+    return rows.view(K, B, N)[:, :, 1:].transpose(0, 1).contiguous()
+
+
+class GraphedRelevanceBatchMulti(GraphedRelevance):
+    """``generate_relevance_batch_multi`` captured once into a hipGraph and replayed (B, K and the image shape are fixed at
+    construction; ``indices=None``: each image's ``top_k`` classes, chosen on the device).
+
+        run = GraphedRelevanceBatchMulti(model, images, indices=labels)          # labels [B, K]
+        maps = run(next_images, next_labels)                                     # [B, K, N-1], the graph's output buffer
+    """
+
+    def __init__(self, model, input, indices=None, top_k=None, warmup=3):
+        self.input = input.clone()
+        self.indices = None if indices is None else torch.as_tensor(indices, device=input.device).clone()
+        call = lambda: generate_relevance_batch_multi(model, self.input, self.indices, top_k)   # noqa: E731
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                call()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(self.graph):
+            self.output = call()
+        self.buffers = model.buffers_       # the slabs the graph reads and writes stay alive with it
+        self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
+
+    def __call__(self, input=None, indices=None):
+        if input is not None:
+            self.input.copy_(input)
+        if indices is not None:
+            if self.indices is None:
+                raise ValueError("this graph picks its classes itself (top_k mode)")
+            self.indices.copy_(torch.as_tensor(indices, device=self.indices.device).reshape(self.indices.shape))
+        self.graph.replay()
+        return self.output
