@@ -375,6 +375,38 @@ int mmx_attn_capture_bwd_ex(const void* q_dev, const void* k_dev, const void* v_
                             int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
                             int need_dqkv, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Attention forward WITHOUT a capture slab: O = softmax(scale.Q.K^T + mask).V and nothing else.  The inference forward of the
+ * perturbation test (vit_perturbation.py), whose S x B re-runs of the model never look at P.  Arguments, layouts, mask
+ * broadcast strides and both scale modes as mmx_attn_capture_fwd, minus `probs_dev`; exact fp32; the same shape space as the
+ * fp32 capture forward (head_dim <= 64, else MMX_ENOTSUP), served by the same three kernel families under the same rules:
+ *   - where the capture forward runs its whole-head kernel (Nk <= 128, Nq <= 256, head_dim % 4 == 0, aligned views): that
+ *     kernel with the P store compiled out -- O is bit-identical to the capture forward's;
+ *   - longer sequences: ONE sweep over the keys with a running row maximum (the accumulators are rescaled when the maximum
+ *     moves, one division at the end): two products per key tile instead of the capture forward's three.  Same result up
+ *     to fp32 rounding; a fully masked row is NaN as there;
+ *   - any other head_dim / unaligned views: the general tiled kernel with the store compiled out.
+ * Every argument is checked before any HIP call (MMX_EINVAL). */
+int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev,
+                 int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                 int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                 int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                 const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
+                 void* o_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                 int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, void* stream);
+
+/* Patch perturbation test for image models (the positive / negative perturbation test of the paper at patch granularity;
+ * evaluator: vit_perturbation.py; same removal order and step counts as the bi-modal evaluators, lxmert/lxmert/perturbation.py:112).
+ * mmx_patch_ranks: scores [B, P] fp32 -> ranks [B, P] int32, ranks[b][i] = position of patch i in ONE stable descending order
+ *   of row b -- torch.sort(descending=True, stable=True): among equal scores the lower index first, +0.0 == -0.0, NaN before
+ *   +inf.  1 <= P <= 4096 (a 64 x 64 grid), else MMX_EINVAL.  The positive test ranks the negated map (the caller negates).
+ * mmx_perturb_patches: images [B, C, R, R] fp32, ranks [B, (R / patch)^2] int32, counts [S] int32 ON THE DEVICE, fill [C] fp32
+ *   -> out [S, B, C, R, R]:  out[s][b][c][y][x] = ranks[b][(y / patch) * (R / patch) + x / patch] < counts[s]
+ *   ? images[b][c][y][x] : fill[c].  One launch writes all S copies.  R % patch != 0 or S / B / C < 1: MMX_EINVAL.
+ * Both check every argument before any HIP call. */
+int mmx_patch_ranks(const void* scores_dev, void* ranks_dev, int B, int P, void* stream);
+int mmx_perturb_patches(const void* images_dev, const void* ranks_dev, const void* counts_dev, const void* fill_dev,
+                        void* out_dev, int B, int C, int R, int patch, int S, void* stream);
+
 /* Row-relevancy mode of the backward (BASELINE config 5; CLIP `interpret`, CLIP/clip/... notebook cell 7:27-37, returns
  * only `R[:, 0, 1:]` of the image tower): row 0 of  R_final = (I + A_L) ... (I + A_start)  is  e_0^T (I + A_L) ... , i.e.
  * a ROW vector carried from the top layer down -- the order the backward visits the layers anyway:

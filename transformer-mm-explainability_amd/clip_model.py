@@ -242,6 +242,52 @@ class Transformer(nn.Module):
                 x = x1 + mlp_out
         return x, tape
 
+    @torch.no_grad()
+    def forward_nocapture(self, x, out_rows=None):
+        """Inference forward of the stack: ``x [B, N, E]`` -> ``y [B, N, E]``, attention on ``ops.attn_fwd``.  No capture slab is
+        touched or allocated (``self.buffers`` stays as it is) and no tape is kept.  ``out_rows``: as in ``forward_tape`` (a
+        ``[B]`` long tensor), or a Python int when every sample reads the same row (the class token); the top block then runs on
+        those rows only -- with an int also its attention queries -- and ``y`` is ``[B, E]``.  fp32 bodies only."""
+        for what in ("forward_gemm_dtype", "capture_dtype"):
+            dt = getattr(self, what, torch.float32)
+            if dt != torch.float32:
+                raise _lib.MMXError("forward_nocapture: fp32 bodies only (the no-capture attention is exact fp32); this tower's "
+                                    "%s is %s" % (what, str(dt).replace("torch.", "")))
+        if x.dtype != torch.float32:
+            raise _lib.MMXError("forward_nocapture: fp32 bodies only; the input is %s" % str(x.dtype).replace("torch.", ""))
+        if not x.is_cuda:
+            raise _lib.MMXError("the CLIP body runs its attention on the HIP kernels: move the model and inputs to the GPU")
+        B, N, E = x.shape
+        blocks = list(self.resblocks)
+        mask = self._mask_for(blocks[0], N, x.device) if blocks else None
+        first = blocks[0].ln_1
+        _, h1, _, _ = ops.add_layernorm(x, None, first.weight, first.bias, first.eps)
+        for l, blk in enumerate(blocks):
+            at = blk.attn
+            top = out_rows is not None and l + 1 == len(blocks)
+            one = top and isinstance(out_rows, int)
+            qkv = self._linear(h1, at.in_proj_weight, at.in_proj_bias).view(B, N, 3, at.num_heads, at.head_dim)
+            q = qkv[:, out_rows:out_rows + 1, 0] if one else qkv[:, :, 0]
+            m_l = mask[out_rows:out_rows + 1] if (one and mask is not None) else mask
+            o = ops.attn_fwd(q, qkv[:, :, 1], qkv[:, :, 2], at.head_dim ** -0.5, _lib.SCALE_Q_FIRST, m_l, layout="bnhd")
+            if one:
+                xr, orows = x[:, out_rows], o.view(B, E)
+            elif top:
+                ar = torch.arange(B, device=x.device)
+                xr, orows = x[ar, out_rows], o.view(B, N, E)[ar, out_rows]
+            else:
+                xr, orows = x, o.view(B, N, E)
+            x1, h2, _, _ = ops.add_layernorm(xr, self._linear(orows, at.out_proj.weight, at.out_proj.bias), blk.ln_2.weight,
+                                             blk.ln_2.bias, blk.ln_2.eps)
+            mlp_out = self._linear(ops.quick_gelu_fwd(self._linear(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias)),
+                                   blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
+            if l + 1 < len(blocks):
+                nxt = blocks[l + 1].ln_1
+                x, h1, _, _ = ops.add_layernorm(x1, mlp_out, nxt.weight, nxt.bias, nxt.eps)
+            else:
+                x = x1 + mlp_out
+        return x
+
     def forward_shared(self, x, batch):
         """Shared-forward mode of ``forward_tape`` (kept under its round-1 name)."""
         if x.shape[0] != 1:
@@ -461,6 +507,21 @@ class VisualTransformer(nn.Module):
         return self.forward_tape(image, batch)
 
     @torch.no_grad()
+    def encode_nocapture(self, images=None, tokens=None):
+        """Inference forward -> image features ``[B, output_dim]`` (``Transformer.forward_nocapture``: no capture slab, no
+        tape; the top block on the class-token row only).  ``tokens [B, n, width]``: rows of the block input (``_embed``: class token first, position
+        embedding added, through ``ln_pre``, which is row-wise; any ``n``) instead of ``images``."""
+        if (images is None) == (tokens is None):
+            raise ValueError("encode_nocapture takes images or tokens (exactly one of them)")
+        if self.conv1.weight.dtype != torch.float32:
+            raise _lib.MMXError("encode_nocapture: fp32 bodies only; the parameters are %s"
+                                % str(self.conv1.weight.dtype).replace("torch.", ""))
+        x = self._embed(images) if tokens is None else tokens
+        cls = self.transformer.forward_nocapture(x, out_rows=0)
+        _, f, _, _ = ops.add_layernorm(cls, None, self.ln_post.weight, self.ln_post.bias, self.ln_post.eps)
+        return f @ self.proj
+
+    @torch.no_grad()
     def backward_tape(self, state, d_features, first_grad_layer=0, cls_row=False, targets_per_image=1):
         """``d_features [B, output_dim]``: per-sample upstream gradients of the image features.
         ``cls_row=True``: row-relevancy mode (``Transformer.backward_tape``): returns row 0 (the class token's) of the
@@ -566,6 +627,14 @@ class CLIP(nn.Module):
         rows, tape = self.transformer.forward_tape(x, first_grad_layer=first_grad_layer, out_rows=eot)
         _, f, mean, rstd = ops.add_layernorm(rows, None, self.ln_final.weight, self.ln_final.bias, self.ln_final.eps)
         return f @ self.text_projection, (tape, x.shape, rows, mean, rstd, eot)
+
+    @torch.no_grad()
+    def encode_text_nocapture(self, text):
+        """``encode_text`` as an inference forward (``Transformer.forward_nocapture``) -> ``features [B, embed_dim]``."""
+        x = self.token_embedding(text).type(self.dtype) + self.positional_embedding[:text.shape[1]].type(self.dtype)
+        rows = self.transformer.forward_nocapture(x, out_rows=text.argmax(dim=-1))         # model.py:360
+        _, f, _, _ = ops.add_layernorm(rows, None, self.ln_final.weight, self.ln_final.bias, self.ln_final.eps)
+        return f @ self.text_projection
 
     @torch.no_grad()
     def backward_text_tape(self, state, d_features, first_grad_layer=0):

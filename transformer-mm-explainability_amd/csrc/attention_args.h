@@ -17,6 +17,7 @@ struct AttnFwdArgs {
     int slab_dt;  // MMX_F32 | MMX_F16 | MMX_BF16: element type behind `probs` (non-fp32: streaming kernels only)
     int mma_bf16; // 1: products on v_mfma_f32_16x16x32_bf16 (operands rounded to bf16, fp32 accumulate, fp32 softmax)
     int tile_skip = 0;  // whole-head kernels: skip the products of key tiles that are masked out for a whole wave (attention_head.hip)
+    int no_probs = 0;   // mmx_attn_fwd: inference forward, `probs` is NULL (read by the host dispatchers only: they pick the NOP instantiations)
 };
 
 struct AttnBwdArgs {

@@ -309,8 +309,11 @@ __device__ __forceinline__ void stagger(int units) {
 
 // ------------------------------------------------------------------------------------------------------- forward
 // grid (H, B), blockDim = 64 * ceil(Nq / 16): wave w owns query rows [16w, 16w + 16).
-template <int DP, int NTK>
-__global__ __launch_bounds__(1024) void attn_fwd_head_kernel(const AttnFwdArgs a) {
+// NOP (mmx_attn_fwd, the inference forward): the P store is compiled out; O comes from the same registers, bit for bit.
+// Its widest key sides (NTK >= 7: 100+ live registers per lane) are capped at 8 waves so that they get 256 VGPRs and do not
+// spill; a head with more than 8 query strips is then split over blockIdx.z (each workgroup stages the head's K / V itself).
+template <int DP, int NTK, bool NOP = false>
+__global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_kernel(const AttnFwdArgs a) {
     constexpr int LSK = DP + 8, LSV = DP + 4, KK = DP / 16, NPk = NTK * 16;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;                 // [NPk][LSK]  A operand of S^T (ds_read_b128 along d)
@@ -320,7 +323,7 @@ __global__ __launch_bounds__(1024) void attn_fwd_head_kernel(const AttnFwdArgs a
     const int h = blockIdx.x, b = blockIdx.y;
     const int c16 = lane & 15, g = lane >> 4;
     const bool q_first = (a.scale_mode == MMX_SCALE_Q_FIRST);
-    const int q = wave * 16 + c16;
+    const int q = (NOP ? blockIdx.z * (nthreads >> 6) * 16 : 0) + wave * 16 + c16;
     const bool qv = q < a.Nq;
 
     stagger(a.debug >> 8);
@@ -395,7 +398,7 @@ __global__ __launch_bounds__(1024) void attn_fwd_head_kernel(const AttnFwdArgs a
     for (int t = 0; t < NTK; ++t) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[t][r] = acc[t][r] * inv_sum;
-        store_chunk(prow, t * 16 + 4 * g, a.Nk, qv && !(skip & 4), acc[t]);
+        if constexpr (!NOP) store_chunk(prow, t * 16 + 4 * g, a.Nk, qv && !(skip & 4), acc[t]);
     }
 
     // O = P.V with P straight from the accumulators: k-step (t, r) pairs P[q][16t + 4g + r] with V[16t + 4g + r][d]
@@ -636,13 +639,13 @@ static size_t bwd_head_lds(int DP, int NTK, int NTQ, bool rel = false) {
 }
 
 template <typename K, typename A>
-static int launch_head(K kern, const A& args, int threads, size_t lds, hipStream_t s, const char* name) {
+static int launch_head(K kern, const A& args, int threads, size_t lds, hipStream_t s, const char* name, int nz = 1) {
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
         if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     }
-    kern<<<dim3(args.H, args.B), threads, lds, s>>>(args);
+    kern<<<dim3(args.H, args.B, nz), threads, lds, s>>>(args);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, name);
     return MMX_OK;
@@ -663,6 +666,31 @@ static int fwd_head_dispatch(const AttnFwdArgs& a, int NTK, int threads, size_t 
         MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 6);
         MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 7);
         MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 8);
+    }
+    return MMX_ENOTSUP;
+}
+
+#define MMX_HEAD_CASE_NOP(DPV, N)                                                                              \
+    case N:                                                                                                    \
+        return launch_head(attn_fwd_head_kernel<DPV, N, true>, a, threads, lds, s, "attn_fwd_head_kernel<nop>", nz)
+
+template <int DP>
+static int fwd_head_dispatch_nop(const AttnFwdArgs& a, int NTK, int threads, size_t lds, hipStream_t s) {
+    int nz = 1;
+    if (NTK >= 7 && threads > 512) {        // (those instantiations are capped at 8 waves: two workgroups per head)
+        const int ntq = threads / 64;
+        nz = 2;
+        threads = 64 * ((ntq + 1) / 2);
+    }
+    switch (NTK) {
+        MMX_HEAD_CASE_NOP(DP, 1);
+        MMX_HEAD_CASE_NOP(DP, 2);
+        MMX_HEAD_CASE_NOP(DP, 3);
+        MMX_HEAD_CASE_NOP(DP, 4);
+        MMX_HEAD_CASE_NOP(DP, 5);
+        MMX_HEAD_CASE_NOP(DP, 6);
+        MMX_HEAD_CASE_NOP(DP, 7);
+        MMX_HEAD_CASE_NOP(DP, 8);
     }
     return MMX_ENOTSUP;
 }
@@ -698,7 +726,10 @@ int attn_fwd_head_try(const AttnFwdArgs& a_in, hipStream_t s, int* rc_out) {
         return 0;
     const int DP = a.D <= 32 ? 32 : 64, NTK = (a.Nk + 15) / 16, threads = 64 * ((a.Nq + 15) / 16);
     const size_t lds = fwd_head_lds(DP, NTK);
-    *rc_out = DP == 32 ? fwd_head_dispatch<32>(a, NTK, threads, lds, s) : fwd_head_dispatch<64>(a, NTK, threads, lds, s);
+    if (a.no_probs)     // mmx_attn_fwd: the same kernel, same launch geometry, no P store
+        *rc_out = DP == 32 ? fwd_head_dispatch_nop<32>(a, NTK, threads, lds, s) : fwd_head_dispatch_nop<64>(a, NTK, threads, lds, s);
+    else
+        *rc_out = DP == 32 ? fwd_head_dispatch<32>(a, NTK, threads, lds, s) : fwd_head_dispatch<64>(a, NTK, threads, lds, s);
     return 1;
 }
 

@@ -30,7 +30,8 @@ __device__ __forceinline__ void stage_tile(float* lds, const float* base, int64_
 }
 
 // ---------------------------------------------------------------------------------------------- forward
-template <int DP>
+// NOP (mmx_attn_fwd, the inference forward): the P store is compiled out.
+template <int DP, bool NOP = false>
 __global__ __launch_bounds__(256) void attn_capture_fwd_kernel(const AttnFwdArgs a) {
     constexpr int LS = DP + 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void attn_capture_fwd_kernel(const AttnFwdArgs
             float p = 0.f;
             if (j < a.Nk) {
                 p = srow[j] / sum;
-                prow[j] = p;
+                if constexpr (!NOP) prow[j] = p;
             }
             srow[j] = p;  // zero the key padding so phase 3 can run over whole 64-key tiles
         }
@@ -358,6 +359,32 @@ extern "C" int mmx_attn_capture_fwd_ex(const void* q_dev, const void* k_dev, con
     if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: K/V streamed, nothing of size Nk on chip
     if (D <= 32) return launch_dyn(attn_capture_fwd_kernel<32>, a, grid, attn_lds_bytes(32, Nk), s, "attn_capture_fwd_kernel<32>");
     return launch_dyn(attn_capture_fwd_kernel<64>, a, grid, attn_lds_bytes(64, Nk), s, "attn_capture_fwd_kernel<64>");
+}
+
+// The inference forward: the capture forward's fp32 dispatch with the no-slab instantiations.
+extern "C" int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                            int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                            const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
+                            int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, void* stream) {
+    MMX_CHECK_ARG(q_dev && k_dev && v_dev && o_dev, "mmx_attn_fwd: null pointer");
+    int rc = check_attn_dims("mmx_attn_fwd", B, H, Nq, Nk, D, scale_mode);
+    if (rc) return rc;
+    AttnFwdArgs a;
+    a.q = static_cast<const float*>(q_dev); a.k = static_cast<const float*>(k_dev); a.v = static_cast<const float*>(v_dev);
+    a.qs = {q_sb, q_sh, q_sn}; a.ks = {k_sb, k_sh, k_sn}; a.vs = {v_sb, v_sh, v_sn};
+    a.mask = static_cast<const float*>(mask_dev); a.mask_sb = mask_sb; a.mask_sq = mask_sq;
+    a.probs = nullptr; a.o = static_cast<float*>(o_dev); a.os = {o_sb, o_sh, o_sn};
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D; a.scale = scale; a.scale_mode = scale_mode; a.debug = 0;
+    a.slab_dt = MMX_F32;
+    a.mma_bf16 = 0;
+    a.no_probs = 1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (attn_fwd_head_try(a, s, &rc)) return rc;    // the whole-head kernel wherever the capture forward picks it
+    if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: one sweep with a running maximum
+    dim3 grid((Nq + kTQ - 1) / kTQ, H, B);
+    if (D <= 32)
+        return launch_dyn(attn_capture_fwd_kernel<32, true>, a, grid, attn_lds_bytes(32, Nk), s, "attn_capture_fwd_kernel<32, nop>");
+    return launch_dyn(attn_capture_fwd_kernel<64, true>, a, grid, attn_lds_bytes(64, Nk), s, "attn_capture_fwd_kernel<64, nop>");
 }
 
 extern "C" size_t mmx_attn_capture_bwd_workspace_bytes(int B, int H, int Nq) {

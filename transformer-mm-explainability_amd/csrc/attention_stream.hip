@@ -380,6 +380,111 @@ __global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_fwd_stream_ke
                 ob[static_cast<int64_t>(rows[r]) * a.os.sn + 16 * dt + i] = oacc[0][dt][r] + oacc[1][dt][r];
 }
 
+// =============================================================================================== forward, no capture slab
+// mmx_attn_fwd (inference: the perturbation re-runs never look at P).  Without a slab to fill with the NORMALISED P there is no
+// reason to know the row sum before P.V: ONE sweep over the keys with a running row maximum.  Per 64-key tile: S = Q.K^T, the
+// tile's row maximum over the 16 lanes of a row (DPP), p = exp(s - max), and -- only the accumulators of a row whose maximum
+// moved change value -- O and the lane-local row sum are rescaled by exp(old max - new max) before the tile's P.V is added.
+// The one division per row happens at the very end.  Two products per tile instead of the capture forward's three; K and V
+// tiles are fetched together, one tile ahead, exactly as sweep 2 above does.  Every lane of a row holds the same maximum, so
+// the lane-local sums merge with one group16_sum at the end.  A fully masked row: max = -inf, base 0, p = 0, sum 0 ->
+// O = 0 * (1 / 0) = NaN, like torch.softmax and the capture forward.
+template <int DP>
+__global__ __launch_bounds__(kThreads, DP == 32 ? 3 : 2) void attn_fwd_stream1_kernel(const AttnFwdArgs a) {
+    constexpr int LS = DP + 4, NB = DP / 16;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
+    float* Ks = smem;
+    float* Vs = Ks + kTile * LS;
+    float* Pw = Vs + kTile * LS + wave * 16 * kPS;
+    const int nrt = (a.Nq + kRows - 1) / kRows;            // 1-D grid, XCD-contiguous logical order (see attn_fwd_stream_kernel)
+    const int wg = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int h = (wg / nrt) % a.H, b = wg / (nrt * a.H);
+    const int rw = (wg % nrt) * kRows + wave * 16;
+    const float* qb = a.q + b * a.qs.sb + h * a.qs.sh;
+    const float* kb = a.k + b * a.ks.sb + h * a.ks.sh;
+    const float* vb = a.v + b * a.vs.sb + h * a.vs.sh;
+    const bool q_first = (a.scale_mode == MMX_SCALE_Q_FIRST);
+    const float ninf = -__builtin_inff();
+
+    f32x4 qa[NB];
+    load_a_rows<DP>(qa, qb, a.qs.sn, min(rw + i, a.Nq - 1), a.D, g, q_first ? a.scale : 1.f);
+
+    int rows[4];
+    const float* mrow[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        rows[r] = rw + 4 * g + r;
+        mrow[r] = a.mask ? a.mask + b * a.mask_sb + static_cast<int64_t>(min(rows[r], a.Nq - 1)) * a.mask_sq : nullptr;
+    }
+    auto score = [&](float s, int r, int k0, auto edge) {
+        constexpr bool EDGE = decltype(edge)::value;
+        if (!q_first) s = s / a.scale;
+        if (a.mask) s += mrow[r][EDGE ? min(k0 + i, a.Nk - 1) : k0 + i];
+        return (!EDGE || k0 + i < a.Nk) ? s : ninf;
+    };
+
+    const int ntiles = (a.Nk + kTile - 1) / kTile;
+    TileRegs<DP> kreg, vreg;
+    float m[4] = {ninf, ninf, ninf, ninf}, l[4] = {0.f, 0.f, 0.f, 0.f};   // row maximum so far (row-uniform), lane-local sum
+    f32x4 oacc[2][NB];
+#pragma unroll
+    for (int dt = 0; dt < NB; ++dt) oacc[0][dt] = oacc[1][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    auto sweep = [&](int kt, auto edge) {
+        constexpr bool EDGE = decltype(edge)::value;
+        f32x4 sacc[4];
+        tile_abt4<DP>(sacc, qa, Ks, i, g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float sv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) sv[t] = score(sacc[t][r], r, kt * kTile + 16 * t, edge);
+            const float mn = fmaxf(m[r], group16_max(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]))));
+            const float base = (mn == ninf) ? 0.f : mn;         // all keys masked so far: p = 0, sum stays 0
+            const float alpha = exp_fast(m[r] - base);          // 1 while the maximum stands; 0 for the first live tile
+            float psum = 0.f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                float p = exp_fast(sv[t] - base);
+                if (EDGE && kt * kTile + 16 * t + i >= a.Nk) p = 0.f;
+                psum += p;
+                Pw[(4 * g + r) * kPS + 16 * t + i] = p;
+            }
+            l[r] = l[r] * alpha + psum;
+            m[r] = mn;
+#pragma unroll
+            for (int dt = 0; dt < NB; ++dt) {
+                oacc[0][dt][r] *= alpha;
+                oacc[1][dt][r] *= alpha;
+            }
+        }
+        tile_wt<DP>(oacc, Pw, Vs, i, g);                        // same-wave LDS traffic is in order: no barrier needed
+    };
+    tile_fetch<DP>(kreg, kb, a.ks.sn, 0, a.Nk, a.D, tid);
+    tile_fetch<DP>(vreg, vb, a.vs.sn, 0, a.Nk, a.D, tid);
+    for (int kt = 0; kt < ntiles; ++kt) {
+        lds_barrier();
+        tile_store<DP>(Ks, kreg, 1.f, a.Nk, a.D, tid);
+        tile_store<DP>(Vs, vreg, 1.f, a.Nk, a.D, tid);
+        lds_barrier();
+        if (kt + 1 < ntiles) {
+            tile_fetch<DP>(kreg, kb, a.ks.sn, (kt + 1) * kTile, a.Nk, a.D, tid);
+            tile_fetch<DP>(vreg, vb, a.vs.sn, (kt + 1) * kTile, a.Nk, a.D, tid);
+        }
+        if (kt + 1 < ntiles) sweep(kt, std::false_type{}); else sweep(kt, std::true_type{});
+    }
+    float* ob = a.o + b * a.os.sb + h * a.os.sh;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float linv = 1.f / group16_sum(l[r]);
+#pragma unroll
+        for (int dt = 0; dt < NB; ++dt)
+            if (rows[r] < a.Nq && 16 * dt + i < a.D)
+                ob[static_cast<int64_t>(rows[r]) * a.os.sn + 16 * dt + i] = (oacc[0][dt][r] + oacc[1][dt][r]) * linv;
+    }
+}
+
 // =============================================================================================== forward, small grids
 // One shared forward (DETR's K kept queries of ONE image: B = 1, 8 heads, 950 tokens) gives the kernel above 15 x 8 = 120
 // workgroups, each walking all 15 key tiles twice behind workgroup barriers: 67 us for 0.9 GFLOP.  Here a workgroup owns 16
@@ -423,7 +528,8 @@ constexpr size_t split_lds_bytes() {
     return sizeof(float) * (4 * (2 * kTile * (DP + 4) + 16 * kPS) + 4 * 16 * 2);
 }
 
-template <int DP>
+// NOP (mmx_attn_fwd): the P store is compiled out, everything else as above.
+template <int DP, bool NOP = false>
 __global__ __launch_bounds__(kThreads, 1) void attn_fwd_split_kernel(const AttnFwdArgs a) {
     constexpr int LS = DP + 4, NB = DP / 16, kWave = 2 * kTile * LS + 16 * kPS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -453,7 +559,7 @@ __global__ __launch_bounds__(kThreads, 1) void attn_fwd_split_kernel(const AttnF
     for (int r = 0; r < 4; ++r) {
         rows[r] = rw + 4 * g + r;
         mrow[r] = a.mask ? a.mask + b * a.mask_sb + static_cast<int64_t>(min(rows[r], a.Nq - 1)) * a.mask_sq : nullptr;
-        pout[r] = rows[r] < a.Nq ? a.probs + (pbase + rows[r]) * a.Nk + i : nullptr;
+        pout[r] = (!NOP && rows[r] < a.Nq) ? a.probs + (pbase + rows[r]) * a.Nk + i : nullptr;
     }
     auto score = [&](float sc, int r, int k0) {           // every tile takes the key-range test here (few tiles per wave)
         if (!q_first) sc = sc / a.scale;
@@ -540,7 +646,7 @@ __global__ __launch_bounds__(kThreads, 1) void attn_fwd_split_kernel(const AttnF
             for (int r = 0; r < 4; ++r) {
                 float p = exp_fast(score(sacc[t][r], r, k0) - m[r]) * linv[r];
                 if (k0 + i >= a.Nk) p = 0.f;                                // (also keeps NaN rows out of the padding)
-                if (pout[r] && k0 + i < a.Nk) pout[r][k0] = p;
+                if constexpr (!NOP) { if (pout[r] && k0 + i < a.Nk) pout[r][k0] = p; }
                 Pw[(4 * g + r) * kPS + 16 * t + i] = p;
             }
         }
@@ -1036,6 +1142,17 @@ int attn_fwd_stream_try(const AttnFwdArgs& a, hipStream_t s, int* rc_out) {
     if ((!g_attn_stream && a.slab_dt == MMX_F32 && !a.mma_bf16) || a.D % 4 || a.D > 64) return 0;
     if (!aligned16(a.q, a.qs) || !aligned16(a.k, a.ks) || !aligned16(a.v, a.vs)) return 0;
     dim3 grid(((a.Nq + kRows - 1) / kRows) * a.H * a.B);
+    if (a.no_probs) {   // mmx_attn_fwd: the same eligibility and grid rules, kernels that write no slab
+        if (g_attn_fwd_split && grid.x < 160 && a.Nk > kTile) {
+            const dim3 g16(((a.Nq + 15) / 16) * a.H * a.B);
+            *rc_out = a.D <= 32 ? launch_stream(attn_fwd_split_kernel<32, true>, a, g16, split_lds_bytes<32>(), s, "attn_fwd_split_kernel<32, nop>")
+                                : launch_stream(attn_fwd_split_kernel<64, true>, a, g16, split_lds_bytes<64>(), s, "attn_fwd_split_kernel<64, nop>");
+            return 1;
+        }
+        *rc_out = a.D <= 32 ? launch_stream(attn_fwd_stream1_kernel<32>, a, grid, stream_lds_bytes<32>(2), s, "attn_fwd_stream1_kernel<32>")
+                            : launch_stream(attn_fwd_stream1_kernel<64>, a, grid, stream_lds_bytes<64>(2), s, "attn_fwd_stream1_kernel<64>");
+        return 1;
+    }
     // a grid that leaves most of the chip idle (one shared forward): 16-row workgroups whose waves split the keys
     if (g_attn_fwd_split && grid.x < 160 && a.slab_dt == MMX_F32 && !a.mma_bf16 && a.Nk > kTile) {
         const dim3 g16(((a.Nq + 15) / 16) * a.H * a.B);

@@ -819,6 +819,18 @@ def _bhnd_strides(t, layout):
     raise MMXError("layout %r" % layout)
 
 
+def _mask_strides(mask, Nk):
+    """``(mask fp32 contiguous, batch stride, query stride)`` of an additive ``[Nq, Nk]`` or ``[B, Nq | 1, Nk]`` mask."""
+    if mask is None:
+        return None, 0, 0
+    mask = _f32c(mask)
+    if mask.dim() == 2:          # [Nq, Nk]
+        return mask, 0, Nk
+    if mask.dim() == 3:          # [B, Nq or 1, Nk]
+        return mask, (mask.shape[1] * Nk if mask.shape[0] > 1 else 0), (Nk if mask.shape[1] > 1 else 0)
+    raise MMXError("mask must be [Nq,Nk] or [B,Nq|1,Nk]")
+
+
 def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="bnhd", mma_bf16=False):
     """``q``: ``[B, Nq, H, D]`` view (``layout='bnhd'``) or ``[B, H, Nq, D]``; writes P into ``probs_out``
     (``[B, H, Nq, Nk]`` fp32 contiguous, caller-owned slab) and returns O in the same layout as q.
@@ -836,22 +848,78 @@ def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, m
     if probs_out.dtype not in _DTYPES or not probs_out.is_contiguous() or probs_out.numel() != B * H * Nq * Nk:
         raise MMXError("probs_out must be a contiguous fp32 / fp16 / bf16 [B,H,Nq,Nk] slab")
     o = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    msb = msq = 0
-    if mask is not None:
-        mask = _f32c(mask)
-        if mask.dim() == 2:          # [Nq, Nk]
-            msb, msq = 0, Nk
-        elif mask.dim() == 3:        # [B, Nq or 1, Nk]
-            msb = mask.shape[1] * Nk if mask.shape[0] > 1 else 0
-            msq = Nk if mask.shape[1] > 1 else 0
-        else:
-            raise MMXError("mask must be [Nq,Nk] or [B,Nq|1,Nk]")
+    mask, msb, msq = _mask_strides(mask, Nk)
     check(lib().mmx_attn_capture_fwd_ex(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
                                         *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(probs_out),
                                         _DTYPES[probs_out.dtype] | (_lib.MMX_ATTN_MMA_BF16 if mma_bf16 else 0),
                                         _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D,
                                         float(scale), scale_mode, _stream()), "mmx_attn_capture_fwd")
     return o
+
+
+def attn_fwd(q, k, v, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="bnhd", out=None):
+    """Attention forward WITHOUT a capture slab (``mmx_attn_fwd``): operands, mask and scale modes as ``attn_capture_fwd``;
+    returns O in the layout of q.  Exact fp32.  Up to 128 keys it is the capture forward's whole-head kernel with the P store
+    compiled out (O bit-identical); beyond, one sweep over the keys with a running row maximum.  ``out``: a caller-owned fp32
+    tensor of q's shape (contiguous head_dim) to write O into."""
+    _dev(q, k, v, mask, out)
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
+        raise MMXError("attn_fwd is exact fp32 (no bf16 / fp16 mode yet), got %s" % str(q.dtype).replace("torch.", ""))
+    if layout == "bnhd":
+        B, Nq, H, D = q.shape
+        Nk = k.shape[1]
+    else:
+        B, H, Nq, D = q.shape
+        Nk = k.shape[2]
+    if out is not None and (out.dtype != torch.float32 or out.shape != q.shape):
+        raise MMXError("attn_fwd: out must be fp32 of q's shape %s" % (tuple(q.shape),))
+    o = out if out is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    mask, msb, msq = _mask_strides(mask, Nk)
+    check(lib().mmx_attn_fwd(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
+                             _p(mask), msb, msq, _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
+                             _stream()), "mmx_attn_fwd")
+    return o
+
+
+def patch_ranks(scores, out=None):
+    """``scores [B, P]`` fp32 -> ``ranks [B, P]`` int32: position of every patch in ONE stable descending order of its row
+    (``torch.sort(descending=True, stable=True)``: ties by ascending index, ``+0.0 == -0.0``, NaN first).  ``P <= 4096``."""
+    _dev(scores, out)
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise MMXError("patch_ranks: scores must be [B, P] fp32, got %s %s" % (tuple(scores.shape), scores.dtype))
+    scores = scores.contiguous()
+    if out is not None and (out.dtype != torch.int32 or out.shape != scores.shape or not out.is_contiguous()):
+        raise MMXError("patch_ranks: out must be a contiguous int32 tensor of the scores' shape")
+    ranks = out if out is not None else torch.empty(scores.shape, dtype=torch.int32, device=scores.device)
+    check(lib().mmx_patch_ranks(_p(scores), _p(ranks), scores.shape[0], scores.shape[1], _stream()), "mmx_patch_ranks")
+    return ranks
+
+
+def perturb_patches(images, ranks, counts, fill, out=None):
+    """``images [B, C, R, R]`` fp32, ``ranks [B, (R / patch)^2]`` int32, ``counts [S]`` int32 (device), ``fill [C]`` fp32 ->
+    ``[S, B, C, R, R]``: copy s keeps the pixels of the patches ranked below ``counts[s]`` and sets the others to ``fill[c]``
+    (one launch).  The patch size follows from ``ranks``' width."""
+    _dev(images, ranks, counts, fill, out)
+    if images.dim() != 4 or images.shape[2] != images.shape[3] or images.dtype != torch.float32:
+        raise MMXError("perturb_patches: images must be [B, C, R, R] fp32, got %s %s" % (tuple(images.shape), images.dtype))
+    B, C, R, _ = images.shape
+    if ranks.dtype != torch.int32 or ranks.dim() != 2 or ranks.shape[0] != B or counts.dtype != torch.int32 or counts.dim() != 1:
+        raise MMXError("perturb_patches: ranks must be [B, P] int32 and counts [S] int32")
+    grid = int(round(ranks.shape[1] ** 0.5))
+    if grid < 1 or grid * grid != ranks.shape[1] or R % grid:
+        raise MMXError("perturb_patches: %d patches are not a square grid that divides the resolution %d" % (ranks.shape[1], R))
+    fill = _f32c(fill).reshape(-1)
+    if fill.numel() != C:
+        raise MMXError("perturb_patches: fill needs one value per channel (%d), got %d" % (C, fill.numel()))
+    S = counts.shape[0]
+    images, ranks, counts = images.contiguous(), ranks.contiguous(), counts.contiguous()
+    if out is None:
+        out = torch.empty(S, B, C, R, R, dtype=torch.float32, device=images.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != S * B * C * R * R:
+        raise MMXError("perturb_patches: out must be a contiguous fp32 [S, B, C, R, R] tensor")
+    check(lib().mmx_perturb_patches(_p(images), _p(ranks), _p(counts), _p(fill), _p(out), B, C, R, R // grid, S, _stream()),
+          "mmx_perturb_patches")
+    return out
 
 
 def head_kernel_shape(n_q, n_k, head_dim, slab_dtype=torch.float32):

@@ -186,6 +186,39 @@ class VisionTransformer(nn.Module):
         return self.head(h1[:, 0]), (tape, x, mean1, rstd1)
 
     @torch.no_grad()
+    def forward_nocapture(self, images=None, tokens=None):
+        """Inference forward -> ``logits [B, C]``: no capture slab is touched or allocated and no tape is kept (the perturbation
+        test re-runs the model ``S x B`` times and never looks at the probabilities, ``vit_perturbation.py``).  The attention is
+        ``ops.attn_fwd``; the LayerNorms are fused with the residual adds as in ``_tape_forward``; the top block runs on the
+        class-token row only (its query, ``proj`` and MLP: everything after the attention is row-wise).  ``tokens [B, n, E]``:
+        an already embedded sequence, class token first (any ``n``: the drop mode of the perturbation test), instead of
+        ``images``.  fp32 bodies only."""
+        if (images is None) == (tokens is None):
+            raise ValueError("forward_nocapture takes images or tokens (exactly one of them)")
+        if self.head.weight.dtype != torch.float32:
+            raise _lib.MMXError("forward_nocapture: fp32 bodies only (the no-capture attention is exact fp32); the parameters are %s"
+                                % str(self.head.weight.dtype).replace("torch.", ""))
+        src = images if tokens is None else tokens
+        if not src.is_cuda:
+            raise _lib.MMXError("the ViT body runs its attention on the HIP kernels: move model and input to the GPU")
+        x = self._embed(images) if tokens is None else tokens
+        B, N, E = x.shape
+        first = self.blocks[0].norm1
+        _, h1, _, _ = ops.add_layernorm(x, None, first.weight, first.bias, first.eps)
+        for l, blk in enumerate(self.blocks):
+            at = blk.attn
+            top = l + 1 == self.depth
+            qkv = at.qkv(h1).view(B, N, 3, at.num_heads, at.head_dim)
+            q = qkv[:, :1, 0] if top else qkv[:, :, 0]
+            o = ops.attn_fwd(q, qkv[:, :, 1], qkv[:, :, 2], 1.0 / at.scale, _lib.SCALE_SCORES, None, layout="bnhd")
+            x1, h2, _, _ = ops.add_layernorm(x[:, :1] if top else x, at.proj(o.view(B, -1, E)), blk.norm2.weight, blk.norm2.bias,
+                                             blk.norm2.eps)
+            mlp_out = blk.mlp.fc2(F.gelu(blk.mlp.fc1(h2)))
+            nxt = self.norm if top else self.blocks[l + 1].norm1
+            x, h1, _, _ = ops.add_layernorm(x1, mlp_out, nxt.weight, nxt.bias, nxt.eps)
+        return self.head(h1[:, 0])
+
+    @torch.no_grad()
     def backward_shared(self, state, d_logits, on_layer_done=None):
         """``d_logits [K, C]``: K upstream gradients over the ONE forward; fills ``grads`` of every block (batch K).
         ``on_layer_done(l)``: called right after block l's gradient slab is complete on the current stream (the backward runs
