@@ -101,6 +101,9 @@ const char* mmx_last_error(void);
  *   "attn_bf16_v2"       1 (default) second-generation bf16 backward | 0: the streaming kernels' bf16 path
  *   "attn_fwd_split"     1 (default) streaming forward on a small grid (< 160 workgroups of 64 rows, fp32 slabs):
  *                        16-row workgroups whose waves split the keys | 0 always the 64-row kernel
+ *   "text_live_rows"     1 (default) mmx_live_rows builds the live-row list (the row-list backward of a causal tower: mmx_gemm_rows_f32
+ *                        and the *_rows kernels) | 0: it declines with MMX_ENOTSUP and the caller runs the dense backward (A / B runs)
+ *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
  *   "debug_flags"        profiling only (phase skipping), 0 in production; one meaning per bit for every chain kernel the dispatcher
  *                        may pick: 1 return before the hand-off / combine | 4 matrix waves skip the MFMAs | 8 layer-group kernel:
  *                        ticket without combine | 16 column kernel: no block rotation
@@ -203,6 +206,34 @@ int mmx_linear_f32(const void* x_dev, const void* wt_dev, const void* bias_dev, 
  * mmx_rows_add: dense[b, rows[b], :] += vals[b, :].  rows: int64 [B] (0 <= rows[b] < N), vals [B, E], E % 4 == 0, 16-byte aligned. */
 int mmx_rows_to_dense(const void* vals_dev, const void* rows_dev, void* out_dev, int B, int N, int E, void* stream);
 int mmx_rows_add(void* dense_dev, const void* rows_dev, const void* vals_dev, int B, int N, int E, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Row-list backward of a CAUSALLY MASKED tower whose feature is read at ONE token per sample (CLIP's text tower: the mask of
+ * CLIP/clip/model.py:334-340, the EOT token of model.py:360).  The upstream gradient enters at row eot[b] only and causal attention
+ * hands gradient to keys j <= i only, so in every layer every gradient row past eot[b] is an exact zero.  These entry points run the
+ * row-wise steps of the hand-written backward on the live rows alone, chosen ON THE DEVICE (nothing is read back; a captured
+ * hipGraph replays them for any input):
+ *   mmx_live_rows               rows[0 .. *count) = b * N + p for p <= clamp(eot[b], 0, N - 1), packed in (b, p) order; eot: int64 [B],
+ *                               rows: int32 [B * N] (capacity: every input fits), count: int32 [1].  MMX_ENOTSUP when option
+ *                               "text_live_rows" is 0 (mmx_set_option): the caller then runs the dense path.
+ *   mmx_gemm_rows_f32           C[r] = A[r] . W for the listed rows r, exact fp32 on the MFMA.  A: [cap_rows, K], C: [cap_rows, N], W: [K, N]
+ *                               (an nn.Linear weight as stored, [out, in], used as x @ weight), fp32 contiguous.  Eligible: N % 4 == 0,
+ *                               K % 4 == 0, 16-byte aligned operands; MMX_ENOTSUP otherwise.  Unlisted rows of C are not written, ids outside
+ *                               [0, cap_rows) are skipped.  Option "gemm_rows_tm": 32 (default) or 64 rows per workgroup tile.
+ *   mmx_quick_gelu_bwd_rows     mmx_quick_gelu_bwd on the listed rows of [cap_rows, row_elems] tensors (row_elems % 4 == 0).
+ *   mmx_layernorm_bwd_add_rows  mmx_layernorm_bwd_add on the listed rows (x / mean / rstd per row: x_rows == cap_rows).
+ * Non-finite values: the dense path multiplies the zero gradient of a dead row with that row's activations, so a non-finite
+ * activation at a padded position turns into a NaN there, as in the reference; these entry points never visit the row, and the
+ * caller's dead rows stay what they were (the attention backward is handed zeros for them).  Same class of deviation as
+ * MMX_CHAIN_CAUSAL above; it needs a forward that already produced non-finite activations. */
+int mmx_live_rows(const void* eot_dev, int B, int N, void* rows_dev, void* count_dev, void* stream);
+int mmx_gemm_rows_f32(const void* a_dev, const void* w_dev, void* c_dev, const void* rows_dev, const void* count_dev,
+                      int cap_rows, int N, int K, void* stream);
+int mmx_quick_gelu_bwd_rows(const void* x_dev, const void* dy_dev, void* dx_dev, const void* rows_dev, const void* count_dev,
+                            int cap_rows, int row_elems, void* stream);
+int mmx_layernorm_bwd_add_rows(const void* dy_dev, const void* x_dev, const void* mean_dev, const void* rstd_dev,
+                               const void* gamma_dev, const void* d_res_dev, void* dx_dev, const void* rows_dev,
+                               const void* count_dev, int cap_rows, int E, void* stream);
 
 /* The chain on VECTORS (rows-only DETR rules): when a caller returns single rows of R_q_i (`aggregated[:, target_index, :]`,
  * DETR/modules/ExplanationGenerator.py:180-182) the encoder product R_ii = (I + A_6) ... (I + A_1) (`:110-118`) is needed only

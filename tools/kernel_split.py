@@ -3,7 +3,8 @@
     python tools/kernel_split.py <results.db> <steps in the trace> > profiles/rNN_bench_kernel_split.json
 
 Families: library GEMMs (rocBLAS / hipBLASLt ``Cijk_*``), our attention-capture kernels, our chain kernels, our fused
-elementwise kernels (QuickGELU, LayerNorm forward / backward), ATen LayerNorm, ATen elementwise / copies / reductions.
+elementwise kernels (QuickGELU, LayerNorm forward / backward), our row-list GEMM (``gemm_rows_f32_kernel``: the text tower's
+backward on its live rows), ATen LayerNorm, ATen elementwise / copies / reductions.
 The trace should be taken with ``bench.py --headline-only`` so that it holds headline steps (plus the two graph warm-ups).
 """
 import json
@@ -21,6 +22,8 @@ def family(name):
         return "mmx_attention_capture"
     if "mmx::self_chain" in name or "mmx::avg_heads" in name or "mmx::bmm" in name or "mmx::row_normalise" in name:
         return "mmx_relevancy_chain"
+    if "mmx::gemm_rows" in name:
+        return "mmx_gemm_rows_fp32"
     if "mmx::" in name:
         return "mmx_fused_elementwise"
     if "layer_norm" in name:

@@ -89,6 +89,10 @@ _PROTOTYPES = {
     "mmx_linear_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_rows_to_dense": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_rows_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mmx_live_rows": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "mmx_gemm_rows_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mmx_quick_gelu_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "mmx_layernorm_bwd_add_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mmx_chain_matvec": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mmx_chain_vecmat_workspace_bytes": (_sz, [_i, _i]),
     "mmx_chain_vecmat": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),

@@ -43,20 +43,7 @@ def _is_causal_tower(tower):
     ``build_attention_mask``, CLIP/clip/model.py:334-340): its probabilities are then exact zeros there and the chain may skip that
     half (``_plan(causal=True)``).  Checked on the mask tensors themselves, once per mask object (one device -> host read, made during
     the warm-up call that precedes any hipGraph capture); anything else -- no mask, another mask -- is not causal."""
-    blocks = list(tower.resblocks)
-    masks = [getattr(blk, "attn_mask", None) for blk in blocks]
-    if not masks or any(m is None for m in masks):
-        return False
-    key = tuple(id(m) for m in masks)
-    cached = tower.__dict__.get("_causal_mask_check")
-    if cached is None or cached[0] != key:
-        ok = True
-        for m in {id(m): m for m in masks}.values():
-            n = m.shape[-1]
-            upper = torch.ones(n, n, dtype=torch.bool, device=m.device).triu_(1)
-            ok = ok and m.dim() == 2 and m.shape[0] == n and bool(torch.isneginf(m[upper]).all())
-        tower.__dict__["_causal_mask_check"] = cached = (key, ok)
-    return cached[1]
+    return tower.is_causal()
 
 
 def _side_stream(device):
@@ -78,6 +65,14 @@ def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, 
     last EOT of the batch influence nothing: their gradient rows are exactly zero and the returned ``R_text`` is the
     identity there.  With the flag the text tower runs only on the first ``max(EOT)+1`` positions and the ``[B,77,77]``
     result is assembled around that block -- identical output, 5-6x less text-tower work for caption-length inputs.
+
+    The text tower's backward runs on the rows up to each caption's EOT token only (on by default; ``clip_model.Transformer.
+    _live_rows_route``): the mask is causal and the feature is read at the EOT token, so every gradient row past it is an exact zero.
+    Unlike ``trim_text_padding`` this is decided on the device per call -- no read of the ids, shapes / slabs / accessors unchanged, a
+    captured graph follows whatever captions it is replayed with -- and it leaves the forward dense.  ``ops.set_option(
+    "text_live_rows", 0)`` switches it off process-wide.  Price: captions at the
+    truncation limit (77 tokens) have no dead rows and the row-list GEMM then does the library GEMM's work (figures, once measured:
+    ``profiles/text_backward_live_rows_probe.txt``); the switch is the answer for such inputs.
 
     ``overlap_towers`` (extra keyword, default on): image tower on a side stream, text tower on the current one (they
     only meet in the similarity head); ``False`` runs them back to back on the current stream.  Same results bit for bit.

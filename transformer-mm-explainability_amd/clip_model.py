@@ -182,6 +182,42 @@ class Transformer(nn.Module):
             mask = mask[:n_tokens, :n_tokens].contiguous()               # trimmed (padding-free) text batch
         return mask
 
+    def is_causal(self):
+        """True iff every block runs under an additive mask that is -inf strictly above the diagonal (CLIP's ``build_attention_mask``,
+        CLIP/clip/model.py:334-340).  Checked on the mask tensors themselves, once per mask object (one device -> host read, made
+        during the warm-up call that precedes any hipGraph capture); anything else -- no mask, another mask -- is not causal."""
+        masks = [getattr(blk, "attn_mask", None) for blk in self.resblocks]
+        if not masks or any(m is None for m in masks):
+            return False
+        key = tuple(id(m) for m in masks)
+        cached = self.__dict__.get("_causal_mask_check")
+        if cached is None or cached[0] != key:
+            ok = True
+            for m in {id(m): m for m in masks}.values():
+                n = m.shape[-1]
+                upper = torch.ones(n, n, dtype=torch.bool, device=m.device).triu_(1)
+                ok = ok and m.dim() == 2 and m.shape[0] == n and bool(torch.isneginf(m[upper]).all())
+            self.__dict__["_causal_mask_check"] = cached = (key, ok)
+        return cached[1]
+
+    def _live_rows_route(self, tape, B, N, E, first_grad_layer, dy_rows, dy_row_values, rel_row, grouped):
+        """The row-list backward (``ops.live_rows``): an fp32 tape of a causally masked tower whose upstream gradient is one row per
+        sample.  Gradient enters at row ``dy_rows[b]`` and causal attention hands it to keys ``j <= i`` only, so every gradient row
+        past it is an exact zero in every layer: the row-wise steps (input-gradient GEMMs, QuickGELU', LayerNorm') then run on the
+        rows up to it, picked on the device.  Returns the ``ops.LiveRows`` or ``None`` (dense path: any other caller, the
+        process-wide switch ``ops.set_option("text_live_rows", 0)``, or a weight outside ``ops.gemm_rows_eligible``)."""
+        top = self.layers - 1
+        if dy_rows is None or dy_row_values is None or rel_row is not None or grouped or top <= first_grad_layer:
+            return None
+        if getattr(self, "backward_gemm_dtype", torch.float32) != torch.float32 or dy_row_values.dtype != torch.float32:
+            return None
+        if tape[top][0].shape[0] != B or E % 4 or not self.is_causal():
+            return None
+        for blk in self.resblocks:
+            if not ops.gemm_rows_eligible(blk.mlp.c_proj.weight, blk.mlp.c_fc.weight, blk.attn.out_proj.weight, blk.attn.in_proj_weight):
+                return None
+        return ops.live_rows(dy_rows, N)
+
     @torch.no_grad()
     def forward_tape(self, x, batch=None, first_grad_layer=0, grads=True, out_rows=None):
         """``x``: ``[Bx, N, E]`` block input (embedded, through ``ln_pre`` for the image tower).  ``batch``: how many
@@ -312,6 +348,10 @@ class Transformer(nn.Module):
         ``dy_row_values`` (``[B, E]``, with ``dy_rows``): those rows themselves -- ``dy`` may then be ``None`` (no dense zero
         tensor is built just to be gathered from again).
 
+        With ``dy_rows`` / ``dy_row_values`` on the fp32 tape of a CAUSALLY masked tower (CLIP's text tower) everything below the top
+        block runs on the rows up to ``dy_rows[b]`` only (``_live_rows_route``): the rest of every gradient tensor is exact zeros.
+        The attention backward still sees a dense ``d_o`` (zeros in the dead rows) and writes the whole gradient slab.
+
         ``targets_per_image=K`` (fp32 body, row mode only): the tape holds M distinct samples and the B = K*M upstream gradients
         are K per sample in K-major order (target t explains sample t % M).  The elementwise steps broadcast the per-sample
         activations (modulo kernels); the capture op runs its grouped row mode (``ops.attn_capture_bwd(images=M)``)."""
@@ -343,6 +383,9 @@ class Transformer(nn.Module):
             raise ValueError("backward_tape: targets_per_image=%d needs an fp32 body in the row mode and a multiple of it "
                              "upstream gradients (got %d)" % (int(targets_per_image), B))
         dx_h = None
+        live = self._live_rows_route(tape, B, N, E, first_grad_layer, dy_rows, dy_row_values, rel_row, grouped)
+        d_o_dense = None      # live-row route: the top block's dense d_o (zeros outside the EOT rows); every block below rewrites its
+                              # live rows only, so the dead rows the attention backward reads stay zero without another pass
         for l in range(top, first_grad_layer - 1, -1):
             blk = self.resblocks[l]
             at = blk.attn
@@ -358,8 +401,15 @@ class Transformer(nn.Module):
                 g = dy_row_values if dy_row_values is not None else dy[torch.arange(B, device=dy_rows.device), dy_rows]
                 d_x1_r, d_o = self._top_block_rows(blk, tape[l], g, dy_rows, shared, N, x.shape[0] if grouped else None)
                 d_x1, top_rows = None, (dy_rows, d_x1_r)
+                d_o_dense = d_o
                 if att16:
                     d_o = d_o.to(torch.bfloat16)
+            elif live is not None:
+                d_a = ops.gemm_rows(dx, blk.mlp.c_proj.weight, live)
+                d_m = ops.quick_gelu_bwd_rows(m, d_a, live)
+                d_h2 = ops.gemm_rows(d_m, blk.mlp.c_fc.weight, live)
+                d_x1 = ops.layernorm_bwd_add_rows(d_h2, x1, mean2, rstd2, blk.ln_2.weight, dx, live)
+                d_o = ops.gemm_rows(d_x1, at.out_proj.weight, live, out=d_o_dense)
             elif stream16:
                 if dx_h is None:
                     dx_h = dx.to(torch.bfloat16)
@@ -395,6 +445,9 @@ class Transformer(nn.Module):
                 dq_in = dqkv.view(B, N, 3 * E)
                 d_h1 = ops.backward_gemm_bf16(dq_in if att16 else dq_in.to(torch.bfloat16), at.in_proj_weight)
                 dx, dx_h = ops.layernorm_bwd_add_bf16(d_h1, x, mean1, rstd1, blk.ln_1.weight, d_x1)
+            elif live is not None:
+                d_h1 = ops.gemm_rows(dqkv.view(B, N, 3 * E), at.in_proj_weight, live)
+                dx = ops.layernorm_bwd_add_rows(d_h1, x, mean1, rstd1, blk.ln_1.weight, d_x1, live)
             else:
                 d_h1 = self._gemm(dqkv.view(B, N, 3 * E), at.in_proj_weight)
                 dx = ops.layernorm_bwd_add(d_h1, x, mean1, rstd1, blk.ln_1.weight, d_x1)

@@ -43,10 +43,22 @@ __global__ __launch_bounds__(256) void quick_gelu_fwd_bf16_kernel(const f32x4* _
 
 // x_n4: number of 16-byte groups of x; x_n4 < n4 broadcasts x over the leading (batch) dimension of dy -- the shared-forward
 // backward has ONE activation tensor for B upstream gradients.
+// ROWS: the row-list form (gemm_rows_f32.hip): only the *count rows of `row4` 16-byte groups that `rows` names are read and written,
+// x at the same row as dy; n4 is then the capacity (cap rows) and bounds the ids.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void quick_gelu_bwd_kernel(const f32x4* __restrict__ x, const f32x4* __restrict__ dy,
                                                              f32x4* __restrict__ dx, int64_t n4, int64_t x_n4, const float* xt,
-                                                             const float* dyt, float* dxt, int tail) {
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<int64_t>(gridDim.x) * 256) {
+                                                             const float* dyt, float* dxt, int tail, const int* __restrict__ rows,
+                                                             const int* __restrict__ count, int row4) {
+    const int64_t cap = ROWS ? n4 / row4 : 0;
+    const int64_t total = ROWS ? (*count < cap ? *count : cap) * row4 : n4;
+    for (int64_t j = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; j < total; j += static_cast<int64_t>(gridDim.x) * 256) {
+        int64_t i = j;
+        if constexpr (ROWS) {
+            const int64_t r = rows[j / row4];
+            if (r < 0 || r >= cap) continue;              // an id outside the tensor is no row at all
+            i = r * row4 + j % row4;
+        }
         const f32x4 v = x[x_n4 == n4 ? i : i % x_n4];
         const f32x4 g = dy[i];
         f32x4 o;
@@ -57,7 +69,7 @@ __global__ __launch_bounds__(256) void quick_gelu_bwd_kernel(const f32x4* __rest
         }
         dx[i] = o;
     }
-    if (blockIdx.x == 0 && threadIdx.x < tail) {
+    if (!ROWS && blockIdx.x == 0 && threadIdx.x < tail) {
         const float v = xt[threadIdx.x], s = sigmoid_f(1.702f * v);
         dxt[threadIdx.x] = dyt[threadIdx.x] * (s + 1.702f * v * s * (1.f - s));
     }
@@ -93,9 +105,9 @@ extern "C" int mmx_quick_gelu_bwd_bcast(const void* x_dev, const void* dy_dev, v
     MMX_CHECK_ARG(((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dy_dev) |
                     reinterpret_cast<uintptr_t>(dx_dev)) & 15u) == 0, "mmx_quick_gelu_bwd_bcast: pointers must be 16-byte aligned");
     const int64_t n4 = n / 4;
-    quick_gelu_bwd_kernel<<<gelu_grid(n4), 256, 0, static_cast<hipStream_t>(stream)>>>(
+    quick_gelu_bwd_kernel<false><<<gelu_grid(n4), 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const f32x4*>(x_dev), static_cast<const f32x4*>(dy_dev), static_cast<f32x4*>(dx_dev), n4, x_n / 4, nullptr,
-        nullptr, nullptr, 0);
+        nullptr, nullptr, 0, nullptr, nullptr, 1);
     MMX_LAUNCH_CHECK("quick_gelu_bwd_kernel");
     return MMX_OK;
 }
@@ -108,10 +120,26 @@ extern "C" int mmx_quick_gelu_bwd(const void* x_dev, const void* dy_dev, void* d
     const float* x = static_cast<const float*>(x_dev);
     const float* dy = static_cast<const float*>(dy_dev);
     float* dx = static_cast<float*>(dx_dev);
-    quick_gelu_bwd_kernel<<<gelu_grid(n4), 256, 0, static_cast<hipStream_t>(stream)>>>(
+    quick_gelu_bwd_kernel<false><<<gelu_grid(n4), 256, 0, static_cast<hipStream_t>(stream)>>>(
         reinterpret_cast<const f32x4*>(x), reinterpret_cast<const f32x4*>(dy), reinterpret_cast<f32x4*>(dx), n4, n4, x + n4 * 4,
-        dy + n4 * 4, dx + n4 * 4, static_cast<int>(n - n4 * 4));
+        dy + n4 * 4, dx + n4 * 4, static_cast<int>(n - n4 * 4), nullptr, nullptr, 1);
     MMX_LAUNCH_CHECK("quick_gelu_bwd_kernel");
+    return MMX_OK;
+}
+
+// Row-list form: x, dy, dx are [cap_rows, row_elems]; only the listed rows are touched (rows / count: mmx_live_rows).
+extern "C" int mmx_quick_gelu_bwd_rows(const void* x_dev, const void* dy_dev, void* dx_dev, const void* rows_dev, const void* count_dev,
+                                       int cap_rows, int row_elems, void* stream) {
+    MMX_CHECK_ARG(x_dev && dy_dev && dx_dev && rows_dev && count_dev, "mmx_quick_gelu_bwd_rows: null pointer");
+    MMX_CHECK_ARG(cap_rows > 0 && row_elems > 0 && row_elems % 4 == 0, "mmx_quick_gelu_bwd_rows: cap_rows=%d row_elems=%d (%% 4 must be 0)",
+                  cap_rows, row_elems);
+    MMX_CHECK_ARG(((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(dy_dev) |
+                    reinterpret_cast<uintptr_t>(dx_dev)) & 15u) == 0, "mmx_quick_gelu_bwd_rows: pointers must be 16-byte aligned");
+    const int64_t n4 = static_cast<int64_t>(cap_rows) * (row_elems / 4);
+    quick_gelu_bwd_kernel<true><<<gelu_grid(n4), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        static_cast<const f32x4*>(x_dev), static_cast<const f32x4*>(dy_dev), static_cast<f32x4*>(dx_dev), n4, n4, nullptr, nullptr,
+        nullptr, 0, static_cast<const int*>(rows_dev), static_cast<const int*>(count_dev), row_elems / 4);
+    MMX_LAUNCH_CHECK("quick_gelu_bwd_kernel<rows>");
     return MMX_OK;
 }
 
@@ -125,12 +153,20 @@ extern "C" int mmx_quick_gelu_bwd(const void* x_dev, const void* dy_dev, void* d
 // ---------------------------------------------------------------------------------------------------------------------
 namespace mmx {
 
+// ROWS: the row-list form (gemm_rows_f32.hip): wave j takes row list[j] of the *count listed ones, `rows` is the capacity.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void layernorm_bwd_add_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                 const float* __restrict__ gamma, const float* d_res,
-                                                                float* __restrict__ dx, int64_t rows, int x_rows, int E) {
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+                                                                float* __restrict__ dx, int64_t rows, int x_rows, int E,
+                                                                const int* __restrict__ list, const int* __restrict__ count) {
+    int64_t r = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
+    if constexpr (ROWS) {
+        if (r >= *count) return;
+        r = list[r];
+        if (r < 0 || r >= rows) return;                   // an id outside the tensor is no row at all
+    }
     const int lane = threadIdx.x & 63;
     const int m = static_cast<int>(r % x_rows);
     const f32x4* dyr = reinterpret_cast<const f32x4*>(dy + r * E);
@@ -168,11 +204,26 @@ extern "C" int mmx_layernorm_bwd_add(const void* dy_dev, const void* x_dev, cons
     MMX_CHECK_ARG(dy_dev && x_dev && mean_dev && rstd_dev && gamma_dev && dx_dev, "mmx_layernorm_bwd_add: null pointer");
     MMX_CHECK_ARG(rows > 0 && x_rows > 0 && E > 0 && E % 4 == 0, "mmx_layernorm_bwd_add: rows=%ld x_rows=%d E=%d (E %% 4 must be 0)",
                   static_cast<long>(rows), x_rows, E);
-    mmx::layernorm_bwd_add_kernel<<<static_cast<unsigned>((rows + 3) / 4), 256, 0, static_cast<hipStream_t>(stream)>>>(
+    mmx::layernorm_bwd_add_kernel<false><<<static_cast<unsigned>((rows + 3) / 4), 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const float*>(dy_dev), static_cast<const float*>(x_dev), static_cast<const float*>(mean_dev),
         static_cast<const float*>(rstd_dev), static_cast<const float*>(gamma_dev), static_cast<const float*>(d_res_dev),
-        static_cast<float*>(dx_dev), rows, x_rows, E);
+        static_cast<float*>(dx_dev), rows, x_rows, E, nullptr, nullptr);
     MMX_LAUNCH_CHECK("layernorm_bwd_add_kernel");
+    return MMX_OK;
+}
+
+// Row-list form: dy, x, d_res, dx are [cap_rows, E], mean / rstd [cap_rows]; only the listed rows are touched (mmx_live_rows).
+extern "C" int mmx_layernorm_bwd_add_rows(const void* dy_dev, const void* x_dev, const void* mean_dev, const void* rstd_dev,
+                                          const void* gamma_dev, const void* d_res_dev, void* dx_dev, const void* rows_dev,
+                                          const void* count_dev, int cap_rows, int E, void* stream) {
+    MMX_CHECK_ARG(dy_dev && x_dev && mean_dev && rstd_dev && gamma_dev && dx_dev && rows_dev && count_dev,
+                  "mmx_layernorm_bwd_add_rows: null pointer");
+    MMX_CHECK_ARG(cap_rows > 0 && E > 0 && E % 4 == 0, "mmx_layernorm_bwd_add_rows: cap_rows=%d E=%d (E %% 4 must be 0)", cap_rows, E);
+    mmx::layernorm_bwd_add_kernel<true><<<static_cast<unsigned>((cap_rows + 3) / 4), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        static_cast<const float*>(dy_dev), static_cast<const float*>(x_dev), static_cast<const float*>(mean_dev),
+        static_cast<const float*>(rstd_dev), static_cast<const float*>(gamma_dev), static_cast<const float*>(d_res_dev),
+        static_cast<float*>(dx_dev), cap_rows, cap_rows, E, static_cast<const int*>(rows_dev), static_cast<const int*>(count_dev));
+    MMX_LAUNCH_CHECK("layernorm_bwd_add_kernel<rows>");
     return MMX_OK;
 }
 

@@ -1,0 +1,202 @@
+// K_gemm_rows_f32: C[r] = A[r] . W for the rows r of a device-side list, exact fp32 on v_mfma_f32_32x32x2_f32 -- the input-gradient
+// GEMMs of a causally masked tower's backward (CLIP's text tower, CLIP/clip/model.py:334-340, 360: the feature is read at the EOT
+// token, so every gradient row past it is an exact zero; 89 % of the rows at caption lengths), plus the kernel that builds the list.
+//
+// The product follows bmm_f32_tiles.hip (k-fastest A tile read with one ds_read_b128 per four MFMA steps, n-fastest B tile, 16-byte
+// global loads, two LDS stages with one barrier per 16-wide K slab and PF slabs requested ahead into registers).  What differs:
+//   * M is a DEVICE-side count: the grid is sized for the capacity (every row of the dense tensor), a workgroup whose row tile starts
+//     at or beyond the count returns at once.  Nothing is read back, the launch is the same for every input (hipGraph replays it).
+//   * a thread's A row address goes through the list once, before the K loop; output rows are scattered back to the same dense
+//     layout, unlisted rows are neither read nor written.
+//   * few rows must still spread over the chip: TM = 32 rows x 64 columns per workgroup, the four waves as 2 column halves x 2 halves of
+//     every K slab (their accumulators meet in LDS at the end); TM = 64 is the 2 x 2 layout of bmm_f32_tiles.hip.
+//   * workgroups are NOT made XCD-contiguous: the live tiles are the first few of the capacity grid, and the plain round-robin spreads
+//     exactly those over the eight XCDs.
+// W is the nn.Linear parameter as stored ([out, in] = [K, N] row-major here), used as x @ weight like ops.backward_gemm.
+#include "mmx_common.h"
+
+namespace mmx {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+static int g_text_live_rows = 1;   // option "text_live_rows": 1 (default) the row-list backward route is offered | 0: mmx_live_rows declines
+static int g_gemm_rows_tm = 32;    // option "gemm_rows_tm": rows per workgroup tile, 32 (default) or 64 (A / B runs)
+bool text_live_rows_option(const char* key, int value) {
+    if (strcmp(key, "text_live_rows") == 0 && value >= 0 && value <= 1) { g_text_live_rows = value; return true; }
+    if (strcmp(key, "gemm_rows_tm") == 0 && (value == 32 || value == 64)) { g_gemm_rows_tm = value; return true; }
+    return false;
+}
+
+// rows[0 .. count) = b * N + p for p <= clamp(eot[b], 0, N - 1), samples in order, positions in order; one workgroup.
+__global__ __launch_bounds__(256) void live_rows_kernel(const long long* __restrict__ eot, int B, int N, int* __restrict__ rows,
+                                                        int* __restrict__ count) {
+    __shared__ int len[256], off[256];
+    __shared__ int base;
+    if (threadIdx.x == 0) base = 0;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int b = b0 + threadIdx.x;
+        if (b < B) {
+            const long long e = eot[b];
+            len[threadIdx.x] = static_cast<int>(e < 0 ? 0 : (e > N - 1 ? N - 1 : e)) + 1;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int run = base;
+            const int n = min(256, B - b0);
+            for (int i = 0; i < n; ++i) { off[i] = run; run += len[i]; }
+            base = run;
+        }
+        __syncthreads();
+        const int n = min(256, B - b0);
+        for (int i = 0; i < n; ++i)
+            for (int p = threadIdx.x; p < len[i]; p += 256) rows[off[i] + p] = (b0 + i) * N + p;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = base;
+}
+
+constexpr int kRowsBK = 16, kRowsTN = 64;
+
+template <int TM, int PF>
+__global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __restrict__ A, const float* __restrict__ W,
+                                                               float* __restrict__ C, const int* __restrict__ rows,
+                                                               const int* __restrict__ count, int cap, int N, int K) {
+    constexpr int TN = kRowsTN, BK = kRowsBK;
+    constexpr int WR = TM / 32;                      // wave rows (one 32 x 32 MFMA tile per wave)
+    constexpr int WK = 2 / WR;                       // waves sharing an output tile, each on its own 8-wide k groups of a slab
+    constexpr int LA = BK + 4;                       // A stage: [TM][20] floats, k fastest
+    constexpr int LB = TN + 4;                       // B stage: [16][68] floats, n fastest
+    __shared__ __attribute__((aligned(16))) float As[2][TM * LA];
+    __shared__ __attribute__((aligned(16))) float Bs[2][BK * LB];
+    __shared__ __attribute__((aligned(16))) float red[WK == 2 ? 2 * 16 * 64 : 4];
+    __shared__ int rid[TM];                          // dense row of every tile row, -1: none
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wc = wave & 1, wr = WR == 2 ? wave >> 1 : 0, wk = WR == 2 ? 0 : wave >> 1;
+    const int M = min(*count, cap);
+    const int tiles_n = (N + TN - 1) / TN;
+    const int bx = blockIdx.x % tiles_n, by = blockIdx.x / tiles_n;
+    const int m0 = by * TM, n0 = bx * TN;
+    if (m0 >= M) return;                             // (workgroup-uniform: no barrier has been reached)
+
+    auto dense_row = [&](int gm) {
+        const int r = gm < M ? rows[gm] : -1;
+        return static_cast<unsigned>(r) < static_cast<unsigned>(cap) ? r : -1;   // an id outside the tensor is no row at all
+    };
+    if (tid < TM) rid[tid] = dense_row(m0 + tid);    // (published by the barrier in front of the first slab)
+
+    f32x16 acc;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+
+    // per-thread chunk addresses, fixed for the whole K loop: one 16-byte chunk of the A slab (the first TM * 4 threads), one of B
+    const bool has_a = tid < TM * 4;
+    const int ar = tid >> 2, ka = (tid & 3) * 4;
+    const int arow = has_a ? dense_row(m0 + ar) : -1;
+    const bool oka = arow >= 0;
+    const float* pa = A + static_cast<int64_t>(oka ? arow : 0) * K + ka;
+    const int kb = tid / (TN / 4), nbl = (tid % (TN / 4)) * 4;
+    const bool okb = n0 + nbl < N;                   // N % 4 == 0: a chunk is inside or outside as a whole
+    const float* pb = W + static_cast<int64_t>(kb) * N + (okb ? n0 + nbl : 0);
+    f32x4 ra[PF], rb[PF];                            // slab t waits in register set t % PF
+    auto fetch = [&](int k0, f32x4& xa, f32x4& xb) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        xa = (oka && k0 + ka < K) ? ldg4_u(pa + k0) : z;                            // K % 4 == 0
+        xb = (okb && k0 + kb < K) ? ldg4_u(pb + static_cast<int64_t>(k0) * N) : z;
+    };
+    auto stash = [&](int stage, const f32x4& xa, const f32x4& xb) {
+        if (has_a) *reinterpret_cast<f32x4*>(&As[stage][ar * LA + ka]) = xa;
+        *reinterpret_cast<f32x4*>(&Bs[stage][kb * LB + nbl]) = xb;
+    };
+
+    const int li = lane & 31, lg = lane >> 5;
+    const bool on = __builtin_amdgcn_readfirstlane(m0 + wr * 32) < M && __builtin_amdgcn_readfirstlane(n0 + wc * 32) < N;
+    const int nslab = (K + BK - 1) / BK;
+    fetch(0, ra[0], rb[0]);
+    stash(0, ra[0], rb[0]);
+#pragma unroll
+    for (int j = 1; j <= PF; ++j)                    // slabs 1 .. PF in flight (set 0 is free again)
+        if (j < nslab) fetch(j * BK, ra[j % PF], rb[j % PF]);
+    lds_barrier();
+    for (int s0 = 0; s0 < nslab; s0 += PF) {
+#pragma unroll
+        for (int j = 0; j < PF; ++j) {
+            const int s = s0 + j;
+            if (s >= nslab) break;
+            const int stage = s & 1;
+            if (s + 1 < nslab) {
+                // every wave left stage ^ 1 at the barrier that ended slab s - 1 (bmm_f32_tiles.hip)
+                stash(stage ^ 1, ra[(j + 1) % PF], rb[(j + 1) % PF]);
+                if (s + 1 + PF < nslab) fetch((s + 1 + PF) * BK, ra[(j + 1) % PF], rb[(j + 1) % PF]);
+            }
+            const float* Asl = &As[stage][(wr * 32 + li) * LA + 4 * lg];
+            const float* Bsl = &Bs[stage][(4 * lg) * LB + wc * 32 + li];
+            if (on) {
+#pragma unroll
+                for (int jj = wk; jj < BK / 8; jj += WK) {
+                    // MFMA step t of the 8-wide k group jj takes k = 8 jj + 4 (lane >> 5) + t
+                    const f32x4 av = *reinterpret_cast<const f32x4*>(Asl + 8 * jj);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], Bsl[(8 * jj + t) * LB], acc, 0, 0, 0);
+                }
+            }
+            if (s + 1 < nslab) lds_barrier();
+        }
+    }
+    if constexpr (WK == 2) {                         // the two k halves of a tile meet: wk = 1 hands its accumulators to wk = 0
+        if (wk == 1)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) red[(wc * 16 + v) * 64 + lane] = acc[v];
+        lds_barrier();
+        if (wk == 1) return;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[v] += red[(wc * 16 + v) * 64 + lane];
+    }
+    const int gn = n0 + wc * 32 + li;
+    if (!on || gn >= N) return;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int r = rid[wr * 32 + (v >> 2) * 8 + lg * 4 + (v & 3)];
+        if (r >= 0) C[static_cast<int64_t>(r) * N + gn] = acc[v];
+    }
+}
+
+}  // namespace mmx
+
+using namespace mmx;
+
+extern "C" int mmx_live_rows(const void* eot_dev, int B, int N, void* rows_dev, void* count_dev, void* stream) {
+    MMX_CHECK_ARG(eot_dev && rows_dev && count_dev, "mmx_live_rows: null pointer");
+    MMX_CHECK_ARG(B > 0 && N > 0 && static_cast<int64_t>(B) * N < (1ll << 31), "mmx_live_rows: B=%d N=%d (B * N must fit an int)", B, N);
+    if (!g_text_live_rows) {
+        set_error("mmx_live_rows: the row-list route is switched off (option text_live_rows = 0)");
+        return MMX_ENOTSUP;
+    }
+    live_rows_kernel<<<1, 256, 0, static_cast<hipStream_t>(stream)>>>(static_cast<const long long*>(eot_dev), B, N,
+                                                                      static_cast<int*>(rows_dev), static_cast<int*>(count_dev));
+    MMX_LAUNCH_CHECK("live_rows_kernel");
+    return MMX_OK;
+}
+
+extern "C" int mmx_gemm_rows_f32(const void* a_dev, const void* w_dev, void* c_dev, const void* rows_dev, const void* count_dev,
+                                 int cap_rows, int N, int K, void* stream) {
+    MMX_CHECK_ARG(a_dev && w_dev && c_dev && rows_dev && count_dev, "mmx_gemm_rows_f32: null pointer");
+    MMX_CHECK_ARG(cap_rows > 0 && N > 0 && K > 0, "mmx_gemm_rows_f32: cap_rows=%d N=%d K=%d", cap_rows, N, K);
+    if (N % 4 || K % 4 ||
+        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(c_dev)) & 15u)) {
+        set_error("mmx_gemm_rows_f32: N=%d and K=%d must be multiples of 4 and the operands 16-byte aligned", N, K);
+        return MMX_ENOTSUP;
+    }
+    const int tm = g_gemm_rows_tm;
+    const int64_t wgs = static_cast<int64_t>((N + kRowsTN - 1) / kRowsTN) * ((cap_rows + tm - 1) / tm);
+    MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
+    const float *A = static_cast<const float*>(a_dev), *W = static_cast<const float*>(w_dev);
+    const int *rows = static_cast<const int*>(rows_dev), *count = static_cast<const int*>(count_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (tm == 32)
+        gemm_rows_f32_kernel<32, 3><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, static_cast<float*>(c_dev), rows, count, cap_rows, N, K);
+    else
+        gemm_rows_f32_kernel<64, 3><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, static_cast<float*>(c_dev), rows, count, cap_rows, N, K);
+    MMX_LAUNCH_CHECK("gemm_rows_f32_kernel");
+    return MMX_OK;
+}

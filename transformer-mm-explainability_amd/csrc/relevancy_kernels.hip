@@ -1020,6 +1020,7 @@ extern "C" int mmx_set_option(const char* key, int value) {
         g_bmm_tiles = value;
         return MMX_OK;
     }
+    if (key && text_live_rows_option(key, value)) return MMX_OK;
     if (key && strcmp(key, "self_chain_nt") == 0 && value >= 0 && value <= 1) {
         g_chain_nt = value;
         return MMX_OK;

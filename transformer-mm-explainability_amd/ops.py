@@ -624,6 +624,87 @@ def rows_add_(dense, rows, vals):
     return dense
 
 
+class LiveRows:
+    """Device-side list of the live rows of a ``[B, N, *]`` gradient stream (``live_rows``): ``rows`` int32 ``[B * N]`` (the first
+    ``count[0]`` entries are valid), ``count`` int32 ``[1]``.  ``poison``: debug switch of the ``*_rows`` wrappers below -- their
+    outputs start as NaN instead of uninitialised memory, so a consumer that reads an unlisted row shows up in the results."""
+    poison = False
+
+    def __init__(self, rows, count, batch, n_tokens):
+        self.rows, self.count, self.batch, self.n_tokens = rows, count, batch, n_tokens
+        self.cap = batch * n_tokens
+
+    def _out(self, like, width):
+        shape = tuple(like.shape[:-1]) + (width,)
+        if LiveRows.poison:
+            return torch.full(shape, float("nan"), dtype=torch.float32, device=like.device)
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+    def _check(self, what, *tensors):
+        for t in tensors:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() // t.shape[-1] != self.cap:
+                raise MMXError("%s: fp32 contiguous tensors of %d rows expected, got %s %s" % (what, self.cap, t.dtype, tuple(t.shape)))
+
+
+def live_rows(eot, n_tokens):
+    """``eot [B]`` long -> ``LiveRows`` naming the rows ``b * n_tokens + p``, ``p <= eot[b]``, built on the device (``mmx_live_rows``:
+    no read-back; per-call tensors, so a hipGraph capture owns them).  ``None`` when option ``text_live_rows`` is 0."""
+    _dev(eot)
+    eot = eot.to(torch.long).contiguous()
+    B = eot.numel()
+    buf = torch.empty(B * n_tokens + 1, dtype=torch.int32, device=eot.device)
+    rc = lib().mmx_live_rows(_p(eot), B, n_tokens, _p(buf[1:]), _p(buf[:1]), _stream())
+    if rc == _lib.MMX_ENOTSUP:
+        return None
+    check(rc, "mmx_live_rows")
+    return LiveRows(buf[1:], buf[:1], B, n_tokens)
+
+
+def gemm_rows_eligible(*weights):
+    """The eligibility rule of ``mmx_gemm_rows_f32`` for ``x @ weight``: fp32 contiguous 2-D weights, both widths multiples of 4
+    (16-byte rows), 16-byte aligned storage."""
+    return all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0
+               and w.data_ptr() % 16 == 0 for w in weights)
+
+
+def gemm_rows(x, weight, live, out=None):
+    """``out[r] = x[r] @ weight`` for the live rows ``r`` (``mmx_gemm_rows_f32``, exact fp32 on the MFMA); every other row of ``out``
+    is left alone.  ``x [B, N, K]``, ``weight [K, M]`` (an ``nn.Linear`` weight as stored), ``out [B, N, M]``."""
+    _dev(x, weight, out)
+    K, M = weight.shape
+    if out is None:
+        out = live._out(x, M)
+    live._check("gemm_rows", x, out)
+    if x.shape[-1] != K or out.shape[-1] != M or not gemm_rows_eligible(weight):
+        raise MMXError("gemm_rows: x %s @ weight %s -> out %s" % (tuple(x.shape), tuple(weight.shape), tuple(out.shape)))
+    check(lib().mmx_gemm_rows_f32(_p(x), _p(weight), _p(out), _p(live.rows), _p(live.count), live.cap, M, K, _stream()),
+          "mmx_gemm_rows_f32")
+    return out
+
+
+def quick_gelu_bwd_rows(x, dy, live):
+    """``quick_gelu_bwd`` on the live rows (``x`` at the same row as ``dy``)."""
+    _dev(x, dy)
+    live._check("quick_gelu_bwd_rows", x, dy)
+    dx = live._out(dy, dy.shape[-1])
+    check(lib().mmx_quick_gelu_bwd_rows(_p(x), _p(dy), _p(dx), _p(live.rows), _p(live.count), live.cap, dy.shape[-1], _stream()),
+          "mmx_quick_gelu_bwd_rows")
+    return dx
+
+
+def layernorm_bwd_add_rows(dy, x, mean, rstd, gamma, d_res, live):
+    """``layernorm_bwd_add`` on the live rows (per-row ``x`` / ``mean`` / ``rstd``)."""
+    _dev(dy, x, mean, rstd, gamma, d_res)
+    live._check("layernorm_bwd_add_rows", dy, x, *([d_res] if d_res is not None else []))
+    mean, rstd = _f32c(mean), _f32c(rstd)
+    if mean.numel() != live.cap or rstd.numel() != live.cap:
+        raise MMXError("layernorm_bwd_add_rows: %d statistics for %d rows" % (mean.numel(), live.cap))
+    dx = live._out(dy, dy.shape[-1])
+    check(lib().mmx_layernorm_bwd_add_rows(_p(dy), _p(x), _p(mean), _p(rstd), _p(_f32c(gamma)), _p(d_res), _p(dx), _p(live.rows),
+                                           _p(live.count), live.cap, dy.shape[-1], _stream()), "mmx_layernorm_bwd_add_rows")
+    return dx
+
+
 def small_linear(x, lin):
     """``lin(x)`` for an ``nn.Linear`` applied to a FEW rows (a shared forward's 100 decoder queries) with a SQUARE weight of at
     most 256: the one shape family where the library's heuristic leaves the chip idle (a 256-row tile for 100 rows: 3
