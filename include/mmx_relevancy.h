@@ -103,6 +103,8 @@ const char* mmx_last_error(void);
  *                        16-row workgroups whose waves split the keys | 0 always the 64-row kernel
  *   "text_live_rows"     1 (default) mmx_live_rows builds the live-row list (the row-list backward of a causal tower: mmx_gemm_rows_f32
  *                        and the *_rows kernels) | 0: it declines with MMX_ENOTSUP and the caller runs the dense backward (A / B runs)
+ *   "text_live_rows_fwd" 1 (default) the forward of that tower runs on the live rows too (mmx_gemm_rows_bias_f32, mmx_add_layernorm_fwd_rows)
+ *                        | 0: dense forward, row-list backward (A / B runs); without "text_live_rows" it has no effect
  *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
  *   "debug_flags"        profiling only (phase skipping), 0 in production; one meaning per bit for every chain kernel the dispatcher
  *                        may pick: 1 return before the hand-off / combine | 4 matrix waves skip the MFMAs | 8 layer-group kernel:
@@ -234,6 +236,24 @@ int mmx_quick_gelu_bwd_rows(const void* x_dev, const void* dy_dev, void* dx_dev,
 int mmx_layernorm_bwd_add_rows(const void* dy_dev, const void* x_dev, const void* mean_dev, const void* rstd_dev,
                                const void* gamma_dev, const void* d_res_dev, void* dx_dev, const void* rows_dev,
                                const void* count_dev, int cap_rows, int E, void* stream);
+/* The FORWARD of such a tower on the same list: row p of a caption depends on rows <= p of that caption only, and the feature, every
+ * gradient and both maps depend on rows p <= eot[b] only, so the row-wise steps of the forward run on the listed rows too.
+ *   mmx_gemm_rows_bias_f32      C[r] = A[r] . Wt + bias for the listed rows r: a forward nn.Linear.  Wt: [K, N] = the weight TRANSPOSED
+ *                               ([in, out]; the caller caches that copy, weights do not change between calls), bias: [N].  The product
+ *                               is mmx_gemm_rows_f32's (same tiles, same eligibility, option "gemm_rows_tm"); the bias is added to the
+ *                               finished sum.  act_dev != NULL ([cap_rows, N], not C): QuickGELU of C's listed rows is stored there as
+ *                               well, with the bits mmx_quick_gelu_fwd gives on C (c_fc: C is the pre-activation the backward keeps).
+ *                               Unlisted rows of C and act are neither read nor written.
+ *   mmx_add_layernorm_fwd_rows  mmx_add_layernorm_fwd (fp32 h) on the listed rows: sum, h, mean and rstd of unlisted rows are left alone;
+ *                               listed rows get the bits the dense kernel gives.
+ *   mmx_text_live_rows_fwd_enabled  1 iff options "text_live_rows" and "text_live_rows_fwd" (default 1 | 0: dense forward, row-list
+ *                               backward, for A / B runs) are both on. */
+int mmx_gemm_rows_bias_f32(const void* a_dev, const void* wt_dev, const void* bias_dev, void* c_dev, void* act_dev,
+                           const void* rows_dev, const void* count_dev, int cap_rows, int N, int K, void* stream);
+int mmx_add_layernorm_fwd_rows(const void* x_dev, const void* y_dev, const void* gamma_dev, const void* beta_dev,
+                               void* sum_dev, void* h_dev, void* mean_dev, void* rstd_dev, const void* rows_dev,
+                               const void* count_dev, int cap_rows, int E, float eps, void* stream);
+int mmx_text_live_rows_fwd_enabled(void);
 
 /* The chain on VECTORS (rows-only DETR rules): when a caller returns single rows of R_q_i (`aggregated[:, target_index, :]`,
  * DETR/modules/ExplanationGenerator.py:180-182) the encoder product R_ii = (I + A_6) ... (I + A_1) (`:110-118`) is needed only

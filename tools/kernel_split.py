@@ -4,7 +4,7 @@
 
 Families: library GEMMs (rocBLAS / hipBLASLt ``Cijk_*``), our attention-capture kernels, our chain kernels, our fused
 elementwise kernels (QuickGELU, LayerNorm forward / backward), our row-list GEMM (``gemm_rows_f32_kernel``: the text tower's
-backward on its live rows), ATen LayerNorm, ATen elementwise / copies / reductions.
+forward and backward on its live rows), ATen LayerNorm, ATen elementwise / copies / reductions.
 The trace should be taken with ``bench.py --headline-only`` so that it holds headline steps (plus the two graph warm-ups).
 """
 import json

@@ -69,8 +69,14 @@ def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, 
     The text tower's backward runs on the rows up to each caption's EOT token only (on by default; ``clip_model.Transformer.
     _live_rows_route``): the mask is causal and the feature is read at the EOT token, so every gradient row past it is an exact zero.
     Unlike ``trim_text_padding`` this is decided on the device per call -- no read of the ids, shapes / slabs / accessors unchanged, a
-    captured graph follows whatever captions it is replayed with -- and it leaves the forward dense.  ``ops.set_option(
-    "text_live_rows", 0)`` switches it off process-wide.  Price: captions at the
+    captured graph follows whatever captions it is replayed with.  The text tower's FORWARD runs on the same rows (``clip_model.
+    Transformer.forward_tape(live=...)``; ``ops.set_option("text_live_rows_fwd", 0)`` keeps it dense): the rows past EOT feed neither
+    the feature nor any gradient.  The slabs then hold what the maps need (a filler in the probabilities' padded rows, zeros in the
+    gradients' masked entries past EOT) until ``blk.attn_probs`` / ``blk.attn_grad`` is read, which completes them with one dense pass
+    (``Transformer.complete_attn_probs``; figures: ``profiles/text_forward_live_rows_probe.txt``).  Cost of that first read: the
+    whole dense text forward and the text backward once more (about the text tower's share of a step of the dense path); later reads
+    are free until the next call, and a caller that only wants the maps never pays it.
+    ``ops.set_option("text_live_rows", 0)`` switches both off process-wide.  Price: captions at the
     truncation limit (77 tokens) have no dead rows and the row-list GEMM then does the library GEMM's work (figures, once measured:
     ``profiles/text_backward_live_rows_probe.txt``); the switch is the answer for such inputs.
 
@@ -181,6 +187,17 @@ class GraphedInterpret:
         # and a following eager call see what the replay wrote.
         vis, txt = model.visual.transformer, model.transformer
         self._pinned = (vis.buffers, txt.buffers)
+        # a captured row-list text forward leaves the slabs pending after every replay (clip_model.Transformer.complete_attn_probs):
+        # the captured block input, rows and upstream gradient rows -- they hold the last replay's values --, re-armed by __call__
+        self._txt_pending = txt.__dict__.get("_probs_pending")
+        txt._probs_pending = None              # (nothing has run yet: the capture recorded the kernels, the warm-up slabs are gone)
+        if self._txt_pending is not None:
+            # the row-list forward reads the cached TRANSPOSED copies of the text tower's weights, and the graph has their addresses:
+            # keep them alive (an in-place weight update makes a later eager call replace the cache entries).  The replays go on
+            # reading these copies -- weights changed after the capture need a new GraphedInterpret to be seen
+            self._pinned_weights = [
+                ops.transposed_weight(w) for blk in txt.resblocks
+                for w in (blk.attn.in_proj_weight, blk.attn.out_proj.weight, blk.mlp.c_fc.weight, blk.mlp.c_proj.weight)]
         self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
 
     def _reinstall(self):
@@ -199,6 +216,8 @@ class GraphedInterpret:
                 raise ValueError("caption longer than the %d positions this graph was captured for" % self.n_text)
             self.texts.copy_(texts)
         self.graph.replay()
+        if self._txt_pending is not None:
+            self.model.transformer._probs_pending = self._txt_pending
         return self.outputs
 
 

@@ -67,7 +67,12 @@ class CapturedSelfAttention(nn.Module):
 
 
 class ResidualAttentionBlock(nn.Module):
-    """Pre-LN block (CLIP/clip/model.py:167-198).  ``attn_probs`` / ``attn_grad`` are slab views."""
+    """Pre-LN block (CLIP/clip/model.py:167-198).  ``attn_probs`` / ``attn_grad`` are slab views.
+
+    Both are properties: after a row-list forward of the tower (``Transformer.forward_tape(live=...)``) the slabs hold what the maps
+    need -- the probabilities of the live rows, the gradients of the entries at and below the diagonal -- and the first read of any
+    block's ``attn_probs`` / ``attn_grad`` completes them (``Transformer.complete_attn_probs``).  Assigning to them
+    (``set_attn_probs`` / ``set_attn_grad``, a forward) works as before."""
 
     def __init__(self, d_model, n_head, attn_mask=None):
         super().__init__()
@@ -82,6 +87,28 @@ class ResidualAttentionBlock(nn.Module):
         self.attn_mask = attn_mask
         self.attn_probs = None
         self.attn_grad = None
+
+    def _slab_view(self, name):
+        owner = self.__dict__.get("_probs_owner")
+        if owner is not None:
+            owner[0].complete_attn_probs()             # (returns at once unless a row-list forward left the slabs pending)
+        return self.__dict__.get(name)
+
+    @property
+    def attn_probs(self):
+        return self._slab_view("_attn_probs")
+
+    @attn_probs.setter
+    def attn_probs(self, value):
+        self.__dict__["_attn_probs"] = value
+
+    @property
+    def attn_grad(self):
+        return self._slab_view("_attn_grad")
+
+    @attn_grad.setter
+    def attn_grad(self, value):
+        self.__dict__["_attn_grad"] = value
 
     # kept for API parity with the reference block (model.py:184-188)
     def set_attn_probs(self, attn_probs):
@@ -126,6 +153,9 @@ class Transformer(nn.Module):
         # capture slabs follow ``set_body_dtype`` (image towers: the slabs are the resident bytes of a long sequence);
         # the 77-token text tower keeps fp32 slabs and its register-resident exact-fp32 attention kernels
         self._long_sequence_slabs_follow_body = attn_mask is None
+        # what a row-list forward (and the backward on its tape) leave behind for complete_attn_probs: the block input, the slabs, the
+        # rows and the upstream gradient rows -- until the slabs have been completed or another forward has rewritten them
+        self._probs_pending = None
 
     def set_body_dtype(self, dtype):
         """``torch.bfloat16``: everything the reference's half-precision body would run in half precision (all GEMMs, the
@@ -200,6 +230,63 @@ class Transformer(nn.Module):
             self.__dict__["_causal_mask_check"] = cached = (key, ok)
         return cached[1]
 
+    def _row_gemm_weights_ok(self):
+        for blk in self.resblocks:
+            if not ops.gemm_rows_eligible(blk.mlp.c_proj.weight, blk.mlp.c_fc.weight, blk.attn.out_proj.weight, blk.attn.in_proj_weight):
+                return False
+        return True
+
+    def live_rows_for_forward(self, x, out_rows):
+        """The row-list FORWARD (``forward_tape(live=...)``): under a causal mask row p of a sample depends on rows ``<= p`` of that
+        sample only, and the caller reads row ``out_rows[b]``, so the rows past it feed nothing -- not the feature, and (the backward
+        being confined to the same rows, ``_live_rows_route``) no gradient either.  Same conditions as the backward's route: fp32
+        tape, causal tower, eligible weights, ``E % 4 == 0``; plus biases on every Linear and options ``text_live_rows`` /
+        ``text_live_rows_fwd``.  Returns the ``ops.LiveRows`` of ``out_rows`` or ``None`` (dense forward)."""
+        if out_rows is None or x.dim() != 3 or x.dtype != torch.float32 or x.shape[-1] % 4 or not x.is_cuda:
+            return None
+        for what in ("forward_gemm_dtype", "backward_gemm_dtype", "capture_dtype"):
+            if getattr(self, what, torch.float32) != torch.float32:
+                return None
+        if self.layers < 1 or not ops.live_rows_forward_enabled() or not self.is_causal() or not self._row_gemm_weights_ok():
+            return None
+        if x.shape[1] < self.resblocks[0].attn_mask.shape[-1]:
+            # a trimmed text batch (``trim_text_padding``: the first max(eot) + 1 positions only) keeps the dense forward: most of its
+            # rows are live, and on them the library GEMM beats the row-list kernel (measured, ViT-B/32, 64 captions: 7.65 ms per
+            # step against 8.96 with the route; profiles/text_forward_live_rows_probe.txt).  Its backward takes the route as before
+            return None
+        for blk in self.resblocks:
+            for bias in (blk.attn.in_proj_bias, blk.attn.out_proj.bias, blk.mlp.c_fc.bias, blk.mlp.c_proj.bias):
+                if bias is None or bias.dtype != torch.float32:
+                    return None
+        return ops.live_rows(out_rows, x.shape[1])
+
+    @torch.no_grad()
+    def complete_attn_probs(self):
+        """After a row-list forward the capture slabs hold what the maps need and no more: the probabilities of the live rows (a filler
+        in the others: the softmax of zero scores), and gradients that are right at and below the diagonal only -- ``dP[i, j] = dO[i] .
+        V[j]`` of a masked entry ``j > eot >= i`` wants the value row of a padded position, which that forward never formed (the chain
+        multiplies it with ``P[i, j] = 0``).  This runs the dense forward of the whole stack from the kept block input into the SAME
+        slabs and, if the backward has run, the backward again on that tape -- no new slabs, current stream -- so that ``blk.attn_probs``
+        and ``blk.attn_grad`` show every entry as a dense forward gives it (the live entries then carry the dense path's roundings).
+        Called by the first read of any block's ``attn_probs`` / ``attn_grad``; a no-op when nothing is pending.  Raw ``buffers.probs[l]``
+        / ``buffers.grads[l]`` are not accessors and stay as the route left them until then."""
+        pending = self.__dict__.get("_probs_pending")
+        if pending is None:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MMXError("attn_probs / attn_grad: the slabs of a row-list forward cannot be completed inside a stream capture "
+                                "(read them outside it, or set option text_live_rows_fwd to 0)")
+        self._probs_pending = None
+        keep, self.buffers = self.buffers, pending["buffers"]
+        try:
+            _, tape = self.forward_tape(pending["x"], first_grad_layer=pending["first_grad_layer"],
+                                        grads=pending["buffers"].grads is not None, out_rows=pending["out_rows"])
+            if pending["dy_row_values"] is not None:
+                self.backward_tape(tape, None, pending["backward_first_grad_layer"], dy_rows=pending["out_rows"],
+                                   dy_row_values=pending["dy_row_values"])
+        finally:
+            self.buffers = keep
+
     def _live_rows_route(self, tape, B, N, E, first_grad_layer, dy_rows, dy_row_values, rel_row, grouped):
         """The row-list backward (``ops.live_rows``): an fp32 tape of a causally masked tower whose upstream gradient is one row per
         sample.  Gradient enters at row ``dy_rows[b]`` and causal attention hands it to keys ``j <= i`` only, so every gradient row
@@ -211,15 +298,12 @@ class Transformer(nn.Module):
             return None
         if getattr(self, "backward_gemm_dtype", torch.float32) != torch.float32 or dy_row_values.dtype != torch.float32:
             return None
-        if tape[top][0].shape[0] != B or E % 4 or not self.is_causal():
+        if tape[top][0].shape[0] != B or E % 4 or not self.is_causal() or not self._row_gemm_weights_ok():
             return None
-        for blk in self.resblocks:
-            if not ops.gemm_rows_eligible(blk.mlp.c_proj.weight, blk.mlp.c_fc.weight, blk.attn.out_proj.weight, blk.attn.in_proj_weight):
-                return None
         return ops.live_rows(dy_rows, N)
 
     @torch.no_grad()
-    def forward_tape(self, x, batch=None, first_grad_layer=0, grads=True, out_rows=None):
+    def forward_tape(self, x, batch=None, first_grad_layer=0, grads=True, out_rows=None, live=None):
         """``x``: ``[Bx, N, E]`` block input (embedded, through ``ln_pre`` for the image tower).  ``batch``: how many
         upstream gradients ``backward_tape`` will carry (default ``Bx``; ``Bx == 1 < batch`` = shared-forward mode).
         Returns ``(y [Bx, N, E], tape)``; the probabilities of every block are in the capture slabs afterwards.
@@ -228,7 +312,16 @@ class Transformer(nn.Module):
         ``out_rows`` (``[Bx]`` long): the caller reads ONE token per sample from the tower output (class token / EOT token:
         CLIP/clip/model.py:235, 360).  Everything after the attention of the top block is row-wise, so ``out_proj``, ``ln_2``
         and the MLP of that block run on those Bx rows only (3 of its 4 GEMMs); ``y`` is then ``[Bx, E]`` -- those rows -- and
-        ``backward_tape`` must be given the same rows as ``dy_rows``."""
+        ``backward_tape`` must be given the same rows as ``dy_rows``.
+
+        ``live`` (``live_rows_for_forward(x, out_rows)``, a causally masked fp32 tower): the row-list forward.  Every row-wise step
+        (LayerNorms, the four GEMMs with their bias, QuickGELU) runs on the rows up to ``out_rows[b]`` only; the other rows of the
+        intermediates and of the tape are NOT written.  The attention stays dense: it reads a ``qkv`` whose unlisted rows are zeros
+        and writes ``P`` and ``O`` for all rows -- live queries see live keys only (causal mask), so their rows are exact; the dead
+        rows of ``P`` hold the softmax of zero scores, finite, which is all the backward and the chain need (their gradient rows are
+        exact zeros).  The gradient slab is then right where ``P`` is not masked (what the chain reads); its masked entries
+        ``dO[i] . V[j]``, ``j`` past the last live row, come out as zeros.  ``backward_tape`` must be given the same ``live``;
+        ``blk.attn_probs`` / ``blk.attn_grad`` complete both slabs on their first read (``complete_attn_probs``)."""
         if not x.is_cuda:
             raise _lib.MMXError("the CLIP body runs its attention on the HIP capture op: move the model and "
                                 "inputs to the MI355X (there is no CPU attention path)")
@@ -241,6 +334,20 @@ class Transformer(nn.Module):
         blocks = list(self.resblocks)
         mask = self._mask_for(blocks[0], N, x.device) if blocks else None
         tape = []
+        self._probs_pending = None
+        if live is not None:
+            if out_rows is None or shared or live.cap != Bx * N:
+                raise ValueError("forward_tape: the row-list forward needs out_rows, one input per gradient and a list over %d rows"
+                                 % (Bx * N))
+            self._probs_pending = {"x": x, "buffers": buffers, "live": live, "out_rows": out_rows, "first_grad_layer": first_grad_layer,
+                                   "dy_row_values": None, "backward_first_grad_layer": None}
+            for blk in blocks:
+                blk.__dict__["_probs_owner"] = (self,)
+
+        def ln(res, y, norm):                 # s = res + y, LayerNorm(s) and its statistics: dense, or on the listed rows
+            if live is not None:
+                return ops.add_layernorm_rows(res, y, norm.weight, norm.bias, norm.eps, live)
+            return ops.add_layernorm(res, y, norm.weight, norm.bias, norm.eps, h_dtype=hd)
         # bf16 matrix cores for the attention products: the long-sequence streaming kernels only (the register-resident
         # head kernels of a short tower such as CLIP's 77-token text side stay exact fp32)
         mma = bool(getattr(self, "attention_mma_bf16", False)) and N > 128
@@ -248,10 +355,16 @@ class Transformer(nn.Module):
         first = blocks[0].ln_1
         # bf16 body: what only feeds a GEMM (LayerNorm outputs, the MLP activation) leaves its kernel as bf16 -- no conversion passes
         hd = torch.bfloat16 if getattr(self, "forward_gemm_dtype", torch.float32) == torch.bfloat16 else torch.float32
-        _, h1, mean1, rstd1 = ops.add_layernorm(x, None, first.weight, first.bias, first.eps, h_dtype=hd)
+        _, h1, mean1, rstd1 = ln(x, None, first)
         for l, blk in enumerate(blocks):
             at = blk.attn
-            qkv = self._linear(h1, at.in_proj_weight, at.in_proj_bias).view(Bx, N, 3, at.num_heads, at.head_dim)
+            if live is not None:
+                # (zeros, not LiveRows._out: the dense attention reads every row of qkv)
+                qkv = ops.linear_rows(h1, at.in_proj_weight, at.in_proj_bias, live,
+                                      out=torch.zeros(Bx, N, 3 * E, dtype=torch.float32, device=x.device))
+            else:
+                qkv = self._linear(h1, at.in_proj_weight, at.in_proj_bias)
+            qkv = qkv.view(Bx, N, 3, at.num_heads, at.head_dim)
             o = ops.attn_capture_fwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buffers.probs[l], at.head_dim ** -0.5,
                                      _lib.SCALE_Q_FIRST, mask, layout="bnhd", mma_bf16=mma)
             if out_rows is not None and l + 1 == len(blocks):
@@ -265,15 +378,18 @@ class Transformer(nn.Module):
                 tape.append((x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o, out_rows) if l >= first_grad_layer else None)
                 blk.attn_probs, blk.attn_grad = buffers.layer_probs(l), buffers.layer_grads(l)
                 return x1 + mlp_out, tape
-            x1, h2, mean2, rstd2 = ops.add_layernorm(x, self._linear(o.view(Bx, N, E), at.out_proj.weight, at.out_proj.bias),
-                                                     blk.ln_2.weight, blk.ln_2.bias, blk.ln_2.eps, h_dtype=hd)
-            m = self._linear(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias)
-            mlp_out = self._linear(ops.quick_gelu_fwd(m, hd), blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
+            if live is not None:
+                x1, h2, mean2, rstd2 = ln(x, ops.linear_rows(o.view(Bx, N, E), at.out_proj.weight, at.out_proj.bias, live), blk.ln_2)
+                m, act = ops.linear_rows(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, live, gelu=True)
+                mlp_out = ops.linear_rows(act, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, live)
+            else:
+                x1, h2, mean2, rstd2 = ln(x, self._linear(o.view(Bx, N, E), at.out_proj.weight, at.out_proj.bias), blk.ln_2)
+                m = self._linear(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias)
+                mlp_out = self._linear(ops.quick_gelu_fwd(m, hd), blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
             tape.append((x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o) if l >= first_grad_layer else None)
             blk.attn_probs, blk.attn_grad = buffers.layer_probs(l), buffers.layer_grads(l)
             if l + 1 < len(blocks):
-                nxt = blocks[l + 1].ln_1
-                x, h1, mean1, rstd1 = ops.add_layernorm(x1, mlp_out, nxt.weight, nxt.bias, nxt.eps, h_dtype=hd)
+                x, h1, mean1, rstd1 = ln(x1, mlp_out, blocks[l + 1].ln_1)
             else:
                 x = x1 + mlp_out
         return x, tape
@@ -331,7 +447,8 @@ class Transformer(nn.Module):
         return self.forward_tape(x, batch)
 
     @torch.no_grad()
-    def backward_tape(self, tape, dy, first_grad_layer=0, dy_rows=None, rel_row=None, dy_row_values=None, targets_per_image=1):
+    def backward_tape(self, tape, dy, first_grad_layer=0, dy_rows=None, rel_row=None, dy_row_values=None, targets_per_image=1,
+                      live=None):
         """``dy``: ``[B, N, E]`` upstream gradients w.r.t. the tower output; fills ``buffers.grads`` of every block
         ``>= first_grad_layer``.
 
@@ -351,6 +468,8 @@ class Transformer(nn.Module):
         With ``dy_rows`` / ``dy_row_values`` on the fp32 tape of a CAUSALLY masked tower (CLIP's text tower) everything below the top
         block runs on the rows up to ``dy_rows[b]`` only (``_live_rows_route``): the rest of every gradient tensor is exact zeros.
         The attention backward still sees a dense ``d_o`` (zeros in the dead rows) and writes the whole gradient slab.
+        ``live``: the list a row-list forward ran on (``forward_tape(live=...)``); it is used again instead of building a second one,
+        and it is required then -- such a tape holds the listed rows only.
 
         ``targets_per_image=K`` (fp32 body, row mode only): the tape holds M distinct samples and the B = K*M upstream gradients
         are K per sample in K-major order (target t explains sample t % M).  The elementwise steps broadcast the per-sample
@@ -383,7 +502,15 @@ class Transformer(nn.Module):
             raise ValueError("backward_tape: targets_per_image=%d needs an fp32 body in the row mode and a multiple of it "
                              "upstream gradients (got %d)" % (int(targets_per_image), B))
         dx_h = None
-        live = self._live_rows_route(tape, B, N, E, first_grad_layer, dy_rows, dy_row_values, rel_row, grouped)
+        if live is None:
+            live = self._live_rows_route(tape, B, N, E, first_grad_layer, dy_rows, dy_row_values, rel_row, grouped)
+        elif dy_rows is None or dy_row_values is None or rel_row is not None or grouped or live.cap != B * N:
+            raise ValueError("backward_tape: the tape of a row-list forward needs the row-list backward (dy_rows and dy_row_values, "
+                             "no rel_row, one target per sample)")
+        else:
+            pending = self.__dict__.get("_probs_pending")
+            if pending is not None and pending["live"] is live:           # what complete_attn_probs needs to run this backward again
+                pending["dy_row_values"], pending["backward_first_grad_layer"] = dy_row_values, first_grad_layer
         d_o_dense = None      # live-row route: the top block's dense d_o (zeros outside the EOT rows); every block below rewrites its
                               # live rows only, so the dead rows the attention backward reads stay zero without another pass
         for l in range(top, first_grad_layer - 1, -1):
@@ -492,6 +619,7 @@ class Transformer(nn.Module):
             raise _lib.MMXError("the CLIP body runs its attention on the HIP capture op: move the model and "
                                 "inputs to the MI355X (there is no CPU attention path)")
         buffers = self._ensure_buffers(x.shape[0], x.shape[1], x.device)
+        self._probs_pending = None            # this (dense) forward writes every row of the slabs
         if not capture_only:
             for l, blk in enumerate(self.resblocks):
                 x = blk(x, buffers, l)
@@ -677,9 +805,12 @@ class CLIP(nn.Module):
         n = text.shape[1]
         x = self.token_embedding(text).type(self.dtype) + self.positional_embedding[:n].type(self.dtype)
         eot = text.argmax(dim=-1)                                            # model.py:360
-        rows, tape = self.transformer.forward_tape(x, first_grad_layer=first_grad_layer, out_rows=eot)
+        # the rows up to each EOT token, picked on the device: the forward runs on them where the tower is eligible, and the state
+        # hands the same list to the backward (None: dense forward; the backward then decides for itself, _live_rows_route)
+        live = self.transformer.live_rows_for_forward(x, eot)
+        rows, tape = self.transformer.forward_tape(x, first_grad_layer=first_grad_layer, out_rows=eot, live=live)
         _, f, mean, rstd = ops.add_layernorm(rows, None, self.ln_final.weight, self.ln_final.bias, self.ln_final.eps)
-        return f @ self.text_projection, (tape, x.shape, rows, mean, rstd, eot)
+        return f @ self.text_projection, (tape, x.shape, rows, mean, rstd, eot, live)
 
     @torch.no_grad()
     def encode_text_nocapture(self, text):
@@ -693,10 +824,11 @@ class CLIP(nn.Module):
     def backward_text_tape(self, state, d_features, first_grad_layer=0):
         """``d_features [B, embed_dim]`` -> fills the text tower's gradient slabs (``ln_final`` is row-wise, so only the
         EOT rows carry a gradient into the stack)."""
-        tape, y_shape, rows, mean, rstd, eot = state
+        tape, y_shape, rows, mean, rstd, eot, live = state
         d_f = torch.matmul(d_features, self.text_projection.t())
         d_rows = ops.layernorm_bwd_add(d_f, rows, mean, rstd, self.ln_final.weight)
-        self.transformer.backward_tape(tape, None, first_grad_layer, dy_rows=eot, dy_row_values=d_rows)
+        self.transformer.backward_tape(tape, None, first_grad_layer, dy_rows=eot, dy_row_values=d_rows,
+                                       live=live)
 
     def forward(self, image, text):
         return self.logits(self.encode_image(image), self.encode_text(text))

@@ -15,19 +15,16 @@ __device__ __forceinline__ unsigned bf_pack(float a, float b) {        // round 
     return __builtin_bit_cast(unsigned, r);
 }
 
-
-__device__ __forceinline__ float sigmoid_f(float z) { return 1.f / (1.f + expf(-z)); }
-
 __global__ __launch_bounds__(256) void quick_gelu_fwd_kernel(const f32x4* __restrict__ x, f32x4* __restrict__ y, int64_t n4,
                                                              const float* xt, float* yt, int tail) {
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<int64_t>(gridDim.x) * 256) {
         const f32x4 v = x[i];
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = v[e] * sigmoid_f(1.702f * v[e]);
+        for (int e = 0; e < 4; ++e) o[e] = quick_gelu_f(v[e]);
         y[i] = o;
     }
-    if (blockIdx.x == 0 && threadIdx.x < tail) yt[threadIdx.x] = xt[threadIdx.x] * sigmoid_f(1.702f * xt[threadIdx.x]);
+    if (blockIdx.x == 0 && threadIdx.x < tail) yt[threadIdx.x] = quick_gelu_f(xt[threadIdx.x]);
 }
 
 // the same with a bf16 result: the activation only feeds the next GEMM of a bf16 body (no conversion pass)
@@ -36,7 +33,7 @@ __global__ __launch_bounds__(256) void quick_gelu_fwd_bf16_kernel(const f32x4* _
         const f32x4 v = x[i];
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = v[e] * sigmoid_f(1.702f * v[e]);
+        for (int e = 0; e < 4; ++e) o[e] = quick_gelu_f(v[e]);
         y[i] = u32x2{bf_pack(o[0], o[1]), bf_pack(o[2], o[3])};
     }
 }
@@ -236,14 +233,22 @@ extern "C" int mmx_layernorm_bwd_add_rows(const void* dy_dev, const void* x_dev,
 // ---------------------------------------------------------------------------------------------------------------------
 namespace mmx {
 
-template <int NV>
+// ROWS: the row-list form (gemm_rows_f32.hip): wave j takes row list[j] of the *count listed ones, `rows` is the capacity; the
+// sum, h and the statistics of every other row are left alone.
+template <int NV, bool ROWS>
 __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                 float* __restrict__ sum_out, float* __restrict__ h_out,
                                                                 float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                                int64_t rows, int E, float eps, unsigned short* __restrict__ h_bf16) {
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+                                                                int64_t rows, int E, float eps, unsigned short* __restrict__ h_bf16,
+                                                                const int* __restrict__ list, const int* __restrict__ count) {
+    int64_t r = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
+    if constexpr (ROWS) {
+        if (r >= *count) return;
+        r = list[r];
+        if (r < 0 || r >= rows) return;                   // an id outside the tensor is no row at all
+    }
     const int lane = threadIdx.x & 63, n4 = E >> 2;
     const f32x4* xr = reinterpret_cast<const f32x4*>(x + r * E);
     const f32x4* yr = y ? reinterpret_cast<const f32x4*>(y + r * E) : nullptr;
@@ -310,12 +315,37 @@ extern "C" int mmx_add_layernorm_fwd_ex(const void* x_dev, const void* y_dev, co
     float *so = static_cast<float*>(sum_dev), *ho = h_dtype == MMX_F32 ? static_cast<float*>(h_dev) : nullptr;
     unsigned short* hb = h_dtype == MMX_BF16 ? static_cast<unsigned short*>(h_dev) : nullptr;
     float *mo = static_cast<float*>(mean_dev), *ro = static_cast<float*>(rstd_dev);
-    if (E <= 256) mmx::add_layernorm_fwd_kernel<1><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb);
-    else if (E <= 512) mmx::add_layernorm_fwd_kernel<2><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb);
-    else if (E <= 1024) mmx::add_layernorm_fwd_kernel<4><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb);
-    else if (E <= 2048) mmx::add_layernorm_fwd_kernel<8><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb);
-    else mmx::add_layernorm_fwd_kernel<16><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb);
+    if (E <= 256) mmx::add_layernorm_fwd_kernel<1, false><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb, nullptr, nullptr);
+    else if (E <= 512) mmx::add_layernorm_fwd_kernel<2, false><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb, nullptr, nullptr);
+    else if (E <= 1024) mmx::add_layernorm_fwd_kernel<4, false><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb, nullptr, nullptr);
+    else if (E <= 2048) mmx::add_layernorm_fwd_kernel<8, false><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb, nullptr, nullptr);
+    else mmx::add_layernorm_fwd_kernel<16, false><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, rows, E, eps, hb, nullptr, nullptr);
     MMX_LAUNCH_CHECK("add_layernorm_fwd_kernel");
+    return MMX_OK;
+}
+
+// Row-list form: x, y, sum, h are [cap_rows, E], mean / rstd [cap_rows], fp32; only the listed rows are touched (mmx_live_rows).
+extern "C" int mmx_add_layernorm_fwd_rows(const void* x_dev, const void* y_dev, const void* gamma_dev, const void* beta_dev,
+                                          void* sum_dev, void* h_dev, void* mean_dev, void* rstd_dev, const void* rows_dev,
+                                          const void* count_dev, int cap_rows, int E, float eps, void* stream) {
+    MMX_CHECK_ARG(x_dev && gamma_dev && beta_dev && h_dev && mean_dev && rstd_dev && rows_dev && count_dev,
+                  "mmx_add_layernorm_fwd_rows: null pointer");
+    MMX_CHECK_ARG(!y_dev || sum_dev, "mmx_add_layernorm_fwd_rows: the sum x + y needs an output buffer");
+    MMX_CHECK_ARG(cap_rows > 0 && E > 0 && E % 4 == 0 && E <= 4096, "mmx_add_layernorm_fwd_rows: cap_rows=%d E=%d (E %% 4 == 0, E <= 4096)",
+                  cap_rows, E);
+    const unsigned grid = static_cast<unsigned>((cap_rows + 3) / 4);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float *x = static_cast<const float*>(x_dev), *y = static_cast<const float*>(y_dev);
+    const float *g = static_cast<const float*>(gamma_dev), *b = static_cast<const float*>(beta_dev);
+    float *so = static_cast<float*>(sum_dev), *ho = static_cast<float*>(h_dev);
+    float *mo = static_cast<float*>(mean_dev), *ro = static_cast<float*>(rstd_dev);
+    const int *list = static_cast<const int*>(rows_dev), *count = static_cast<const int*>(count_dev);
+    if (E <= 256) mmx::add_layernorm_fwd_kernel<1, true><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, cap_rows, E, eps, nullptr, list, count);
+    else if (E <= 512) mmx::add_layernorm_fwd_kernel<2, true><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, cap_rows, E, eps, nullptr, list, count);
+    else if (E <= 1024) mmx::add_layernorm_fwd_kernel<4, true><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, cap_rows, E, eps, nullptr, list, count);
+    else if (E <= 2048) mmx::add_layernorm_fwd_kernel<8, true><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, cap_rows, E, eps, nullptr, list, count);
+    else mmx::add_layernorm_fwd_kernel<16, true><<<grid, 256, 0, s>>>(x, y, g, b, so, ho, mo, ro, cap_rows, E, eps, nullptr, list, count);
+    MMX_LAUNCH_CHECK("add_layernorm_fwd_kernel<rows>");
     return MMX_OK;
 }
 

@@ -21,8 +21,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static int g_text_live_rows = 1;   // option "text_live_rows": 1 (default) the row-list backward route is offered | 0: mmx_live_rows declines
 static int g_gemm_rows_tm = 32;    // option "gemm_rows_tm": rows per workgroup tile, 32 (default) or 64 (A / B runs)
+static int g_text_live_rows_fwd = 1;   // option "text_live_rows_fwd": 1 (default) the forward of that tower takes the route too | 0: dense forward
 bool text_live_rows_option(const char* key, int value) {
     if (strcmp(key, "text_live_rows") == 0 && value >= 0 && value <= 1) { g_text_live_rows = value; return true; }
+    if (strcmp(key, "text_live_rows_fwd") == 0 && value >= 0 && value <= 1) { g_text_live_rows_fwd = value; return true; }
     if (strcmp(key, "gemm_rows_tm") == 0 && (value == 32 || value == 64)) { g_gemm_rows_tm = value; return true; }
     return false;
 }
@@ -57,10 +59,15 @@ __global__ __launch_bounds__(256) void live_rows_kernel(const long long* __restr
 
 constexpr int kRowsBK = 16, kRowsTN = 64;
 
-template <int TM, int PF>
+// EPI: what happens to a finished row of the product on its way out.  0: stored as it is (the backward's input-gradient GEMMs) |
+// 1: + bias[n] (a forward nn.Linear, W then being the cached [in, out] copy of the weight) | 2: + bias[n], stored to C, and
+// QuickGELU of it stored to C2 (c_fc: the backward's tape wants the pre-activation, c_proj the activation; quick_gelu_f is the
+// device function of quick_gelu_fwd_kernel, so C2 has the bits ops.quick_gelu_fwd(C) would have).
+template <int TM, int PF, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ C, const int* __restrict__ rows,
-                                                               const int* __restrict__ count, int cap, int N, int K) {
+                                                               const int* __restrict__ count, int cap, int N, int K,
+                                                               const float* __restrict__ bias, float* __restrict__ C2) {
     constexpr int TN = kRowsTN, BK = kRowsBK;
     constexpr int WR = TM / 32;                      // wave rows (one 32 x 32 MFMA tile per wave)
     constexpr int WK = 2 / WR;                       // waves sharing an output tile, each on its own 8-wide k groups of a slab
@@ -154,11 +161,29 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
     }
     const int gn = n0 + wc * 32 + li;
     if (!on || gn >= N) return;
+    float bv = 0.f;
+    if constexpr (EPI != 0) bv = bias[gn];
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
         const int r = rid[wr * 32 + (v >> 2) * 8 + lg * 4 + (v & 3)];
-        if (r >= 0) C[static_cast<int64_t>(r) * N + gn] = acc[v];
+        if (r < 0) continue;
+        if constexpr (EPI == 0) {
+            C[static_cast<int64_t>(r) * N + gn] = acc[v];
+        } else {
+            const float m = acc[v] + bv;
+            C[static_cast<int64_t>(r) * N + gn] = m;
+            if constexpr (EPI == 2) C2[static_cast<int64_t>(r) * N + gn] = quick_gelu_f(m);
+        }
     }
+}
+
+template <int EPI>
+static void launch_gemm_rows(int tm, int64_t wgs, hipStream_t s, const float* A, const float* W, float* C, const int* rows,
+                             const int* count, int cap_rows, int N, int K, const float* bias, float* C2) {
+    if (tm == 32)
+        gemm_rows_f32_kernel<32, 3, EPI><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+    else
+        gemm_rows_f32_kernel<64, 3, EPI><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
 }
 
 }  // namespace mmx
@@ -190,13 +215,35 @@ extern "C" int mmx_gemm_rows_f32(const void* a_dev, const void* w_dev, void* c_d
     const int tm = g_gemm_rows_tm;
     const int64_t wgs = static_cast<int64_t>((N + kRowsTN - 1) / kRowsTN) * ((cap_rows + tm - 1) / tm);
     MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
-    const float *A = static_cast<const float*>(a_dev), *W = static_cast<const float*>(w_dev);
+    launch_gemm_rows<0>(tm, wgs, static_cast<hipStream_t>(stream), static_cast<const float*>(a_dev), static_cast<const float*>(w_dev),
+                        static_cast<float*>(c_dev), static_cast<const int*>(rows_dev), static_cast<const int*>(count_dev), cap_rows, N, K,
+                        nullptr, nullptr);
+    MMX_LAUNCH_CHECK("gemm_rows_f32_kernel");
+    return MMX_OK;
+}
+
+extern "C" int mmx_text_live_rows_fwd_enabled(void) { return g_text_live_rows && g_text_live_rows_fwd; }
+
+extern "C" int mmx_gemm_rows_bias_f32(const void* a_dev, const void* wt_dev, const void* bias_dev, void* c_dev, void* act_dev,
+                                      const void* rows_dev, const void* count_dev, int cap_rows, int N, int K, void* stream) {
+    MMX_CHECK_ARG(a_dev && wt_dev && bias_dev && c_dev && rows_dev && count_dev, "mmx_gemm_rows_bias_f32: null pointer");
+    MMX_CHECK_ARG(cap_rows > 0 && N > 0 && K > 0, "mmx_gemm_rows_bias_f32: cap_rows=%d N=%d K=%d", cap_rows, N, K);
+    MMX_CHECK_ARG(act_dev != c_dev, "mmx_gemm_rows_bias_f32: the activation needs a buffer of its own");
+    if (N % 4 || K % 4 ||
+        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(wt_dev) | reinterpret_cast<uintptr_t>(c_dev)) & 15u)) {
+        set_error("mmx_gemm_rows_bias_f32: N=%d and K=%d must be multiples of 4 and the operands 16-byte aligned", N, K);
+        return MMX_ENOTSUP;
+    }
+    const int tm = g_gemm_rows_tm;
+    const int64_t wgs = static_cast<int64_t>((N + kRowsTN - 1) / kRowsTN) * ((cap_rows + tm - 1) / tm);
+    MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_bias_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
+    const float *A = static_cast<const float*>(a_dev), *W = static_cast<const float*>(wt_dev), *bias = static_cast<const float*>(bias_dev);
     const int *rows = static_cast<const int*>(rows_dev), *count = static_cast<const int*>(count_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (tm == 32)
-        gemm_rows_f32_kernel<32, 3><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, static_cast<float*>(c_dev), rows, count, cap_rows, N, K);
+    if (act_dev)
+        launch_gemm_rows<2>(tm, wgs, s, A, W, static_cast<float*>(c_dev), rows, count, cap_rows, N, K, bias, static_cast<float*>(act_dev));
     else
-        gemm_rows_f32_kernel<64, 3><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, static_cast<float*>(c_dev), rows, count, cap_rows, N, K);
-    MMX_LAUNCH_CHECK("gemm_rows_f32_kernel");
+        launch_gemm_rows<1>(tm, wgs, s, A, W, static_cast<float*>(c_dev), rows, count, cap_rows, N, K, bias, nullptr);
+    MMX_LAUNCH_CHECK("gemm_rows_f32_kernel<bias>");
     return MMX_OK;
 }

@@ -148,6 +148,11 @@ __device__ __forceinline__ void slab_store(typename slab_elem<DT>::type* p, floa
 // clamp(x, min=0) with torch semantics: NaN propagates (fmaxf would drop it)
 __device__ __forceinline__ float relu_nan(float x) { return (x < 0.0f) ? 0.0f : x; }
 
+// QuickGELU, x * sigmoid(1.702 x) (CLIP/clip/model.py:162-164): ONE device function for every kernel that evaluates it (the fused
+// elementwise passes, the c_fc epilogue of the row-list GEMM), so that they agree bit for bit.
+__device__ __forceinline__ float sigmoid_f(float z) { return 1.f / (1.f + expf(-z)); }
+__device__ __forceinline__ float quick_gelu_f(float v) { return v * sigmoid_f(1.702f * v); }
+
 // exact-fp32 MFMA: D(16x16) += A(16x4) . B(4x16).
 // lane l: a = A[l & 15][l >> 4], b = B[l >> 4][l & 15]; acc[r] = D[(l >> 4) * 4 + r][l & 15].
 __device__ __forceinline__ f32x4 mfma16x16x4(float a, float b, f32x4 acc) {

@@ -682,6 +682,57 @@ def gemm_rows(x, weight, live, out=None):
     return out
 
 
+def live_rows_forward_enabled():
+    """Options ``text_live_rows`` and ``text_live_rows_fwd`` are both on: the forward of a causal tower may take the row list too."""
+    return bool(lib().mmx_text_live_rows_fwd_enabled())
+
+
+def linear_rows(x, weight, bias, live, out=None, gelu=False, act_out=None):
+    """``out[r] = x[r] @ weight.t() + bias`` for the live rows ``r`` (``mmx_gemm_rows_bias_f32``: a forward ``nn.Linear`` on the tiles of
+    ``gemm_rows``, fed with the cached ``transposed_weight``); every other row of ``out`` is left alone.  ``x [B, N, in]``, ``weight
+    [out, in]``.  ``gelu``: returns ``(out, act)`` with ``act = QuickGELU(out)`` on the live rows, written by the same kernel -- the bits
+    ``quick_gelu_fwd(out)`` has there (``act_out``: the tensor to write it to)."""
+    _dev(x, weight, bias, out, act_out)
+    M, K = weight.shape
+    if out is None:
+        out = live._out(x, M)
+    live._check("linear_rows", x, out)
+    if x.shape[-1] != K or out.shape[-1] != M or not gemm_rows_eligible(weight) or bias is None or bias.numel() != M:
+        raise MMXError("linear_rows: x %s @ weight %s^T + bias -> out %s" % (tuple(x.shape), tuple(weight.shape), tuple(out.shape)))
+    act = (act_out if act_out is not None else live._out(x, M)) if gelu else None
+    if act is not None:
+        live._check("linear_rows", act)
+        if act.shape[-1] != M or act.data_ptr() == out.data_ptr():
+            raise MMXError("linear_rows: the activation needs a [.., %d] tensor of its own" % M)
+    check(lib().mmx_gemm_rows_bias_f32(_p(x), _p(transposed_weight(weight)), _p(_f32c(bias.detach())), _p(out), _p(act), _p(live.rows),
+                                       _p(live.count), live.cap, M, K, _stream()), "mmx_gemm_rows_bias_f32")
+    return (out, act) if gelu else out
+
+
+def add_layernorm_rows(x, y, gamma, beta, eps, live, out=None):
+    """``add_layernorm`` on the live rows -> ``(s, h, mean, rstd)`` of the dense shapes; the rows outside the list are not written
+    (``y=None``: ``s`` is ``x`` itself).  Listed rows have the bits of the dense kernel.  ``out``: ``(s, h, mean, rstd)`` to write to."""
+    _dev(x, y, gamma, beta)
+    live._check("add_layernorm_rows", x, *([y] if y is not None else []))
+    E = x.shape[-1]
+    if out is not None:
+        s, h, mean, rstd = out
+        _dev(s, h, mean, rstd)
+        s = s if y is not None else x
+        live._check("add_layernorm_rows", h, *([s] if y is not None else []))
+        if h.shape[-1] != E or (y is not None and s.shape[-1] != E) or mean.numel() != live.cap or rstd.numel() != live.cap or \
+                not (mean.is_contiguous() and rstd.is_contiguous() and mean.dtype == rstd.dtype == torch.float32):
+            raise MMXError("add_layernorm_rows: out must be (s, h [.., %d], mean, rstd [%d]) fp32 contiguous" % (E, live.cap))
+    else:
+        s = live._out(x, E) if y is not None else x
+        h = live._out(x, E)
+        mean, rstd = live._out(x, 1).view(-1), live._out(x, 1).view(-1)
+    check(lib().mmx_add_layernorm_fwd_rows(_p(x), _p(y), _p(_f32c(gamma)), _p(_f32c(beta)), _p(s) if y is not None else _p(None), _p(h),
+                                           _p(mean), _p(rstd), _p(live.rows), _p(live.count), live.cap, E, float(eps), _stream()),
+          "mmx_add_layernorm_fwd_rows")
+    return s, h, mean, rstd
+
+
 def quick_gelu_bwd_rows(x, dy, live):
     """``quick_gelu_bwd`` on the live rows (``x`` at the same row as ``dy``)."""
     _dev(x, dy)
