@@ -106,6 +106,8 @@ const char* mmx_last_error(void);
  *   "text_live_rows_fwd" 1 (default) the forward of that tower runs on the live rows too (mmx_gemm_rows_bias_f32, mmx_add_layernorm_fwd_rows)
  *                        | 0: dense forward, row-list backward (A / B runs); without "text_live_rows" it has no effect
  *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
+ *   "gemm_rows_tn"       0 (default: chosen from N and K) | 32 | 64: columns per workgroup tile of mmx_gemm_rows_f32 at 32 rows (same
+ *                        products, another order of the k sum; 64-row tiles are always 64 wide)
  *   "debug_flags"        profiling only (phase skipping), 0 in production; one meaning per bit for every chain kernel the dispatcher
  *                        may pick: 1 return before the hand-off / combine | 4 matrix waves skip the MFMAs | 8 layer-group kernel:
  *                        ticket without combine | 16 column kernel: no block rotation

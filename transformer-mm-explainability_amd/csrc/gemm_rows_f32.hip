@@ -2,14 +2,16 @@
 // GEMMs of a causally masked tower's backward (CLIP's text tower, CLIP/clip/model.py:334-340, 360: the feature is read at the EOT
 // token, so every gradient row past it is an exact zero; 89 % of the rows at caption lengths), plus the kernel that builds the list.
 //
-// The product follows bmm_f32_tiles.hip (k-fastest A tile read with one ds_read_b128 per four MFMA steps, n-fastest B tile, 16-byte
-// global loads, two LDS stages with one barrier per 16-wide K slab and PF slabs requested ahead into registers).  What differs:
+// The product uses the tiles of bmm_f32_tiles.hip (k-fastest A tile read with one ds_read_b128 per four MFMA steps, n-fastest B tile, 16-byte
+// global loads, two LDS stages with one barrier per K slab and PF slabs requested ahead into registers); its K loop is its own (see the
+// kernel).  What differs:
 //   * M is a DEVICE-side count: the grid is sized for the capacity (every row of the dense tensor), a workgroup whose row tile starts
 //     at or beyond the count returns at once.  Nothing is read back, the launch is the same for every input (hipGraph replays it).
 //   * a thread's A row address goes through the list once, before the K loop; output rows are scattered back to the same dense
 //     layout, unlisted rows are neither read nor written.
-//   * few rows must still spread over the chip: TM = 32 rows x 64 columns per workgroup, the four waves as 2 column halves x 2 halves of
-//     every K slab (their accumulators meet in LDS at the end); TM = 64 is the 2 x 2 layout of bmm_f32_tiles.hip.
+//   * few rows must still spread over the chip: TM = 32 rows x 64 columns per workgroup, the four waves as 2 column halves x 2 shares of
+//     every K slab (their accumulators meet in LDS at the end, added in a fixed order); 32 x 32: four shares of one MFMA tile, twice the
+//     workgroups; TM = 64 is the 2 x 2 layout of bmm_f32_tiles.hip.
 //   * workgroups are NOT made XCD-contiguous: the live tiles are the first few of the capacity grid, and the plain round-robin spreads
 //     exactly those over the eight XCDs.
 // W is the nn.Linear parameter as stored ([out, in] = [K, N] row-major here), used as x @ weight like ops.backward_gemm.
@@ -21,11 +23,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static int g_text_live_rows = 1;   // option "text_live_rows": 1 (default) the row-list backward route is offered | 0: mmx_live_rows declines
 static int g_gemm_rows_tm = 32;    // option "gemm_rows_tm": rows per workgroup tile, 32 (default) or 64 (A / B runs)
+static int g_gemm_rows_tn = 0;     // option "gemm_rows_tn": columns per workgroup tile at 32 rows, 0 (default: from the shape) | 32 | 64 (A / B runs)
 static int g_text_live_rows_fwd = 1;   // option "text_live_rows_fwd": 1 (default) the forward of that tower takes the route too | 0: dense forward
 bool text_live_rows_option(const char* key, int value) {
     if (strcmp(key, "text_live_rows") == 0 && value >= 0 && value <= 1) { g_text_live_rows = value; return true; }
     if (strcmp(key, "text_live_rows_fwd") == 0 && value >= 0 && value <= 1) { g_text_live_rows_fwd = value; return true; }
     if (strcmp(key, "gemm_rows_tm") == 0 && (value == 32 || value == 64)) { g_gemm_rows_tm = value; return true; }
+    if (strcmp(key, "gemm_rows_tn") == 0 && (value == 0 || value == 32 || value == 64)) { g_gemm_rows_tn = value; return true; }
     return false;
 }
 
@@ -57,29 +61,39 @@ __global__ __launch_bounds__(256) void live_rows_kernel(const long long* __restr
     if (threadIdx.x == 0) *count = base;
 }
 
-constexpr int kRowsBK = 16, kRowsTN = 64;
-
 // EPI: what happens to a finished row of the product on its way out.  0: stored as it is (the backward's input-gradient GEMMs) |
 // 1: + bias[n] (a forward nn.Linear, W then being the cached [in, out] copy of the weight) | 2: + bias[n], stored to C, and
 // QuickGELU of it stored to C2 (c_fc: the backward's tape wants the pre-activation, c_proj the activation; quick_gelu_f is the
 // device function of quick_gelu_fwd_kernel, so C2 has the bits ops.quick_gelu_fwd(C) would have).
-template <int TM, int PF, int EPI>
+//
+// The K loop is a software pipeline without a predicate in its steady state:
+//   * global loads are issued unconditionally, PF slabs ahead, from an address clamped into the tensor (row 0 for a tile row
+//     that names no dense row, the last chunk / last row of K past the end); what must not count is replaced by zeros when the
+//     registers go to LDS.  No branch surrounds a load, so the wait in front of the ds_write is a counted vmcnt.
+//   * a wave holds the MFMA operands of the current slab in registers.  It issues the first half of the slab's MFMAs, passes the
+//     one barrier of the slab (the next slab is then complete in the other LDS stage), requests the next slab's operands and
+//     issues the second half of the MFMAs while those reads are under way.
+//   * the last slab is peeled out of the loop (nothing left to stash or to read ahead).
+template <int TM, int TN, int BK, int PF, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ C, const int* __restrict__ rows,
                                                                const int* __restrict__ count, int cap, int N, int K,
                                                                const float* __restrict__ bias, float* __restrict__ C2) {
-    constexpr int TN = kRowsTN, BK = kRowsBK;
-    constexpr int WR = TM / 32;                      // wave rows (one 32 x 32 MFMA tile per wave)
-    constexpr int WK = 2 / WR;                       // waves sharing an output tile, each on its own 8-wide k groups of a slab
-    constexpr int LA = BK + 4;                       // A stage: [TM][20] floats, k fastest
-    constexpr int LB = TN + 4;                       // B stage: [16][68] floats, n fastest
+    constexpr int WR = TM / 32, WC = TN / 32;        // wave rows x wave columns (one 32 x 32 MFMA tile per wave)
+    constexpr int WK = 4 / (WR * WC);                // waves sharing an output tile, each on its own 8-wide k groups of a slab
+    constexpr int NG = BK / 8 / WK;                  // k groups of a slab per wave: 4 MFMAs each, half of them on either side of the barrier
+    constexpr int LA = BK + 4;                       // A stage: [TM][BK + 4] floats, k fastest
+    constexpr int LB = TN + 4;                       // B stage: [BK][TN + 4] floats, n fastest
+    constexpr int CA = TM * BK / 1024, CB = BK * TN / 1024;   // 16-byte chunks of a slab per thread
+    constexpr int RA = 1024 / BK, RB = 1024 / TN;    // tile rows / k rows between two chunks of a thread
+    static_assert(WR * WC * WK == 4 && NG >= 2 && NG % 2 == 0 && CA >= 1 && CB >= 1 && PF >= 2, "tile shape");
     __shared__ __attribute__((aligned(16))) float As[2][TM * LA];
     __shared__ __attribute__((aligned(16))) float Bs[2][BK * LB];
-    __shared__ __attribute__((aligned(16))) float red[WK == 2 ? 2 * 16 * 64 : 4];
+    __shared__ __attribute__((aligned(16))) float red[WK > 1 ? (WK - 1) * WR * WC * 16 * 64 : 4];
     __shared__ int rid[TM];                          // dense row of every tile row, -1: none
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wc = wave & 1, wr = WR == 2 ? wave >> 1 : 0, wk = WR == 2 ? 0 : wave >> 1;
+    const int wc = wave % WC, wr = (wave / WC) % WR, wk = wave / (WC * WR);
     const int M = min(*count, cap);
     const int tiles_n = (N + TN - 1) / TN;
     const int bx = blockIdx.x % tiles_n, by = blockIdx.x / tiles_n;
@@ -96,71 +110,106 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
 
-    // per-thread chunk addresses, fixed for the whole K loop: one 16-byte chunk of the A slab (the first TM * 4 threads), one of B
-    const bool has_a = tid < TM * 4;
-    const int ar = tid >> 2, ka = (tid & 3) * 4;
-    const int arow = has_a ? dense_row(m0 + ar) : -1;
-    const bool oka = arow >= 0;
-    const float* pa = A + static_cast<int64_t>(oka ? arow : 0) * K + ka;
+    // per-thread chunk addresses, fixed for the whole K loop: CA 16-byte chunks of the A slab (tile rows ar + i RA), CB of the B slab
+    // (k rows kb + i RB of one column chunk)
+    const int ar = tid / (BK / 4), ka = (tid % (BK / 4)) * 4;
+    bool oka[CA];
+    const float* pa[CA];
+#pragma unroll
+    for (int i = 0; i < CA; ++i) {
+        const int arow = dense_row(m0 + ar + i * RA);
+        oka[i] = arow >= 0;
+        pa[i] = A + static_cast<int64_t>(oka[i] ? arow : 0) * K;
+    }
     const int kb = tid / (TN / 4), nbl = (tid % (TN / 4)) * 4;
     const bool okb = n0 + nbl < N;                   // N % 4 == 0: a chunk is inside or outside as a whole
-    const float* pb = W + static_cast<int64_t>(kb) * N + (okb ? n0 + nbl : 0);
-    f32x4 ra[PF], rb[PF];                            // slab t waits in register set t % PF
-    auto fetch = [&](int k0, f32x4& xa, f32x4& xb) {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        xa = (oka && k0 + ka < K) ? ldg4_u(pa + k0) : z;                            // K % 4 == 0
-        xb = (okb && k0 + kb < K) ? ldg4_u(pb + static_cast<int64_t>(k0) * N) : z;
+    const float* pb = W + (okb ? n0 + nbl : 0);
+    struct Slab { f32x4 a[CA], b[CB]; };
+    Slab ring[PF];                                   // slab t waits in register set t % PF
+    auto fetch = [&](int t, Slab& x) {               // any t: an address past K is clamped to the last chunk (K % 4 == 0) / last row
+        const int k0 = t * BK;
+#pragma unroll
+        for (int i = 0; i < CA; ++i) x.a[i] = ldg4_u(pa[i] + min(k0 + ka, K - 4));
+#pragma unroll
+        for (int i = 0; i < CB; ++i) x.b[i] = ldg4_u(pb + static_cast<int64_t>(min(k0 + kb + i * RB, K - 1)) * N);
     };
-    auto stash = [&](int stage, const f32x4& xa, const f32x4& xb) {
-        if (has_a) *reinterpret_cast<f32x4*>(&As[stage][ar * LA + ka]) = xa;
-        *reinterpret_cast<f32x4*>(&Bs[stage][kb * LB + nbl]) = xb;
+    auto stash = [&](int stage, int t, const Slab& x) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const int k0 = t * BK;
+#pragma unroll
+        for (int i = 0; i < CA; ++i)
+            *reinterpret_cast<f32x4*>(&As[stage][(ar + i * RA) * LA + ka]) = (oka[i] && k0 + ka < K) ? x.a[i] : z;
+#pragma unroll
+        for (int i = 0; i < CB; ++i)
+            *reinterpret_cast<f32x4*>(&Bs[stage][(kb + i * RB) * LB + nbl]) = (okb && k0 + kb + i * RB < K) ? x.b[i] : z;
     };
 
+    // MFMA operands of one slab: step t of the wave's g-th k group (group jj = wk + g WK of the slab) takes k = 8 jj + 4 (lane >> 5) + t
     const int li = lane & 31, lg = lane >> 5;
-    const bool on = __builtin_amdgcn_readfirstlane(m0 + wr * 32) < M && __builtin_amdgcn_readfirstlane(n0 + wc * 32) < N;
-    const int nslab = (K + BK - 1) / BK;
-    fetch(0, ra[0], rb[0]);
-    stash(0, ra[0], rb[0]);
+    struct Frag { f32x4 a[NG]; float b[NG][4]; };
+    auto read_frag = [&](Frag& f, int stage) {
+        const float* Asl = &As[stage][(wr * 32 + li) * LA + 4 * lg];
+        const float* Bsl = &Bs[stage][(4 * lg) * LB + wc * 32 + li];
 #pragma unroll
-    for (int j = 1; j <= PF; ++j)                    // slabs 1 .. PF in flight (set 0 is free again)
-        if (j < nslab) fetch(j * BK, ra[j % PF], rb[j % PF]);
-    lds_barrier();
-    for (int s0 = 0; s0 < nslab; s0 += PF) {
+        for (int g = 0; g < NG; ++g) {
+            const int jj = wk + g * WK;
+            f.a[g] = *reinterpret_cast<const f32x4*>(Asl + 8 * jj);
 #pragma unroll
-        for (int j = 0; j < PF; ++j) {
-            const int s = s0 + j;
-            if (s >= nslab) break;
-            const int stage = s & 1;
-            if (s + 1 < nslab) {
-                // every wave left stage ^ 1 at the barrier that ended slab s - 1 (bmm_f32_tiles.hip)
-                stash(stage ^ 1, ra[(j + 1) % PF], rb[(j + 1) % PF]);
-                if (s + 1 + PF < nslab) fetch((s + 1 + PF) * BK, ra[(j + 1) % PF], rb[(j + 1) % PF]);
-            }
-            const float* Asl = &As[stage][(wr * 32 + li) * LA + 4 * lg];
-            const float* Bsl = &Bs[stage][(4 * lg) * LB + wc * 32 + li];
-            if (on) {
-#pragma unroll
-                for (int jj = wk; jj < BK / 8; jj += WK) {
-                    // MFMA step t of the 8-wide k group jj takes k = 8 jj + 4 (lane >> 5) + t
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(Asl + 8 * jj);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], Bsl[(8 * jj + t) * LB], acc, 0, 0, 0);
-                }
-            }
-            if (s + 1 < nslab) lds_barrier();
+            for (int t = 0; t < 4; ++t) f.b[g][t] = Bsl[(8 * jj + t) * LB];
         }
-    }
-    if constexpr (WK == 2) {                         // the two k halves of a tile meet: wk = 1 hands its accumulators to wk = 0
-        if (wk == 1)
+    };
+    auto mfma_half = [&](const Frag& f, int h) {
 #pragma unroll
-            for (int v = 0; v < 16; ++v) red[(wc * 16 + v) * 64 + lane] = acc[v];
+        for (int g = h * (NG / 2); g < (h + 1) * (NG / 2); ++g)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[g][t], f.b[g][t], acc, 0, 0, 0);
+    };
+
+    const int nslab = (K + BK - 1) / BK;
+    fetch(0, ring[0]);
+    stash(0, 0, ring[0]);
+#pragma unroll
+    for (int j = 1; j <= PF; ++j) fetch(j, ring[j % PF]);   // slabs 1 .. PF in flight (set 0 is free again)
+    lds_barrier();
+    Frag cur;
+    read_frag(cur, 0);
+    // slab s: stash slab s + 1 (every wave left stage (s + 1) & 1, slab s - 1, before the barrier of slab s - 1: lds_barrier() waits
+    // for the wave's reads), half of the MFMAs, the barrier, the reads of slab s + 1, the other half
+    auto step = [&](int s, Slab& x, bool refill) {
+        stash((s + 1) & 1, s + 1, x);
+        if (refill) fetch(s + 1 + PF, x);
+        mfma_half(cur, 0);
         lds_barrier();
-        if (wk == 1) return;
+        Frag nxt;
+        read_frag(nxt, (s + 1) & 1);
+        mfma_half(cur, 1);
+        cur = nxt;
+    };
+    int s = 0;
+    for (; s + PF < nslab; s += PF)                  // steady state: one basic block, no test between the PF steps
 #pragma unroll
-        for (int v = 0; v < 16; ++v) acc[v] += red[(wc * 16 + v) * 64 + lane];
+        for (int j = 0; j < PF; ++j) step(s + j, ring[(j + 1) % PF], true);
+#pragma unroll
+    for (int j = 0; j < PF - 1; ++j) {               // at most PF - 1 steps are left, and nothing they would request is inside K
+        if (s + j + 1 >= nslab) break;
+        step(s + j, ring[(j + 1) % PF], false);
+    }
+    mfma_half(cur, 0);
+    mfma_half(cur, 1);
+    if constexpr (WK > 1) {                          // the k shares of a tile meet: wk > 0 hand their accumulators to wk = 0, added in order
+        const int tile = wr * WC + wc;
+        if (wk > 0)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) red[(((wk - 1) * WR * WC + tile) * 16 + v) * 64 + lane] = acc[v];
+        lds_barrier();
+        if (wk > 0) return;
+#pragma unroll
+        for (int q = 0; q < WK - 1; ++q)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[v] += red[((q * WR * WC + tile) * 16 + v) * 64 + lane];
     }
     const int gn = n0 + wc * 32 + li;
-    if (!on || gn >= N) return;
+    if (m0 + wr * 32 >= M || gn >= N) return;
     float bv = 0.f;
     if constexpr (EPI != 0) bv = bias[gn];
 #pragma unroll
@@ -177,13 +226,27 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
     }
 }
 
+// The tile of a launch: rows x columns per workgroup, chosen from the options and the shape only (the live count stays on the device).
+struct RowsTile { int tm, tn; };
+static RowsTile rows_tile(int N, int K) {
+    if (g_gemm_rows_tm == 64) return {64, 64};
+    const int tn = g_gemm_rows_tn ? g_gemm_rows_tn : 64;
+    return {32, tn};
+}
+static int64_t rows_grid(RowsTile t, int cap_rows, int N) {
+    return static_cast<int64_t>((N + t.tn - 1) / t.tn) * ((cap_rows + t.tm - 1) / t.tm);
+}
+
 template <int EPI>
-static void launch_gemm_rows(int tm, int64_t wgs, hipStream_t s, const float* A, const float* W, float* C, const int* rows,
+static void launch_gemm_rows(RowsTile t, int64_t wgs, hipStream_t s, const float* A, const float* W, float* C, const int* rows,
                              const int* count, int cap_rows, int N, int K, const float* bias, float* C2) {
-    if (tm == 32)
-        gemm_rows_f32_kernel<32, 3, EPI><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+    const unsigned g = static_cast<unsigned>(wgs);
+    if (t.tm == 64)
+        gemm_rows_f32_kernel<64, 64, 32, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+    else if (t.tn == 32)
+        gemm_rows_f32_kernel<32, 32, 64, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
     else
-        gemm_rows_f32_kernel<64, 3, EPI><<<static_cast<unsigned>(wgs), 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+        gemm_rows_f32_kernel<32, 64, 32, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
 }
 
 }  // namespace mmx
@@ -212,8 +275,8 @@ extern "C" int mmx_gemm_rows_f32(const void* a_dev, const void* w_dev, void* c_d
         set_error("mmx_gemm_rows_f32: N=%d and K=%d must be multiples of 4 and the operands 16-byte aligned", N, K);
         return MMX_ENOTSUP;
     }
-    const int tm = g_gemm_rows_tm;
-    const int64_t wgs = static_cast<int64_t>((N + kRowsTN - 1) / kRowsTN) * ((cap_rows + tm - 1) / tm);
+    const RowsTile tm = rows_tile(N, K);
+    const int64_t wgs = rows_grid(tm, cap_rows, N);
     MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
     launch_gemm_rows<0>(tm, wgs, static_cast<hipStream_t>(stream), static_cast<const float*>(a_dev), static_cast<const float*>(w_dev),
                         static_cast<float*>(c_dev), static_cast<const int*>(rows_dev), static_cast<const int*>(count_dev), cap_rows, N, K,
@@ -234,8 +297,8 @@ extern "C" int mmx_gemm_rows_bias_f32(const void* a_dev, const void* wt_dev, con
         set_error("mmx_gemm_rows_bias_f32: N=%d and K=%d must be multiples of 4 and the operands 16-byte aligned", N, K);
         return MMX_ENOTSUP;
     }
-    const int tm = g_gemm_rows_tm;
-    const int64_t wgs = static_cast<int64_t>((N + kRowsTN - 1) / kRowsTN) * ((cap_rows + tm - 1) / tm);
+    const RowsTile tm = rows_tile(N, K);
+    const int64_t wgs = rows_grid(tm, cap_rows, N);
     MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_bias_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
     const float *A = static_cast<const float*>(a_dev), *W = static_cast<const float*>(wt_dev), *bias = static_cast<const float*>(bias_dev);
     const int *rows = static_cast<const int*>(rows_dev), *count = static_cast<const int*>(count_dev);
