@@ -105,6 +105,8 @@ const char* mmx_last_error(void);
  *                        and the *_rows kernels) | 0: it declines with MMX_ENOTSUP and the caller runs the dense backward (A / B runs)
  *   "text_live_rows_fwd" 1 (default) the forward of that tower runs on the live rows too (mmx_gemm_rows_bias_f32, mmx_add_layernorm_fwd_rows)
  *                        | 0: dense forward, row-list backward (A / B runs); without "text_live_rows" it has no effect
+ *   "text_live_attn"     1 (default) inside that forward route the attention takes the caption lengths too (mmx_attn_capture_fwd_live /
+ *                        _bwd_live: no dead row of q / k / v is read, no zero fill of qkv) | 0: dense attention over a zero-filled qkv (A / B runs)
  *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
  *   "gemm_rows_tn"       0 (default: chosen from N and K) | 32 | 64: columns per workgroup tile of mmx_gemm_rows_f32 at 32 rows (same
  *                        products, another order of the k sum; 64-row tiles are always 64 wide)
@@ -427,6 +429,43 @@ int mmx_attn_capture_bwd_ex(const void* q_dev, const void* k_dev, const void* v_
                             int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
                             int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
                             int need_dqkv, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The capture pair with a LIVE LENGTH per sample, for the row-list route of a causally masked text tower (mmx_live_rows): sample b
+ * has L = clamp(eot_dev[b], 0, Nq - 1) + 1 live rows, eot_dev: int64 [B] on the device, read by the kernels (nothing comes back to the
+ * host, so a captured hipGraph follows the captions it is replayed with).  `mask_dev` must be a causal mask and Nq == Nk.
+ *   forward:  no row >= L of q / k / v is read.  Rows < L of P and O get the bits mmx_attn_capture_fwd_ex gives them on a q / k / v
+ *             whose rows >= L are zeros; rows >= L of P get that call's bits too (the softmax of zero scores under the mask), rows
+ *             >= L of O are NOT written.
+ *   backward: no row >= L of q / k / v / dO is read (rows >= L of P are not read either).  dP is written whole: rows < L with the bits
+ *             of mmx_attn_capture_bwd_ex on operands whose rows >= L are zeros, rows >= L exact zeros.  dq / dk / dv: rows < L only,
+ *             same bits; rows >= L are NOT written.
+ * Served by live-length instantiations of the whole-head fp32 kernels only: mmx_attn_live_shape(Nq, Nk, D) returns MMX_OK where one
+ * exists, MMX_ENOTSUP where not, and launches nothing
+ * (today: Nq == Nk in 65 ... 80, head_dim <= 64 and % 4 == 0 -- CLIP's text towers have 77 tokens) and option "text_live_attn" (default 1 | 0
+ * for A / B runs) is on; otherwise these calls return MMX_ENOTSUP and the caller keeps mmx_attn_capture_*_ex on a zero-filled q / k / v. */
+int mmx_attn_live_shape(int Nq, int Nk, int D);
+int mmx_attn_capture_fwd_live(const void* q_dev, const void* k_dev, const void* v_dev,
+                              int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                              int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                              int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                              const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
+                              void* probs_dev, int slab_dtype,
+                              void* o_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                              int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                              const void* eot_dev, void* stream);
+int mmx_attn_capture_bwd_live(const void* q_dev, const void* k_dev, const void* v_dev,
+                              int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                              int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                              int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                              const void* probs_dev, int64_t probs_sb, int slab_dtype,
+                              const void* do_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                              void* dprobs_dev,
+                              void* dq_dev, void* dk_dev, void* dv_dev,
+                              int64_t dq_sb, int64_t dq_sh, int64_t dq_sn,
+                              int64_t dk_sb, int64_t dk_sh, int64_t dk_sn,
+                              int64_t dv_sb, int64_t dv_sh, int64_t dv_sn,
+                              int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                              int need_dqkv, const void* eot_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* Attention forward WITHOUT a capture slab: O = softmax(scale.Q.K^T + mask).V and nothing else.  The inference forward of the
  * perturbation test (vit_perturbation.py), whose S x B re-runs of the model never look at P.  Arguments, layouts, mask

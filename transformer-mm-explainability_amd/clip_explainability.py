@@ -71,7 +71,10 @@ def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, 
     Unlike ``trim_text_padding`` this is decided on the device per call -- no read of the ids, shapes / slabs / accessors unchanged, a
     captured graph follows whatever captions it is replayed with.  The text tower's FORWARD runs on the same rows (``clip_model.
     Transformer.forward_tape(live=...)``; ``ops.set_option("text_live_rows_fwd", 0)`` keeps it dense): the rows past EOT feed neither
-    the feature nor any gradient.  The slabs then hold what the maps need (a filler in the probabilities' padded rows, zeros in the
+    the feature nor any gradient.  Inside that route the attention takes the caption lengths too, forward and backward, where the
+    whole-head kernels have a live-length instantiation (65 ... 80 tokens: every CLIP text tower has 77): no dead row of ``qkv`` is
+    read, so ``qkv`` is not zero-filled either; ``ops.set_option("text_live_attn", 0)`` restores the dense attention over a zero-filled
+    ``qkv`` (same bits; figures: ``profiles/text_attention_live_rows_probe.txt``).  The slabs then hold what the maps need (a filler in the probabilities' padded rows, zeros in the
     gradients' masked entries past EOT) until ``blk.attn_probs`` / ``blk.attn_grad`` is read, which completes them with one dense pass
     (``Transformer.complete_attn_probs``; figures: ``profiles/text_forward_live_rows_probe.txt``).  Cost of that first read: the
     whole dense text forward and the text backward once more (about the text tower's share of a step of the dense path); later reads

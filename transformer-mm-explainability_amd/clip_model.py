@@ -316,12 +316,15 @@ class Transformer(nn.Module):
 
         ``live`` (``live_rows_for_forward(x, out_rows)``, a causally masked fp32 tower): the row-list forward.  Every row-wise step
         (LayerNorms, the four GEMMs with their bias, QuickGELU) runs on the rows up to ``out_rows[b]`` only; the other rows of the
-        intermediates and of the tape are NOT written.  The attention stays dense: it reads a ``qkv`` whose unlisted rows are zeros
-        and writes ``P`` and ``O`` for all rows -- live queries see live keys only (causal mask), so their rows are exact; the dead
-        rows of ``P`` hold the softmax of zero scores, finite, which is all the backward and the chain need (their gradient rows are
-        exact zeros).  The gradient slab is then right where ``P`` is not masked (what the chain reads); its masked entries
-        ``dO[i] . V[j]``, ``j`` past the last live row, come out as zeros.  ``backward_tape`` must be given the same ``live``;
-        ``blk.attn_probs`` / ``blk.attn_grad`` complete both slabs on their first read (``complete_attn_probs``)."""
+        intermediates and of the tape are NOT written.  The attention takes the caption lengths too where the whole-head kernels have
+        a live-length instantiation (``ops.attn_live_shape``: CLIP's 77 tokens; ``ops.attn_capture_fwd(live=...)``): it
+        reads the live rows of an uninitialised ``qkv`` and writes ``O`` for them only.  Elsewhere, and with
+        ``ops.set_option("text_live_attn", 0)``, it stays dense on a ``qkv`` whose unlisted rows are zeros.  Either way live queries see
+        live keys only (causal mask), so their rows of ``P`` and ``O`` are exact and the same bits; the dead rows of ``P`` hold the
+        softmax of zero scores, finite, which is all the backward and the chain need (their gradient rows are exact zeros).  The
+        gradient slab is then right where ``P`` is not masked (what the chain reads); its masked entries ``dO[i] . V[j]``, ``j`` past
+        the last live row, come out as zeros.  ``backward_tape`` must be given the same ``live``; ``blk.attn_probs`` /
+        ``blk.attn_grad`` complete both slabs on their first read (``complete_attn_probs``)."""
         if not x.is_cuda:
             raise _lib.MMXError("the CLIP body runs its attention on the HIP capture op: move the model and "
                                 "inputs to the MI355X (there is no CPU attention path)")
@@ -343,6 +346,8 @@ class Transformer(nn.Module):
                                    "dy_row_values": None, "backward_first_grad_layer": None}
             for blk in blocks:
                 blk.__dict__["_probs_owner"] = (self,)
+            # the attention on the live rows too (kept on the list: the backward of this tape must then do the same)
+            live.attn = ops.attn_live_shape(N, blocks[0].attn.head_dim)
 
         def ln(res, y, norm):                 # s = res + y, LayerNorm(s) and its statistics: dense, or on the listed rows
             if live is not None:
@@ -359,14 +364,15 @@ class Transformer(nn.Module):
         for l, blk in enumerate(blocks):
             at = blk.attn
             if live is not None:
-                # (zeros, not LiveRows._out: the dense attention reads every row of qkv)
-                qkv = ops.linear_rows(h1, at.in_proj_weight, at.in_proj_bias, live,
-                                      out=torch.zeros(Bx, N, 3 * E, dtype=torch.float32, device=x.device))
+                # (without live lengths in the attention: zeros, not LiveRows._out -- the dense attention reads every row of qkv)
+                qkv = ops.linear_rows(h1, at.in_proj_weight, at.in_proj_bias, live, out=None if live.attn else
+                                      torch.zeros(Bx, N, 3 * E, dtype=torch.float32, device=x.device))
             else:
                 qkv = self._linear(h1, at.in_proj_weight, at.in_proj_bias)
             qkv = qkv.view(Bx, N, 3, at.num_heads, at.head_dim)
             o = ops.attn_capture_fwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buffers.probs[l], at.head_dim ** -0.5,
-                                     _lib.SCALE_Q_FIRST, mask, layout="bnhd", mma_bf16=mma)
+                                     _lib.SCALE_Q_FIRST, mask, layout="bnhd", mma_bf16=mma,
+                                     live=live if live is not None and live.attn else None)
             if out_rows is not None and l + 1 == len(blocks):
                 ar = torch.arange(Bx, device=x.device)
                 x1, h2, mean2, rstd2 = ops.add_layernorm(
@@ -469,7 +475,11 @@ class Transformer(nn.Module):
         block runs on the rows up to ``dy_rows[b]`` only (``_live_rows_route``): the rest of every gradient tensor is exact zeros.
         The attention backward still sees a dense ``d_o`` (zeros in the dead rows) and writes the whole gradient slab.
         ``live``: the list a row-list forward ran on (``forward_tape(live=...)``); it is used again instead of building a second one,
-        and it is required then -- such a tape holds the listed rows only.
+        and it is required then -- such a tape holds the listed rows only.  Where that forward's attention took the caption lengths
+        (``live.attn``), the attention backward takes them as well (``ops.attn_capture_bwd(live=...)``): ``qkv`` holds the live rows
+        only, the dead rows of ``dqkv`` are not written (nothing reads them), the gradient slab still is written whole, zeros in the
+        dead rows as before.  After a dense forward the attention backward stays dense, whatever the row-wise steps do: its masked
+        entries ``dO[i] . V[j]`` are what ``blk.attn_grad`` shows.
 
         ``targets_per_image=K`` (fp32 body, row mode only): the tape holds M distinct samples and the B = K*M upstream gradients
         are K per sample in K-major order (target t explains sample t % M).  The elementwise steps broadcast the per-sample
@@ -502,6 +512,7 @@ class Transformer(nn.Module):
             raise ValueError("backward_tape: targets_per_image=%d needs an fp32 body in the row mode and a multiple of it "
                              "upstream gradients (got %d)" % (int(targets_per_image), B))
         dx_h = None
+        handed_in = live is not None
         if live is None:
             live = self._live_rows_route(tape, B, N, E, first_grad_layer, dy_rows, dy_row_values, rel_row, grouped)
         elif dy_rows is None or dy_row_values is None or rel_row is not None or grouped or live.cap != B * N:
@@ -511,6 +522,7 @@ class Transformer(nn.Module):
             pending = self.__dict__.get("_probs_pending")
             if pending is not None and pending["live"] is live:           # what complete_attn_probs needs to run this backward again
                 pending["dy_row_values"], pending["backward_first_grad_layer"] = dy_row_values, first_grad_layer
+        live_attn = live if handed_in and live.attn else None      # the forward's attention took the lengths: so does this one
         d_o_dense = None      # live-row route: the top block's dense d_o (zeros outside the EOT rows); every block below rewrites its
                               # live rows only, so the dead rows the attention backward reads stay zero without another pass
         for l in range(top, first_grad_layer - 1, -1):
@@ -557,13 +569,16 @@ class Transformer(nn.Module):
                 d_o = d_o.float()
             d_o = d_o.view(B, N, at.num_heads, at.head_dim)
             need = l > first_grad_layer                                       # nothing below needs gradients
-            dqkv = torch.empty(B, N, 3, at.num_heads, at.head_dim, dtype=d_o.dtype, device=d_o.device) if need else None
+            if need and live_attn is not None:        # (its dead rows are not written: NaN there under LiveRows.poison)
+                dqkv = live_attn._out(d_o.view(B, N, E), 3 * E).view(B, N, 3, at.num_heads, at.head_dim)
+            else:
+                dqkv = torch.empty(B, N, 3, at.num_heads, at.head_dim, dtype=d_o.dtype, device=d_o.device) if need else None
             out = (dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2]) if need else None
             res = ops.attn_capture_bwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], buffers.probs[l], d_o,
                                        buffers.grads[l] if buffers.grads is not None else None,
                                        at.head_dim ** -0.5, _lib.SCALE_Q_FIRST, need_dqkv=need, layout="bnhd", out=out,
                                        batch=B if shared else None, o=o_fwd, mma_bf16=mma, rel_row=rel_row,
-                                       images=x.shape[0] if grouped else None)
+                                       images=x.shape[0] if grouped else None, live=live_attn)
             if rel_row is not None:
                 rel_row = res[3]
             if not need:

@@ -18,6 +18,10 @@ struct AttnFwdArgs {
     int mma_bf16; // 1: products on v_mfma_f32_16x16x32_bf16 (operands rounded to bf16, fp32 accumulate, fp32 softmax)
     int tile_skip = 0;  // whole-head kernels: skip the products of key tiles that are masked out for a whole wave (attention_head.hip)
     int no_probs = 0;   // mmx_attn_fwd: inference forward, `probs` is NULL (read by the host dispatchers only: they pick the NOP instantiations)
+    // Whole-head kernels, causally masked self-attention only (mmx_attn_capture_fwd_live): eot [B] int64 on the device -- sample b has
+    // L = clamp(eot[b], 0, Nq - 1) + 1 live rows (live_rows_kernel's formula, read by the kernel: nothing comes back to the host); no row
+    // >= L of q / k / v is read and none of o is written.  nullptr: off.  (Last member: the offsets of the others stay what they were.)
+    const long long* eot = nullptr;
 };
 
 struct AttnBwdArgs {
@@ -49,10 +53,15 @@ struct AttnBwdArgs {
     // per image over M = B / K images, K-major -- target t explains image t % M.  q / k / v / probs / o are per IMAGE (batch index
     // t % M with their own batch strides); dout, dq / dk / dv, dprobs, delta and the relevancy rows are per TARGET.  0: off.
     int grp_k = 0;
+    // see AttnFwdArgs::eot (mmx_attn_capture_bwd_live): no row >= L of q / k / v / dout / o is read, dq / dk / dv are written for the rows
+    // < L only, the dP slab is written whole (exact zeros in the rows >= L).  nullptr: off.
+    const long long* eot = nullptr;
 };
 
 int attn_fwd_head_try(const AttnFwdArgs& a, hipStream_t s, int* rc_out);    // attention_head.hip (register-resident)
 int attn_bwd_head_try(const AttnBwdArgs& a, hipStream_t s, int* rc_out);
+// is there a live-length (eot) instantiation of the whole-head kernels for this shape, and are they switched on?
+bool attn_head_live_shape(int Nq, int Nk, int D);
 int attn_fwd_stream_try(const AttnFwdArgs& a, hipStream_t s, int* rc_out);   // attention_stream.hip
 int attn_bwd_stream_try(const AttnBwdArgs& a, hipStream_t s, int* rc_out);
 // out[b][k] = v_in[b][k] + inv_h * sum_{j < J} part[b][j][k]   (row-relevancy mode, second pass; attention_kernels.hip)

@@ -312,8 +312,15 @@ __device__ __forceinline__ void stagger(int units) {
 // NOP (mmx_attn_fwd, the inference forward): the P store is compiled out; O comes from the same registers, bit for bit.
 // Its widest key sides (NTK >= 7: 100+ live registers per lane) are capped at 8 waves so that they get 256 VGPRs and do not
 // spill; a head with more than 8 query strips is then split over blockIdx.z (each workgroup stages the head's K / V itself).
-template <int DP, int NTK, bool NOP = false>
+// LIVE (AttnFwdArgs::eot; causally masked self-attention): sample b has L = clamp(eot[b], 0, Nq - 1) + 1 live rows.  Rows >= L of q / k / v
+// are never read: only the ceil(L / 16) key tiles that hold a live row are staged, the rows >= L inside them are zeros in LDS, and the
+// products run over those tiles at most.  A live row sees the keys <= itself, all live: same operands, same k-order, same bits.  A dead
+// row goes through the same softmax and store code on zero accumulators -- the softmax of zero scores under the mask, which is what
+// the dense kernel writes for a zero row of q -- and its row of O is not written.  A wave whose strip is all dead runs no MFMA; it
+// still takes the workgroup's barrier.
+template <int DP, int NTK, bool NOP = false, bool LIVE = false>
 __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_kernel(const AttnFwdArgs a) {
+    static_assert(!(LIVE && NOP), "the live-length kernels are capture kernels");
     constexpr int LSK = DP + 8, LSV = DP + 4, KK = DP / 16, NPk = NTK * 16;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;                 // [NPk][LSK]  A operand of S^T (ds_read_b128 along d)
@@ -325,14 +332,21 @@ __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_
     const bool q_first = (a.scale_mode == MMX_SCALE_Q_FIRST);
     const int q = (NOP ? blockIdx.z * (nthreads >> 6) * 16 : 0) + wave * 16 + c16;
     const bool qv = q < a.Nq;
+    int L = 0, nt = NTK;                               // LIVE: live rows of this sample, key tiles that hold one
+    if constexpr (LIVE) {
+        L = static_cast<int>(min(max(a.eot[b], 0ll), static_cast<long long>(a.Nq - 1))) + 1;
+        nt = (L + 15) >> 4;
+    }
+    const int Lq = LIVE ? L : a.Nq, Lk = LIVE ? L : a.Nk;
+    const bool strip_live = !LIVE || wave * 16 < L;    // wave-uniform
 
     stagger(a.debug >> 8);
     const int skip = a.debug & 0xff;     // profiling only: 1 no loads, 2 no S MFMA, 4 no P store, 8 no PV MFMA, 16 no O store
     f32x4 qreg[KK];
     if (!(skip & 1)) {
-        load_rows16<DP>(qreg, a.q + b * a.qs.sb + h * a.qs.sh, a.qs.sn, q, a.Nq, a.D, g, q_first ? a.scale : 1.f);
+        load_rows16<DP>(qreg, a.q + b * a.qs.sb + h * a.qs.sh, a.qs.sn, q, Lq, a.D, g, q_first ? a.scale : 1.f);
         stage_pair<DP, 4>(Ks, LSK, a.k + b * a.ks.sb + h * a.ks.sh, a.ks.sn, Vs, LSV, a.v + b * a.vs.sb + h * a.vs.sh,
-                          a.vs.sn, a.Nk, NPk, a.D, tid, nthreads);
+                          a.vs.sn, Lk, LIVE ? nt * 16 : NPk, a.D, tid, nthreads);
     } else {
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) qreg[kk] = f32x4{0.01f * lane, 0.02f, 0.03f, 0.04f};
@@ -363,7 +377,8 @@ __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_
             if (!__all(dead || !qv)) na = t + 1;
         }
     }
-    if (!(skip & 2))
+    if constexpr (LIVE) na = min(na, nt);      // (the tiles beyond hold no live key: not staged; zero scores for the dead rows)
+    if (!(skip & 2) && strip_live)
         with_tile_count<NTK>(na, [&](auto n) { tiles_kd<DP, NTK, LSK, decltype(n)::value>(acc, Ks, qreg, c16, g); });
 
     // scale / mask / softmax, all in registers (the mask chunks were requested before the S MFMAs)
@@ -405,9 +420,10 @@ __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_
     f32x4 oacc[KK];
 #pragma unroll
     for (int td = 0; td < KK; ++td) oacc[td] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!(skip & 8))
+    if (!(skip & 8) && strip_live)
         with_tile_count<NTK>(na, [&](auto n) { tiles_from_regs<DP, NTK, LSV, decltype(n)::value>(oacc, acc, Vs, c16, g); });
-    store_rows16<DP>(a.o + b * a.os.sb + h * a.os.sh, a.os.sn, q, qv && (!(skip & 16) || oacc[0][0] == 12345.f), a.D, g, oacc, 1.f);
+    store_rows16<DP>(a.o + b * a.os.sb + h * a.os.sh, a.os.sn, q, (LIVE ? q < L : qv) && (!(skip & 16) || oacc[0][0] == 12345.f), a.D,
+                     g, oacc, 1.f);
 }
 
 // ------------------------------------------------------------------------------------------------------- backward
@@ -418,8 +434,14 @@ __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_
 // GRP (grouped row mode, with REL; AttnBwdArgs::grp_k): b is the target, bi its image (Q / K / V / P); the workgroups run in the
 // logical order (image, head, target of the image), XCD-contiguous, so an image-head's K targets are neighbours on one XCD and
 // read its P / K / V / Q through L2.  Every target does the arithmetic of the per-sample kernel on the same operand values.
-template <int DP, int NTK, bool IOH = false, bool REL = false, bool GRP = false>
+// LIVE (AttnBwdArgs::eot; the backward of the LIVE forward): rows >= L of q / k / v / dO are never read and the dead rows of P are
+// taken as zeros (dO is zero there, so they only ever met exact-zero products).  dP is written whole -- live rows from the ceil(L / 16)
+// staged tiles (zeros beyond: dO . 0), dead rows exact zeros; dQ / dK / dV are written for the rows < L only, and phase C contracts
+// over the live query strips only.  Skipped k-steps had an exact-zero product: same bits.  A wave whose strip is all dead runs no MFMA and
+// writes nothing to LDS, but takes every barrier.
+template <int DP, int NTK, bool IOH = false, bool REL = false, bool GRP = false, bool LIVE = false>
 __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(const AttnBwdArgs a) {
+    static_assert(!LIVE || (!REL && !GRP), "the live-length backward is the plain capture backward");
     constexpr int LSA = DP + 8, LSB = DP + 4, KK = DP / 16, NPk = NTK * 16, SS = NPk + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
@@ -442,6 +464,14 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     const int q = wave * 16 + c16;
     const bool qv = q < a.Nq;
     const int64_t head = static_cast<int64_t>(b) * a.H + h;
+    int L = 0, nt = NTK;                               // LIVE: live rows of this sample, key tiles / query strips that hold one
+    if constexpr (LIVE) {
+        L = static_cast<int>(min(max(a.eot[b], 0ll), static_cast<long long>(a.Nq - 1))) + 1;
+        nt = (L + 15) >> 4;
+    }
+    const int Lq = LIVE ? L : a.Nq, Lk = LIVE ? L : a.Nk;
+    const bool lv = LIVE ? q < L : qv;                 // this lane's row is read and written
+    const bool strip_live = !LIVE || wave * 16 < L;    // wave-uniform
 
     stagger(a.debug >> 8);
     MMX_TL_DECL;
@@ -449,22 +479,22 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     // this wave's rows of dO (and Q') and its chunks of P: global -> registers, issued before the LDS staging
     f32x4 doreg[KK], qreg[KK], preg[NTK];
     if constexpr (IOH)
-        load_rows16_bf16<DP>(doreg, reinterpret_cast<const unsigned short*>(a.dout) + b * a.os.sb + h * a.os.sh, a.os.sn, q, a.Nq,
+        load_rows16_bf16<DP>(doreg, reinterpret_cast<const unsigned short*>(a.dout) + b * a.os.sb + h * a.os.sh, a.os.sn, q, Lq,
                              a.D, g);
     else
-        load_rows16<DP>(doreg, a.dout + b * a.os.sb + h * a.os.sh, a.os.sn, q, a.Nq, a.D, g, 1.f);
+        load_rows16<DP>(doreg, a.dout + b * a.os.sb + h * a.os.sh, a.os.sn, q, Lq, a.D, g, 1.f);
     const float* prow = a.probs + bi * a.probs_sb + (static_cast<int64_t>(h) * a.Nq + (qv ? q : 0)) * a.Nk;
 #pragma unroll
-    for (int t = 0; t < NTK; ++t) preg[t] = load_chunk(prow, t * 16 + 4 * g, a.Nk, qv);
+    for (int t = 0; t < NTK; ++t) preg[t] = load_chunk(prow, t * 16 + 4 * g, a.Nk, lv);
     const float* vb = a.v + bi * a.vs.sb + h * a.vs.sh;
     float vq = 0.f;     // REL: this row's weight, loaded with the other operands (retired by the staging barrier)
     if constexpr (REL) vq = a.rel_v[static_cast<int64_t>(b) * a.Nq + (qv ? q : a.Nq - 1)];
     if (a.need_dqkv) {
-        load_rows16<DP>(qreg, a.q + bi * a.qs.sb + h * a.qs.sh, a.qs.sn, q, a.Nq, a.D, g, q_first ? a.scale : 1.f);
-        stage_pair<DP, 4>(Vs, LSA, vb, a.vs.sn, Ks, LSB, a.k + bi * a.ks.sb + h * a.ks.sh, a.ks.sn, a.Nk, NPk, a.D, tid,
+        load_rows16<DP>(qreg, a.q + bi * a.qs.sb + h * a.qs.sh, a.qs.sn, q, Lq, a.D, g, q_first ? a.scale : 1.f);
+        stage_pair<DP, 4>(Vs, LSA, vb, a.vs.sn, Ks, LSB, a.k + bi * a.ks.sb + h * a.ks.sh, a.ks.sn, Lk, LIVE ? nt * 16 : NPk, a.D, tid,
                           nthreads);
     } else {
-        stage_one<DP, 4>(Vs, LSA, vb, a.vs.sn, a.Nk, NPk, a.D, tid, nthreads);
+        stage_one<DP, 4>(Vs, LSA, vb, a.vs.sn, Lk, LIVE ? nt * 16 : NPk, a.D, tid, nthreads);
     }
     MMX_TL_MARK();                                                   // 1: V / K staged (this wave's part)
     lds_barrier();
@@ -477,7 +507,11 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     f32x4 acc[NTK];
 #pragma unroll
     for (int t = 0; t < NTK; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    tiles_kd<DP, NTK, LSA>(acc, Vs, doreg, c16, g);
+    if constexpr (LIVE) {
+        if (strip_live) with_tile_count<NTK>(nt, [&](auto n) { tiles_kd<DP, NTK, LSA, decltype(n)::value>(acc, Vs, doreg, c16, g); });
+    } else {
+        tiles_kd<DP, NTK, LSA>(acc, Vs, doreg, c16, g);
+    }
     MMX_TL_MARK();                                                   // 3: dP tiles done (waits for dO rows)
     float* dprow = a.dprobs + (head * a.Nq + (qv ? q : 0)) * a.Nk;
     float dot = 0.f;
@@ -519,7 +553,8 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
         }
     }
     if (lane == 0) live_tab[wave] = live;
-    const int na = live ? 32 - __builtin_clz(live) : 1;
+    const int na_p = live ? 32 - __builtin_clz(live) : 1;
+    const int na = LIVE ? min(na_p, nt) : na_p;        // (LIVE: the tiles beyond are not staged)
     dot = rows4_allreduce<false>(dot);
 #pragma unroll
     for (int t = 0; t < NTK; ++t)
@@ -532,16 +567,16 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
 
     MMX_TL_MARK();                                                   // 4: dP stored, delta reduced, dS (waits for P chunks)
     // ---- phase B: dQ = dS.K, dS straight from the accumulators
-    {
+    if (strip_live) {
         f32x4 dq[KK];
 #pragma unroll
         for (int td = 0; td < KK; ++td) dq[td] = f32x4{0.f, 0.f, 0.f, 0.f};
         with_tile_count<NTK>(na, [&](auto n) { tiles_from_regs<DP, NTK, LSB, decltype(n)::value>(dq, acc, Ks, c16, g); });
         if constexpr (IOH)
-            store_rows16_bf16<DP>(reinterpret_cast<unsigned short*>(a.dq) + b * a.dqs.sb + h * a.dqs.sh, a.dqs.sn, q, qv, a.D, g, dq,
+            store_rows16_bf16<DP>(reinterpret_cast<unsigned short*>(a.dq) + b * a.dqs.sb + h * a.dqs.sh, a.dqs.sn, q, lv, a.D, g, dq,
                                   q_first ? a.scale : 1.f);
         else
-            store_rows16<DP>(a.dq + b * a.dqs.sb + h * a.dqs.sh, a.dqs.sn, q, qv, a.D, g, dq, q_first ? a.scale : 1.f);
+            store_rows16<DP>(a.dq + b * a.dqs.sb + h * a.dqs.sh, a.dqs.sn, q, lv, a.D, g, dq, q_first ? a.scale : 1.f);
     }
 
     MMX_TL_MARK();                                                   // 5: dQ done and stored
@@ -550,18 +585,20 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     for (int pass = 0; pass < 2; ++pass) {
         lds_barrier();                                           // previous readers of this LDS region are done
         MMX_TL_MARK();                                               // 6 / 8: barrier passed
+        if (strip_live) {                                        // (LIVE: the rows of a dead strip are not read below)
 #pragma unroll
-        for (int t = 0; t < NTK; ++t)
-            *reinterpret_cast<f32x4*>(Ts + q * SS + t * 16 + 4 * g) = pass == 0 ? acc[t] : preg[t];
+            for (int t = 0; t < NTK; ++t)
+                *reinterpret_cast<f32x4*>(Ts + q * SS + t * 16 + 4 * g) = pass == 0 ? acc[t] : preg[t];
 #pragma unroll
-        for (int kk = 0; kk < KK; ++kk)
-            *reinterpret_cast<f32x4*>(Bs + q * LSB + kk * 16 + 4 * g) = pass == 0 ? qreg[kk] : doreg[kk];
+            for (int kk = 0; kk < KK; ++kk)
+                *reinterpret_cast<f32x4*>(Bs + q * LSB + kk * 16 + 4 * g) = pass == 0 ? qreg[kk] : doreg[kk];
+        }
         lds_barrier();
         float* outb = pass == 0 ? a.dk + b * a.dks.sb + h * a.dks.sh : a.dv + b * a.dvs.sb + h * a.dvs.sh;
         unsigned short* outh = pass == 0 ? reinterpret_cast<unsigned short*>(a.dk) + b * a.dks.sb + h * a.dks.sh
                                          : reinterpret_cast<unsigned short*>(a.dv) + b * a.dvs.sb + h * a.dvs.sh;
         const int64_t osn = pass == 0 ? a.dks.sn : a.dvs.sn;
-        for (int kt = wave; kt < NTK; kt += NTQ) {
+        for (int kt = wave; kt < (LIVE ? nt : NTK); kt += NTQ) {     // (LIVE: the key tiles beyond hold dead rows only)
             // out^T tile (keys 16kt .. + 15 as the MFMA's N index): k-step s = (tq, r) pairs row 16tq + 4g + r of Ts (column
             // 16kt + c16) with the same row of Bs; the operands of step s + 1 are fetched before the MFMAs of step s
             f32x4 o[KK];
@@ -570,10 +607,12 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
             const float* t0 = Ts + 4 * g * SS + kt * 16 + c16;
             const float* b0 = Bs + 4 * g * LSB + c16;
             // query strips whose P tile at this key tile is all zero contribute exact zeros (dS = P (dP - delta) is zero with it): run from
-            // the first live strip to the last one (a causal tower: strips kt ... NTQ - 1)
+            // the first live strip to the last one (a causal tower: strips kt ... NTQ - 1; LIVE: ... ceil(L / 16) - 1, the strips beyond
+            // hold dead rows only and wrote nothing)
             int tq0 = NTQ, tq1 = 0;
             for (int tq = 0; tq < NTQ; ++tq)
                 if ((live_tab[tq] >> kt) & 1u) { tq0 = min(tq0, tq); tq1 = tq + 1; }
+            if constexpr (LIVE) tq1 = min(tq1, nt);
             tq0 = __builtin_amdgcn_readfirstlane(min(tq0, tq1));
             tq1 = __builtin_amdgcn_readfirstlane(tq1);
             const int s0 = tq0 * 4, steps = tq1 * 4;
@@ -597,8 +636,8 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
                 for (int td = 0; td < KK; ++td) b_cur[td] = b_nxt[td];
             }
             const int key = kt * 16 + c16;
-            if constexpr (IOH) store_rows16_bf16<DP>(outh, osn, key, key < a.Nk, a.D, g, o, 1.f);
-            else store_rows16<DP>(outb, osn, key, key < a.Nk, a.D, g, o, 1.f);
+            if constexpr (IOH) store_rows16_bf16<DP>(outh, osn, key, key < Lk, a.D, g, o, 1.f);
+            else store_rows16<DP>(outb, osn, key, key < Lk, a.D, g, o, 1.f);
         }
         MMX_TL_MARK();                                               // 7 / 9: pass done
     }
@@ -628,6 +667,17 @@ static int g_attn_head_tile_skip = 1;   // option "attn_head_tile_skip": masked-
 void attn_head_tile_skip(int on) { g_attn_head_tile_skip = on ? 1 : 0; }
 static int g_attn_head_stagger = 0;
 void attn_head_enable(int on) { g_attn_head = on & 1; g_attn_head_stagger = on >> 8; }   // bits 8..15 fwd phase skips, 16.. stagger
+// option "text_live_attn": 1 (default) the row-list route of a causal text tower hands the caption lengths to these kernels (LIVE) |
+// 0: attn_head_live_shape says no, and the route keeps the dense attention over a zero-filled qkv (A / B runs)
+static int g_text_live_attn = 1;
+bool attn_head_live_option(const char* key, int value) {
+    if (strcmp(key, "text_live_attn") == 0 && value >= 0 && value <= 1) { g_text_live_attn = value; return true; }
+    return false;
+}
+// The LIVE instantiations: 65 ... 80 tokens (five key tiles: CLIP's text towers have 77), either head_dim padding.
+bool attn_head_live_shape(int Nq, int Nk, int D) {
+    return g_attn_head && g_text_live_attn && Nq == Nk && D >= 4 && D <= 64 && D % 4 == 0 && (Nk + 15) / 16 == 5;
+}
 
 static size_t fwd_head_lds(int DP, int NTK) { return sizeof(float) * NTK * 16 * (2 * DP + 12); }
 
@@ -726,6 +776,17 @@ int attn_fwd_head_try(const AttnFwdArgs& a_in, hipStream_t s, int* rc_out) {
         return 0;
     const int DP = a.D <= 32 ? 32 : 64, NTK = (a.Nk + 15) / 16, threads = 64 * ((a.Nq + 15) / 16);
     const size_t lds = fwd_head_lds(DP, NTK);
+    if (a.eot) {
+        if (a.no_probs || !a.mask || !attn_head_live_shape(a.Nq, a.Nk, a.D)) {
+            set_error("attn_fwd_head: no live-length instantiation for Nq=%d Nk=%d D=%d (masked capture forward, 65 ... 80 tokens; "
+                      "option text_live_attn)", a.Nq, a.Nk, a.D);
+            *rc_out = MMX_ENOTSUP;
+        } else {
+            *rc_out = DP == 32 ? launch_head(attn_fwd_head_kernel<32, 5, false, true>, a, threads, lds, s, "attn_fwd_head_kernel<live>")
+                               : launch_head(attn_fwd_head_kernel<64, 5, false, true>, a, threads, lds, s, "attn_fwd_head_kernel<live>");
+        }
+        return 1;
+    }
     if (a.no_probs)     // mmx_attn_fwd: the same kernel, same launch geometry, no P store
         *rc_out = DP == 32 ? fwd_head_dispatch_nop<32>(a, NTK, threads, lds, s) : fwd_head_dispatch_nop<64>(a, NTK, threads, lds, s);
     else
@@ -754,6 +815,18 @@ int attn_bwd_head_try(const AttnBwdArgs& a_in, hipStream_t s, int* rc_out) {
     const size_t lds = bwd_head_lds(DP, NTK, NTQ, rel);
     if (lds > 160 * 1024 || (NTK >= 7 && NTQ > 8)) return 0;
     if (rel && (a.io_bf16 || a.Nq != a.Nk)) return 0;
+    if (a.eot) {
+        if (rel || a.io_bf16 || !attn_head_live_shape(a.Nq, a.Nk, a.D)) {
+            set_error("attn_bwd_head: no live-length instantiation for Nq=%d Nk=%d D=%d (fp32 capture backward, 65 ... 80 tokens; "
+                      "option text_live_attn)", a.Nq, a.Nk, a.D);
+            *rc_out = MMX_ENOTSUP;
+        } else {
+            *rc_out = DP == 32
+                ? launch_head(attn_bwd_head_kernel<32, 5, false, false, false, true>, a, threads, lds, s, "attn_bwd_head_kernel<live>")
+                : launch_head(attn_bwd_head_kernel<64, 5, false, false, false, true>, a, threads, lds, s, "attn_bwd_head_kernel<live>");
+        }
+        return 1;
+    }
     if (rel && a.grp_k) {
         // grouped row mode: the same grid, one workgroup per (target, head), in the order the kernel decodes
         *rc_out = DP == 32 ? bwd_head_dispatch<32, false, true, true>(a, NTK, threads, lds, s)

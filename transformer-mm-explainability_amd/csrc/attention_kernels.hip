@@ -326,12 +326,12 @@ extern "C" int mmx_attn_capture_fwd(const void* q_dev, const void* k_dev, const 
                                    scale_mode, stream);
 }
 
-extern "C" int mmx_attn_capture_fwd_ex(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
+static int attn_fwd_impl(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
                                        int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
                                        int64_t v_sh, int64_t v_sn, const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
                                        void* probs_dev, int slab_dtype, void* o_dev, int64_t o_sb, int64_t o_sh,
                                        int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
-                                       void* stream) {
+                                       void* stream, const void* eot_dev) {
     MMX_CHECK_ARG(q_dev && k_dev && v_dev && probs_dev && o_dev, "mmx_attn_capture_fwd: null pointer");
     const int mma_bf16 = (slab_dtype & MMX_ATTN_MMA_BF16) ? 1 : 0;
     slab_dtype &= ~MMX_ATTN_MMA_BF16;
@@ -349,6 +349,13 @@ extern "C" int mmx_attn_capture_fwd_ex(const void* q_dev, const void* k_dev, con
     a.mma_bf16 = mma_bf16;
     dim3 grid((Nq + kTQ - 1) / kTQ, H, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (eot_dev) {      // live lengths: the whole-head kernels' LIVE instantiations or nothing (the other kernels would read every row)
+        a.eot = static_cast<const long long*>(eot_dev);
+        if (slab_dtype == MMX_F32 && !mma_bf16 && attn_fwd_head_try(a, s, &rc)) return rc;
+        set_error("mmx_attn_capture_fwd_live: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels "
+                  "(mmx_attn_live_shape)", Nq, Nk, D);
+        return MMX_ENOTSUP;
+    }
     if (slab_dtype != MMX_F32 || mma_bf16) {   // half-precision slabs / bf16 MFMA: the streaming kernels only
         if (attn_fwd_stream_try(a, s, &rc)) return rc;
         set_error("mmx_attn_capture_fwd: fp16 / bf16 capture slabs and MMX_ATTN_MMA_BF16 need head_dim %% 4 == 0 "
@@ -359,6 +366,37 @@ extern "C" int mmx_attn_capture_fwd_ex(const void* q_dev, const void* k_dev, con
     if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: K/V streamed, nothing of size Nk on chip
     if (D <= 32) return launch_dyn(attn_capture_fwd_kernel<32>, a, grid, attn_lds_bytes(32, Nk), s, "attn_capture_fwd_kernel<32>");
     return launch_dyn(attn_capture_fwd_kernel<64>, a, grid, attn_lds_bytes(64, Nk), s, "attn_capture_fwd_kernel<64>");
+}
+
+extern "C" int mmx_attn_capture_fwd_ex(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
+                                       int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
+                                       int64_t v_sh, int64_t v_sn, const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
+                                       void* probs_dev, int slab_dtype, void* o_dev, int64_t o_sb, int64_t o_sh,
+                                       int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                                       void* stream) {
+    return attn_fwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev, mask_sb, mask_sq,
+                         probs_dev, slab_dtype, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, stream, nullptr);
+}
+
+extern "C" int mmx_attn_live_shape(int Nq, int Nk, int D) {
+    MMX_CHECK_ARG(Nq > 0 && Nk > 0 && D > 0, "mmx_attn_live_shape: non-positive size");
+    if (attn_head_live_shape(Nq, Nk, D)) return MMX_OK;
+    set_error("mmx_attn_live_shape: no live-length instantiation of the whole-head kernels for Nq=%d Nk=%d D=%d, or option "
+              "text_live_attn / attn_head is 0", Nq, Nk, D);
+    return MMX_ENOTSUP;
+}
+
+// mmx_attn_capture_fwd_ex with a live length per sample (AttnFwdArgs::eot): a causally masked self-attention whose rows past
+// eot_dev[b] are neither read (q / k / v) nor written (o).
+extern "C" int mmx_attn_capture_fwd_live(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
+                                         int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
+                                         int64_t v_sh, int64_t v_sn, const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
+                                         void* probs_dev, int slab_dtype, void* o_dev, int64_t o_sb, int64_t o_sh,
+                                         int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                                         const void* eot_dev, void* stream) {
+    MMX_CHECK_ARG(eot_dev && mask_dev, "mmx_attn_capture_fwd_live: null eot / mask (the lengths stand on a causal mask)");
+    return attn_fwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev, mask_sb, mask_sq,
+                         probs_dev, slab_dtype, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, stream, eot_dev);
 }
 
 // The inference forward: the capture forward's fp32 dispatch with the no-slab instantiations.
@@ -463,7 +501,7 @@ static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev
                                        int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D, float scale,
                                        int scale_mode, int need_dqkv, void* workspace_dev, size_t workspace_bytes,
                                        void* stream, const void* rel_in_dev, void* rel_out_dev, bool rel_f32 = false,
-                                       int grp_k = 0) {
+                                       int grp_k = 0, const void* eot_dev = nullptr) {
     const bool rel = rel_in_dev != nullptr;
     MMX_CHECK_ARG(v_dev && probs_dev && do_dev && (dprobs_dev || rel), "mmx_attn_capture_bwd: null pointer");
     const int io_bf16 = (slab_dtype & MMX_ATTN_IO_BF16) ? 1 : 0;
@@ -520,6 +558,13 @@ static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev
     a.rel_out = static_cast<float*>(rel_out_dev);
     a.grp_k = grp_k;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (eot_dev) {      // live lengths: the whole-head kernels' LIVE instantiations or nothing
+        a.eot = static_cast<const long long*>(eot_dev);
+        if (!rel && slab_dtype == MMX_F32 && !mma_bf16 && !io_bf16 && attn_bwd_head_try(a, s, &rc)) return rc;
+        set_error("mmx_attn_capture_bwd_live: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels "
+                  "(mmx_attn_live_shape)", Nq, Nk, D);
+        return MMX_ENOTSUP;
+    }
     if (rel && rel_f32) {
         if (attn_bwd_head_try(a, s, &rc)) return rc;    // N <= 128: one partial row per head
         // the exact-fp32 key-side streaming kernel reads dP back from the slab (the row is extra work, not another schedule)
@@ -581,6 +626,24 @@ extern "C" int mmx_attn_capture_bwd_ex(const void* q_dev, const void* k_dev, con
                          slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
                          dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
                          scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, nullptr, nullptr);
+}
+
+// mmx_attn_capture_bwd_ex with a live length per sample (AttnBwdArgs::eot), the backward of mmx_attn_capture_fwd_live: rows past
+// eot_dev[b] of q / k / v / dO are not read, those of dq / dk / dv not written; the dP slab is written whole (zeros in those rows).
+extern "C" int mmx_attn_capture_bwd_live(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
+                                         int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
+                                         int64_t v_sh, int64_t v_sn, const void* probs_dev, int64_t probs_sb, int slab_dtype,
+                                         const void* do_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn, void* dprobs_dev,
+                                         void* dq_dev, void* dk_dev, void* dv_dev, int64_t dq_sb, int64_t dq_sh,
+                                         int64_t dq_sn, int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t dv_sb,
+                                         int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D, float scale,
+                                         int scale_mode, int need_dqkv, const void* eot_dev, void* workspace_dev,
+                                         size_t workspace_bytes, void* stream) {
+    MMX_CHECK_ARG(eot_dev, "mmx_attn_capture_bwd_live: null eot");
+    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
+                         slab_dtype, do_dev, o_sb, o_sh, o_sn, nullptr, 0, 0, 0, dprobs_dev, dq_dev, dk_dev,
+                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
+                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, nullptr, nullptr, false, 0, eot_dev);
 }
 
 extern "C" int mmx_attn_capture_bwd_rowrel(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,

@@ -626,13 +626,16 @@ def rows_add_(dense, rows, vals):
 
 class LiveRows:
     """Device-side list of the live rows of a ``[B, N, *]`` gradient stream (``live_rows``): ``rows`` int32 ``[B * N]`` (the first
-    ``count[0]`` entries are valid), ``count`` int32 ``[1]``.  ``poison``: debug switch of the ``*_rows`` wrappers below -- their
+    ``count[0]`` entries are valid), ``count`` int32 ``[1]``; ``eot`` int64 ``[B]``: the last live position of every sample, what the list was
+    built from and what the attention takes as its live lengths (``attn_capture_fwd(live=...)``); ``attn``: set by a forward whose
+    attention did take them -- its ``qkv`` then holds the listed rows only, and the backward must take them too.  ``poison``: debug switch of the ``*_rows`` wrappers below -- their
     outputs start as NaN instead of uninitialised memory, so a consumer that reads an unlisted row shows up in the results."""
     poison = False
 
-    def __init__(self, rows, count, batch, n_tokens):
+    def __init__(self, rows, count, batch, n_tokens, eot=None):
         self.rows, self.count, self.batch, self.n_tokens = rows, count, batch, n_tokens
         self.cap = batch * n_tokens
+        self.eot, self.attn = eot, False
 
     def _out(self, like, width):
         shape = tuple(like.shape[:-1]) + (width,)
@@ -657,7 +660,20 @@ def live_rows(eot, n_tokens):
     if rc == _lib.MMX_ENOTSUP:
         return None
     check(rc, "mmx_live_rows")
-    return LiveRows(buf[1:], buf[:1], B, n_tokens)
+    return LiveRows(buf[1:], buf[:1], B, n_tokens, eot)
+
+
+def attn_live_shape(n_tokens, head_dim):
+    """Is there a live-length instantiation of the whole-head attention kernels for a self-attention over ``n_tokens`` with this
+    ``head_dim`` (``mmx_attn_live_shape``; today 65 ... 80 tokens, head_dim <= 64 and a multiple of 4 -- CLIP's text towers have 77), and is option
+    ``text_live_attn`` on?  If not, the row-list route keeps the dense attention over a zero-filled ``qkv``."""
+    return lib().mmx_attn_live_shape(n_tokens, n_tokens, head_dim) == 0
+
+
+def _live_attn_check(what, live, B, Nq, Nk, probs):
+    if live.eot is None or live.batch != B or live.n_tokens != Nq or Nq != Nk or probs.dtype != torch.float32:
+        raise MMXError("%s: live= needs an fp32 self-attention over the %d x %d rows of the list, got batch %d, Nq %d, Nk %d, %s slab"
+                       % (what, live.batch, live.n_tokens, B, Nq, Nk, str(probs.dtype).replace("torch.", "")))
 
 
 def gemm_rows_eligible(*weights):
@@ -963,12 +979,17 @@ def _mask_strides(mask, Nk):
     raise MMXError("mask must be [Nq,Nk] or [B,Nq|1,Nk]")
 
 
-def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="bnhd", mma_bf16=False):
+def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="bnhd", mma_bf16=False, live=None,
+                     out=None):
     """``q``: ``[B, Nq, H, D]`` view (``layout='bnhd'``) or ``[B, H, Nq, D]``; writes P into ``probs_out``
     (``[B, H, Nq, Nk]`` fp32 contiguous, caller-owned slab) and returns O in the same layout as q.
     ``mma_bf16``: products on the bf16 matrix cores (``MMX_ATTN_MMA_BF16``: operands rounded to bf16, fp32 accumulate
-    and softmax; long-sequence streaming kernels only)."""
-    _dev(q, k, v, probs_out, mask)
+    and softmax; long-sequence streaming kernels only).
+    ``live`` (a ``LiveRows`` over the ``B x N`` rows; CAUSAL ``mask``, ``attn_live_shape``): ``mmx_attn_capture_fwd_live`` -- the rows
+    past ``live.eot[b]`` of q / k / v are not read and those of O are not written; the live rows of P and O get the bits of the dense
+    call on a q / k / v with zeros in the dead rows, and so do the dead rows of P (the softmax of zero scores under the mask).
+    ``out``: a caller-owned fp32 tensor of q's shape (contiguous head_dim) to write O into."""
+    _dev(q, k, v, probs_out, mask, out)
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
         raise MMXError("attention capture op is fp32 in this ABI version")
     if layout == "bnhd":
@@ -979,8 +1000,20 @@ def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, m
         Nk = k.shape[2]
     if probs_out.dtype not in _DTYPES or not probs_out.is_contiguous() or probs_out.numel() != B * H * Nq * Nk:
         raise MMXError("probs_out must be a contiguous fp32 / fp16 / bf16 [B,H,Nq,Nk] slab")
-    o = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    if out is not None and (out.dtype != torch.float32 or out.shape != q.shape):
+        raise MMXError("attn_capture_fwd: out must be fp32 of q's shape %s" % (tuple(q.shape),))
     mask, msb, msq = _mask_strides(mask, Nk)
+    if live is not None:
+        _live_attn_check("attn_capture_fwd", live, B, Nq, Nk, probs_out)
+        if mask is None or mma_bf16:
+            raise MMXError("attn_capture_fwd: live= stands on a causal mask and the exact-fp32 kernels")
+        o = out if out is not None else live._out(q, D)
+        check(lib().mmx_attn_capture_fwd_live(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
+                                              *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(probs_out), _DTYPES[probs_out.dtype],
+                                              _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
+                                              _p(live.eot), _stream()), "mmx_attn_capture_fwd_live")
+        return o
+    o = out if out is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
     check(lib().mmx_attn_capture_fwd_ex(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
                                         *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(probs_out),
                                         _DTYPES[probs_out.dtype] | (_lib.MMX_ATTN_MMA_BF16 if mma_bf16 else 0),
@@ -1119,8 +1152,12 @@ def _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode
 
 
 def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, need_dqkv=True,
-                     layout="bnhd", out=None, batch=None, o=None, mma_bf16=False, rel_row=None, images=None):
+                     layout="bnhd", out=None, batch=None, o=None, mma_bf16=False, rel_row=None, images=None, live=None):
     """Writes dP into ``dprobs_out`` and returns ``(dq, dk, dv)`` (``None`` when ``need_dqkv`` is False).
+    ``live`` (the backward of ``attn_capture_fwd(live=...)``, ``mmx_attn_capture_bwd_live``; fp32 ``d_o``, none of ``batch`` /
+    ``rel_row`` / ``images`` / ``mma_bf16``): the rows past ``live.eot[b]`` of q / k / v / d_o are not read and those of dq / dk / dv
+    are not written; ``dprobs_out`` is written whole, exact zeros in the dead rows; every live value has the bits of the dense call
+    on operands with zeros in the dead rows.
     ``out=(dq, dk, dv)`` lets the caller hand in (strided) views, e.g. of one packed dqkv tensor.
     ``batch``: shared-forward mode -- q/k/v/probs come from ONE forward (batch 1) and are broadcast (stride 0) over the
     ``batch`` upstream gradients in ``d_o``; dq/dk/dv/dprobs are per sample.
@@ -1133,6 +1170,10 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
     come from ONE forward over M distinct images (batch M); ``d_o``, ``rel_row``, dq/dk/dv and ``dprobs_out`` have batch T, a
     multiple of M, in K-major order -- target t explains image t % M."""
     _dev(q, k, v, probs, d_o, dprobs_out, rel_row)
+    if live is not None and (images is not None or rel_row is not None or mma_bf16 or dprobs_out is None
+                             or (batch is not None and batch != q.shape[0]) or d_o.dtype != torch.float32):
+        raise MMXError("attn_capture_bwd: live= is the plain fp32 capture backward (a dprobs slab, an fp32 d_o, one forward per "
+                       "gradient; no rel_row / images / mma_bf16)")
     if images is not None:
         return _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode, need_dqkv, layout, out, o,
                                          mma_bf16, rel_row, int(images))
@@ -1212,6 +1253,17 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
             B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(rel_row), _p(rel_out), _p(ws), need, _stream()),
             "mmx_attn_capture_bwd_rowrel")
         return dq, dk, dv, rel_out
+    if live is not None:
+        _live_attn_check("attn_capture_bwd", live, B, Nq, Nk, probs)
+        check(lib().mmx_attn_capture_bwd_live(
+            _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
+            _p(probs), probs_sb, _DTYPES[probs.dtype], _p(d_o), *_bhnd_strides(d_o, layout), _p(dprobs_out), _p(dq), _p(dk), _p(dv),
+            *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
+            *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
+            B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(live.eot), _p(ws), need, _stream()),
+            "mmx_attn_capture_bwd_live")
+        return dq, dk, dv
+
     def call(d_o_, dq_, dk_, dv_, flags_):
         return lib().mmx_attn_capture_bwd_ex(
             _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
