@@ -749,24 +749,34 @@ def add_layernorm_rows(x, y, gamma, beta, eps, live, out=None):
     return s, h, mean, rstd
 
 
-def quick_gelu_bwd_rows(x, dy, live):
-    """``quick_gelu_bwd`` on the live rows (``x`` at the same row as ``dy``)."""
-    _dev(x, dy)
+def quick_gelu_bwd_rows(x, dy, live, out=None):
+    """``quick_gelu_bwd`` on the live rows (``x`` at the same row as ``dy``); every other row of the result is left alone.  ``out``: an
+    fp32 contiguous tensor of ``dy``'s shape to write to."""
+    _dev(x, dy, out)
     live._check("quick_gelu_bwd_rows", x, dy)
-    dx = live._out(dy, dy.shape[-1])
+    dx = out if out is not None else live._out(dy, dy.shape[-1])
+    if out is not None:
+        live._check("quick_gelu_bwd_rows", out)
+        if out.shape != dy.shape:
+            raise MMXError("quick_gelu_bwd_rows: dy %s -> out %s" % (tuple(dy.shape), tuple(out.shape)))
     check(lib().mmx_quick_gelu_bwd_rows(_p(x), _p(dy), _p(dx), _p(live.rows), _p(live.count), live.cap, dy.shape[-1], _stream()),
           "mmx_quick_gelu_bwd_rows")
     return dx
 
 
-def layernorm_bwd_add_rows(dy, x, mean, rstd, gamma, d_res, live):
-    """``layernorm_bwd_add`` on the live rows (per-row ``x`` / ``mean`` / ``rstd``)."""
-    _dev(dy, x, mean, rstd, gamma, d_res)
+def layernorm_bwd_add_rows(dy, x, mean, rstd, gamma, d_res, live, out=None):
+    """``layernorm_bwd_add`` on the live rows (per-row ``x`` / ``mean`` / ``rstd``); every other row of the result is left alone.
+    ``out``: an fp32 contiguous tensor of ``dy``'s shape to write to."""
+    _dev(dy, x, mean, rstd, gamma, d_res, out)
     live._check("layernorm_bwd_add_rows", dy, x, *([d_res] if d_res is not None else []))
     mean, rstd = _f32c(mean), _f32c(rstd)
     if mean.numel() != live.cap or rstd.numel() != live.cap:
         raise MMXError("layernorm_bwd_add_rows: %d statistics for %d rows" % (mean.numel(), live.cap))
-    dx = live._out(dy, dy.shape[-1])
+    dx = out if out is not None else live._out(dy, dy.shape[-1])
+    if out is not None:
+        live._check("layernorm_bwd_add_rows", out)
+        if out.shape != dy.shape:
+            raise MMXError("layernorm_bwd_add_rows: dy %s -> out %s" % (tuple(dy.shape), tuple(out.shape)))
     check(lib().mmx_layernorm_bwd_add_rows(_p(dy), _p(x), _p(mean), _p(rstd), _p(_f32c(gamma)), _p(d_res), _p(dx), _p(live.rows),
                                            _p(live.count), live.cap, dy.shape[-1], _stream()), "mmx_layernorm_bwd_add_rows")
     return dx
