@@ -486,6 +486,22 @@ int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev,
                  void* o_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
                  int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, void* stream);
 
+/* mmx_attn_fwd with a LIVE LENGTH per sample: the no-slab forward of the row-list inference route of a causally masked text tower
+ * (Transformer.forward_nocapture(live=...), the re-runs of the caption perturbation test, clip_text_perturbation.py).  Arguments of
+ * mmx_attn_fwd plus eot_dev (int64 [B] on the device), placed as in mmx_attn_capture_fwd_live; `mask_dev` must be a causal mask and
+ * Nq == Nk (else MMX_EINVAL).  With L = clamp(eot_dev[b], 0, Nq - 1) + 1: no row >= L of q / k / v is read; rows < L of O carry the
+ * bits mmx_attn_capture_fwd_live writes to O (which are the bits of mmx_attn_fwd on operands whose rows >= L are zeros); rows >= L of
+ * O are NOT written.  Same shape space and option as the capture pair above (mmx_attn_live_shape), else MMX_ENOTSUP and nothing is
+ * launched.  Every argument is checked before any HIP call. */
+int mmx_attn_fwd_live(const void* q_dev, const void* k_dev, const void* v_dev,
+                      int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                      int64_t k_sb, int64_t k_sh, int64_t k_sn,
+                      int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                      const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
+                      void* o_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn,
+                      int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                      const void* eot_dev, void* stream);
+
 /* Patch perturbation test for image models (the positive / negative perturbation test of the paper at patch granularity;
  * evaluator: vit_perturbation.py; same removal order and step counts as the bi-modal evaluators, lxmert/lxmert/perturbation.py:112).
  * mmx_patch_ranks: scores [B, P] fp32 -> ranks [B, P] int32, ranks[b][i] = position of patch i in ONE stable descending order
@@ -498,6 +514,24 @@ int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev,
 int mmx_patch_ranks(const void* scores_dev, void* ranks_dev, int B, int P, void* stream);
 int mmx_perturb_patches(const void* images_dev, const void* ranks_dev, const void* counts_dev, const void* fill_dev,
                         void* out_dev, int B, int C, int R, int patch, int S, void* stream);
+
+/* Token perturbation test for CLIP captions (evaluator: clip_text_perturbation.py): the text half of the reference's bi-modal test,
+ * lxmert/lxmert/perturbation.py:158-176 -- the first and the last token always stay, the int((1 - step) * W) top-scoring words stay in
+ * their original order, the rest is dropped -- on CLIP's EOT convention (CLIP/clip/model.py:360).  One launch builds the S perturbed
+ * copies of B captions:
+ *   ids [B, N] int64, scores [B, N] fp32 (one per POSITION), counts [S, N - 1] int32 ON THE DEVICE
+ *   -> out_ids [S, B, N] int64, out_eot [S, B] int64, ranks [B, N] int32 (or NULL).
+ * Per caption b: e = index of the FIRST maximum of ids[b] (text.argmax(dim=-1); an all-zero row gives 0); the words are the positions
+ * 1 <= p < e, W = max(e - 1, 0); scores outside the words are never read.  rank[p] = position of word p in ONE stable descending
+ * order of the words' scores, the total order of mmx_patch_ranks (lower index first among equals, +0.0 == -0.0, NaN before +inf);
+ * ranks[b][p] receives it at the words and -1 elsewhere.  Step s keeps word p iff rank[p] < counts[s][W]; the host fills
+ * counts[s][w] = int((1 - step_s) * w), w = 0 ... N - 2, in host float arithmetic (lxmert/lxmert/perturbation.py:112) -- the kernel
+ * does no float arithmetic on steps.  out_ids[s][b] = [ids[b][0], kept words in ascending position, ids[b][e], 0, ...] and
+ * out_eot[s][b] = 1 + kept (e = 0: [ids[b][0], 0, ...] and 0), so argmax(out_ids[s][b]) == out_eot[s][b].  The positive test ranks
+ * the negated scores (the caller negates).  2 <= N <= 256, 1 <= S <= 64, B >= 1, else MMX_EINVAL; every argument is checked before
+ * any HIP call. */
+int mmx_perturb_tokens(const void* ids_dev, const void* scores_dev, const void* counts_dev, void* out_ids_dev, void* out_eot_dev,
+                       void* ranks_dev, int B, int N, int S, void* stream);
 
 /* Row-relevancy mode of the backward (BASELINE config 5; CLIP `interpret`, CLIP/clip/... notebook cell 7:27-37, returns
  * only `R[:, 0, 1:]` of the image tower): row 0 of  R_final = (I + A_L) ... (I + A_start)  is  e_0^T (I + A_L) ... , i.e.

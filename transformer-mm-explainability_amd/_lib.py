@@ -67,7 +67,10 @@ _PROTOTYPES = {
     "mmx_attn_capture_bwd_live": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
                                   + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
     "mmx_attn_fwd": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "mmx_attn_fwd_live": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _i, _vp,
+                               _vp]),
     "mmx_patch_ranks": (_i, [_vp, _vp, _i, _i, _vp]),
+    "mmx_perturb_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_perturb_patches": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mmx_attn_capture_bwd_ex": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64,
                                      _vp, _vp, _vp, _vp]

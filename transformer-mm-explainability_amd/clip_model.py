@@ -401,11 +401,15 @@ class Transformer(nn.Module):
         return x, tape
 
     @torch.no_grad()
-    def forward_nocapture(self, x, out_rows=None):
+    def forward_nocapture(self, x, out_rows=None, live=None):
         """Inference forward of the stack: ``x [B, N, E]`` -> ``y [B, N, E]``, attention on ``ops.attn_fwd``.  No capture slab is
         touched or allocated (``self.buffers`` stays as it is) and no tape is kept.  ``out_rows``: as in ``forward_tape`` (a
         ``[B]`` long tensor), or a Python int when every sample reads the same row (the class token); the top block then runs on
-        those rows only -- with an int also its attention queries -- and ``y`` is ``[B, E]``.  fp32 bodies only."""
+        those rows only -- with an int also its attention queries -- and ``y`` is ``[B, E]``.  fp32 bodies only.
+        ``live`` (``live_rows_for_forward(x, out_rows)``, a causally masked tower, ``out_rows`` a tensor): the row-list route of
+        ``forward_tape(live=...)`` without the tape -- LayerNorms and the four GEMMs (QuickGELU from ``c_fc``'s epilogue) on the rows
+        up to ``out_rows[b]`` only, the attention on ``ops.attn_fwd(live=...)`` where ``ops.attn_live_shape`` allows it and dense over a
+        ``qkv`` whose unlisted rows are zeros elsewhere; the top block gathers row ``out_rows[b]`` as before."""
         for what in ("forward_gemm_dtype", "capture_dtype"):
             dt = getattr(self, what, torch.float32)
             if dt != torch.float32:
@@ -418,6 +422,10 @@ class Transformer(nn.Module):
         B, N, E = x.shape
         blocks = list(self.resblocks)
         mask = self._mask_for(blocks[0], N, x.device) if blocks else None
+        if live is not None:
+            if out_rows is None or isinstance(out_rows, int) or live.cap != B * N:
+                raise ValueError("forward_nocapture: the row-list forward needs out_rows [B] and a list over %d rows" % (B * N))
+            return self._forward_nocapture_rows(x, out_rows, live, blocks, mask)
         first = blocks[0].ln_1
         _, h1, _, _ = ops.add_layernorm(x, None, first.weight, first.bias, first.eps)
         for l, blk in enumerate(blocks):
@@ -445,6 +453,35 @@ class Transformer(nn.Module):
             else:
                 x = x1 + mlp_out
         return x
+
+    def _forward_nocapture_rows(self, x, out_rows, live, blocks, mask):
+        """``forward_nocapture(live=...)``: the steps of ``forward_tape(live=...)``, nothing kept."""
+        B, N, E = x.shape
+        live_attn = ops.attn_live_shape(N, blocks[0].attn.head_dim)
+        first = blocks[0].ln_1
+        _, h1, _, _ = ops.add_layernorm_rows(x, None, first.weight, first.bias, first.eps, live)
+        for l, blk in enumerate(blocks):
+            at = blk.attn
+            # (without live lengths in the attention: zeros, not LiveRows._out -- the dense attention reads every row of qkv)
+            qkv = ops.linear_rows(h1, at.in_proj_weight, at.in_proj_bias, live, out=None if live_attn else
+                                  torch.zeros(B, N, 3 * E, dtype=torch.float32, device=x.device))
+            qkv = qkv.view(B, N, 3, at.num_heads, at.head_dim)
+            o = ops.attn_fwd(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], at.head_dim ** -0.5, _lib.SCALE_Q_FIRST, mask, layout="bnhd",
+                             live=live if live_attn else None)
+            if l + 1 == len(blocks):
+                ar = torch.arange(B, device=x.device)
+                x1, h2, _, _ = ops.add_layernorm(x[ar, out_rows],
+                                                 self._linear(o.view(B, N, E)[ar, out_rows], at.out_proj.weight, at.out_proj.bias),
+                                                 blk.ln_2.weight, blk.ln_2.bias, blk.ln_2.eps)
+                mlp_out = self._linear(ops.quick_gelu_fwd(self._linear(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias)),
+                                       blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
+                return x1 + mlp_out
+            x1, h2, _, _ = ops.add_layernorm_rows(x, ops.linear_rows(o.view(B, N, E), at.out_proj.weight, at.out_proj.bias, live),
+                                                  blk.ln_2.weight, blk.ln_2.bias, blk.ln_2.eps, live)
+            _, act = ops.linear_rows(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, live, gelu=True)
+            mlp_out = ops.linear_rows(act, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, live)
+            nxt = blocks[l + 1].ln_1
+            x, h1, _, _ = ops.add_layernorm_rows(x1, mlp_out, nxt.weight, nxt.bias, nxt.eps, live)
 
     def forward_shared(self, x, batch):
         """Shared-forward mode of ``forward_tape`` (kept under its round-1 name)."""
@@ -828,10 +865,17 @@ class CLIP(nn.Module):
         return f @ self.text_projection, (tape, x.shape, rows, mean, rstd, eot, live)
 
     @torch.no_grad()
-    def encode_text_nocapture(self, text):
-        """``encode_text`` as an inference forward (``Transformer.forward_nocapture``) -> ``features [B, embed_dim]``."""
+    def encode_text_nocapture(self, text, live=False, eot=None):
+        """``encode_text`` as an inference forward (``Transformer.forward_nocapture``) -> ``features [B, embed_dim]``.
+        ``live=True``: on the rows up to each caption's EOT token where the tower is eligible (``Transformer.live_rows_for_forward``;
+        the dense forward where it is not) -- the re-runs of the caption perturbation test (``clip_text_perturbation``), whose
+        captions get shorter with every step.  Default: the dense forward.  ``eot [B]`` long: ``text.argmax(dim=-1)`` where the
+        caller holds it already."""
         x = self.token_embedding(text).type(self.dtype) + self.positional_embedding[:text.shape[1]].type(self.dtype)
-        rows = self.transformer.forward_nocapture(x, out_rows=text.argmax(dim=-1))         # model.py:360
+        if eot is None:
+            eot = text.argmax(dim=-1)                                                      # model.py:360
+        rows = self.transformer.forward_nocapture(x, out_rows=eot,
+                                                  live=self.transformer.live_rows_for_forward(x, eot) if live else None)
         _, f, _, _ = ops.add_layernorm(rows, None, self.ln_final.weight, self.ln_final.bias, self.ln_final.eps)
         return f @ self.text_projection
 

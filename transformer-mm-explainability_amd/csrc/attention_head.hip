@@ -318,9 +318,11 @@ __device__ __forceinline__ void stagger(int units) {
 // row goes through the same softmax and store code on zero accumulators -- the softmax of zero scores under the mask, which is what
 // the dense kernel writes for a zero row of q -- and its row of O is not written.  A wave whose strip is all dead runs no MFMA; it
 // still takes the workgroup's barrier.
+// LIVE && NOP (mmx_attn_fwd_live, the row-list inference forward): the same, without the P store; a wave whose strip is all dead has
+// neither a P row to fill nor an O row to store and leaves after the barrier.
 template <int DP, int NTK, bool NOP = false, bool LIVE = false>
 __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_kernel(const AttnFwdArgs a) {
-    static_assert(!(LIVE && NOP), "the live-length kernels are capture kernels");
+    static_assert(!(LIVE && NOP) || NTK < 7, "LIVE takes wave w's strip as rows 16w ...: no blockIdx.z split");
     constexpr int LSK = DP + 8, LSV = DP + 4, KK = DP / 16, NPk = NTK * 16;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem;                 // [NPk][LSK]  A operand of S^T (ds_read_b128 along d)
@@ -360,6 +362,9 @@ __global__ __launch_bounds__((NOP && NTK >= 7) ? 512 : 1024) void attn_fwd_head_
             mk[t] = mrow ? load_chunk(mrow, t * 16 + 4 * g, a.Nk, true) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     lds_barrier();
+    if constexpr (LIVE && NOP) {
+        if (!strip_live) return;       // (wave-uniform; the only barrier of this kernel is behind it)
+    }
 
     // S^T tiles: acc[t][r] = S[q][key = 16t + 4g + r]
     f32x4 acc[NTK];
@@ -777,10 +782,13 @@ int attn_fwd_head_try(const AttnFwdArgs& a_in, hipStream_t s, int* rc_out) {
     const int DP = a.D <= 32 ? 32 : 64, NTK = (a.Nk + 15) / 16, threads = 64 * ((a.Nq + 15) / 16);
     const size_t lds = fwd_head_lds(DP, NTK);
     if (a.eot) {
-        if (a.no_probs || !a.mask || !attn_head_live_shape(a.Nq, a.Nk, a.D)) {
-            set_error("attn_fwd_head: no live-length instantiation for Nq=%d Nk=%d D=%d (masked capture forward, 65 ... 80 tokens; "
+        if (!a.mask || !attn_head_live_shape(a.Nq, a.Nk, a.D)) {
+            set_error("attn_fwd_head: no live-length instantiation for Nq=%d Nk=%d D=%d (masked forward, 65 ... 80 tokens; "
                       "option text_live_attn)", a.Nq, a.Nk, a.D);
             *rc_out = MMX_ENOTSUP;
+        } else if (a.no_probs) {     // mmx_attn_fwd_live: the same kernel, same launch geometry, no P store
+            *rc_out = DP == 32 ? launch_head(attn_fwd_head_kernel<32, 5, true, true>, a, threads, lds, s, "attn_fwd_head_kernel<nop, live>")
+                               : launch_head(attn_fwd_head_kernel<64, 5, true, true>, a, threads, lds, s, "attn_fwd_head_kernel<nop, live>");
         } else {
             *rc_out = DP == 32 ? launch_head(attn_fwd_head_kernel<32, 5, false, true>, a, threads, lds, s, "attn_fwd_head_kernel<live>")
                                : launch_head(attn_fwd_head_kernel<64, 5, false, true>, a, threads, lds, s, "attn_fwd_head_kernel<live>");

@@ -399,13 +399,15 @@ extern "C" int mmx_attn_capture_fwd_live(const void* q_dev, const void* k_dev, c
                          probs_dev, slab_dtype, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, stream, eot_dev);
 }
 
-// The inference forward: the capture forward's fp32 dispatch with the no-slab instantiations.
-extern "C" int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh, int64_t q_sn,
-                            int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
-                            const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
-                            int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, void* stream) {
-    MMX_CHECK_ARG(q_dev && k_dev && v_dev && o_dev, "mmx_attn_fwd: null pointer");
-    int rc = check_attn_dims("mmx_attn_fwd", B, H, Nq, Nk, D, scale_mode);
+// The inference forward: the capture forward's fp32 dispatch with the no-slab instantiations.  eot_dev: live lengths
+// (mmx_attn_fwd_live): the whole-head kernels' LIVE instantiations or nothing -- the other kernels would read every row.
+static int attn_fwd_nop_impl(const char* fn, const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,
+                             int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                             const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
+                             int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, const void* eot_dev,
+                             void* stream) {
+    MMX_CHECK_ARG(q_dev && k_dev && v_dev && o_dev, "%s: null pointer", fn);
+    int rc = check_attn_dims(fn, B, H, Nq, Nk, D, scale_mode);
     if (rc) return rc;
     AttnFwdArgs a;
     a.q = static_cast<const float*>(q_dev); a.k = static_cast<const float*>(k_dev); a.v = static_cast<const float*>(v_dev);
@@ -417,12 +419,39 @@ extern "C" int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_
     a.mma_bf16 = 0;
     a.no_probs = 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (eot_dev) {
+        a.eot = static_cast<const long long*>(eot_dev);
+        if (attn_fwd_head_try(a, s, &rc)) return rc;
+        set_error("%s: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels (mmx_attn_live_shape)", fn, Nq, Nk, D);
+        return MMX_ENOTSUP;
+    }
     if (attn_fwd_head_try(a, s, &rc)) return rc;    // the whole-head kernel wherever the capture forward picks it
     if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: one sweep with a running maximum
     dim3 grid((Nq + kTQ - 1) / kTQ, H, B);
     if (D <= 32)
         return launch_dyn(attn_capture_fwd_kernel<32, true>, a, grid, attn_lds_bytes(32, Nk), s, "attn_capture_fwd_kernel<32, nop>");
     return launch_dyn(attn_capture_fwd_kernel<64, true>, a, grid, attn_lds_bytes(64, Nk), s, "attn_capture_fwd_kernel<64, nop>");
+}
+
+extern "C" int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                            int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                            const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
+                            int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, void* stream) {
+    return attn_fwd_nop_impl("mmx_attn_fwd", q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev,
+                             mask_sb, mask_sq, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, nullptr, stream);
+}
+
+// mmx_attn_fwd with a live length per sample (AttnFwdArgs::eot): the no-slab forward of a causally masked self-attention whose rows
+// past eot_dev[b] are neither read (q / k / v) nor written (o).
+extern "C" int mmx_attn_fwd_live(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh, int64_t q_sn,
+                                 int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
+                                 const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
+                                 int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
+                                 const void* eot_dev, void* stream) {
+    MMX_CHECK_ARG(eot_dev && mask_dev, "mmx_attn_fwd_live: null eot / mask (the lengths stand on a causal mask)");
+    MMX_CHECK_ARG(Nq == Nk, "mmx_attn_fwd_live: a self-attention is expected, got Nq=%d Nk=%d", Nq, Nk);
+    return attn_fwd_nop_impl("mmx_attn_fwd_live", q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev,
+                             mask_sb, mask_sq, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, eot_dev, stream);
 }
 
 extern "C" size_t mmx_attn_capture_bwd_workspace_bytes(int B, int H, int Nq) {

@@ -12,6 +12,16 @@
 //     16-byte stores (rows that are not a multiple of 4 pixels wide, or unaligned tensors, take the one-pixel form).  A pure
 //     streaming kernel: S * B * C * R^2 * 4 bytes written, B * C * R^2 * 4 read.  counts lives on the device so that a
 //     captured pass builds nothing from host lists.
+//
+// Token perturbation test for CLIP captions (clip_text_perturbation.py; the text half of the reference's bi-modal test,
+// lxmert/lxmert/perturbation.py:158-176, on the EOT convention of CLIP/clip/model.py:360):
+//   * mmx_perturb_tokens: the S perturbed copies of B captions in ONE launch.  One wave per caption: the ids are read once into LDS, the
+//     wave finds e = the first maximum of the row (text.argmax: the EOT token), turns the scores of the words 1 <= p < e into the keys
+//     of mmx_patch_ranks (every other position: key 0, below every real key, so the counting loop needs no second predicate), ranks them
+//     by counting (W <= 254 words: at most 64 k comparisons), and for every step compacts [SOT, kept words, EOT] with one ballot and a
+//     popcount prefix per 64 positions.  The compacted row is assembled in LDS and leaves as contiguous 8-byte stores, zeros behind
+//     it.  counts [S][N - 1] (device, host-built once: int((1 - step) * w) for every word count w) is indexed with the caption's own
+//     W: no float arithmetic on steps here, nothing read back.  No atomics, no workspace.
 #include "mmx_common.h"
 
 namespace mmx {
@@ -86,6 +96,89 @@ __global__ __launch_bounds__(256) void perturb_patches_kernel(const float* __res
     }
 }
 
+constexpr int kMaxPositions = 256, kMaxTokenSteps = 64;
+
+// grid B, one wave: caption b -> out_ids[s][b][.], out_eot[s][b] for every step s, ranks[b][.] (optional)
+__global__ __launch_bounds__(64) void perturb_tokens_kernel(const long long* __restrict__ ids, const float* __restrict__ scores,
+                                                            const int* __restrict__ counts, long long* __restrict__ out_ids,
+                                                            long long* __restrict__ out_eot, int* __restrict__ ranks, int B, int N,
+                                                            int S) {
+    __shared__ __attribute__((aligned(16))) unsigned keys[kMaxPositions];
+    __shared__ long long idrow[kMaxPositions];
+    __shared__ long long outrow[kMaxPositions];
+    __shared__ int rk[kMaxPositions];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long* irow = ids + static_cast<int64_t>(b) * N;
+    const float* srow = scores + static_cast<int64_t>(b) * N;
+    const int chunks = (N + 63) >> 6;
+
+    // e: index of the FIRST maximum of the row (a lane walks its positions in ascending order: strictly greater only)
+    long long best = 0;
+    int e = N;                                              // (a lane without a position: loses every tie)
+    for (int c = 0; c < chunks; ++c) {
+        const int p = c * 64 + lane;
+        if (p < N) {
+            const long long v = irow[p];
+            idrow[p] = v;
+            if (e == N || v > best) { best = v; e = p; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const long long ob = __shfl_xor(best, off);
+        const int oe = __shfl_xor(e, off);
+        if (oe < N && (e == N || ob > best || (ob == best && oe < e))) { best = ob; e = oe; }
+    }
+    const int W = e > 1 ? e - 1 : 0;                        // the words are the positions 1 .. e - 1
+
+    const int N4 = (N + 3) & ~3;
+    for (int c = 0; c < (N4 + 63) >> 6; ++c) {
+        const int p = c * 64 + lane;
+        if (p < N4) keys[p] = (p >= 1 && p < e) ? order_key(srow[p]) : 0u;       // scores outside the words are never read
+    }
+    __syncthreads();
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    const int E4 = (e + 3) & ~3;                            // <= N4: keys at and past e are 0
+    for (int c = 0; c < chunks; ++c) {
+        const int p = c * 64 + lane;
+        if (p < N) {
+            int before = -1;
+            if (p >= 1 && p < e) {
+                const unsigned kp = keys[p];
+                before = 0;
+                for (int j = 0; j < E4; j += 4) {
+                    const u32x4_t kj = *reinterpret_cast<const u32x4_t*>(keys + j);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) before += (kj[r] > kp || (kj[r] == kp && j + r < p)) ? 1 : 0;
+                }
+            }
+            rk[p] = before;
+            if (ranks) ranks[static_cast<int64_t>(b) * N + p] = before;
+        }
+    }
+    __syncthreads();
+
+    for (int s = 0; s < S; ++s) {
+        const int keep_n = counts[static_cast<int64_t>(s) * (N - 1) + W];        // W <= N - 2
+        int total = 0;
+        for (int c = 0; c < chunks; ++c) {
+            const int p = c * 64 + lane;
+            const bool keep = p < N && (p == 0 || p == e || (p < e && rk[p] < keep_n));
+            const unsigned long long m = __ballot(keep);
+            if (keep) outrow[total + __popcll(m & ((1ull << lane) - 1ull))] = idrow[p];
+            total += __popcll(m);
+        }
+        __syncthreads();
+        long long* orow = out_ids + (static_cast<int64_t>(s) * B + b) * N;
+        for (int c = 0; c < chunks; ++c) {
+            const int p = c * 64 + lane;
+            if (p < N) orow[p] = p < total ? outrow[p] : 0ll;
+        }
+        if (lane == 0) out_eot[static_cast<int64_t>(s) * B + b] = total - 1;
+        __syncthreads();                                    // the next step rewrites outrow
+    }
+}
+
 }  // namespace
 }  // namespace mmx
 
@@ -122,5 +215,18 @@ extern "C" int mmx_perturb_patches(const void* images_dev, const void* ranks_dev
     else if (vec) perturb_patches_kernel<4, false><<<grid, 256, 0, s>>>(img, rk, cn, fl, out, B, C, R, patch, S);
     else perturb_patches_kernel<1, false><<<grid, 256, 0, s>>>(img, rk, cn, fl, out, B, C, R, patch, S);
     MMX_LAUNCH_CHECK("perturb_patches_kernel");
+    return MMX_OK;
+}
+
+extern "C" int mmx_perturb_tokens(const void* ids_dev, const void* scores_dev, const void* counts_dev, void* out_ids_dev,
+                                  void* out_eot_dev, void* ranks_dev, int B, int N, int S, void* stream) {
+    MMX_CHECK_ARG(ids_dev && scores_dev && counts_dev && out_ids_dev && out_eot_dev, "mmx_perturb_tokens: null pointer");
+    MMX_CHECK_ARG(B >= 1, "mmx_perturb_tokens: batch %d < 1", B);
+    MMX_CHECK_ARG(N >= 2 && N <= kMaxPositions, "mmx_perturb_tokens: %d positions outside 2 .. %d", N, kMaxPositions);
+    MMX_CHECK_ARG(S >= 1 && S <= kMaxTokenSteps, "mmx_perturb_tokens: %d steps outside 1 .. %d", S, kMaxTokenSteps);
+    perturb_tokens_kernel<<<dim3(B), 64, 0, static_cast<hipStream_t>(stream)>>>(
+        static_cast<const long long*>(ids_dev), static_cast<const float*>(scores_dev), static_cast<const int*>(counts_dev),
+        static_cast<long long*>(out_ids_dev), static_cast<long long*>(out_eot_dev), static_cast<int*>(ranks_dev), B, N, S);
+    MMX_LAUNCH_CHECK("perturb_tokens_kernel");
     return MMX_OK;
 }

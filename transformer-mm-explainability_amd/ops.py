@@ -1032,11 +1032,15 @@ def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, m
     return o
 
 
-def attn_fwd(q, k, v, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="bnhd", out=None):
+def attn_fwd(q, k, v, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="bnhd", out=None, live=None):
     """Attention forward WITHOUT a capture slab (``mmx_attn_fwd``): operands, mask and scale modes as ``attn_capture_fwd``;
     returns O in the layout of q.  Exact fp32.  Up to 128 keys it is the capture forward's whole-head kernel with the P store
     compiled out (O bit-identical); beyond, one sweep over the keys with a running row maximum.  ``out``: a caller-owned fp32
-    tensor of q's shape (contiguous head_dim) to write O into."""
+    tensor of q's shape (contiguous head_dim) to write O into.
+    ``live`` (a ``LiveRows`` over the ``B x N`` rows; CAUSAL ``mask``, ``attn_live_shape``): ``mmx_attn_fwd_live`` -- the rows past
+    ``live.eot[b]`` of q / k / v are not read and those of O are not written; the live rows of O get the bits of
+    ``attn_capture_fwd(live=...)``, which are those of the dense call on a q / k / v with zeros in the dead rows.  Outside
+    ``attn_live_shape`` it raises (``MMX_ENOTSUP``; nothing is launched)."""
     _dev(q, k, v, mask, out)
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
         raise MMXError("attn_fwd is exact fp32 (no bf16 / fp16 mode yet), got %s" % str(q.dtype).replace("torch.", ""))
@@ -1048,8 +1052,17 @@ def attn_fwd(q, k, v, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="b
         Nk = k.shape[2]
     if out is not None and (out.dtype != torch.float32 or out.shape != q.shape):
         raise MMXError("attn_fwd: out must be fp32 of q's shape %s" % (tuple(q.shape),))
-    o = out if out is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
     mask, msb, msq = _mask_strides(mask, Nk)
+    if live is not None:
+        _live_attn_check("attn_fwd", live, B, Nq, Nk, q)
+        if mask is None:
+            raise MMXError("attn_fwd: live= stands on a causal mask")
+        o = out if out is not None else live._out(q, D)
+        check(lib().mmx_attn_fwd_live(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
+                                      *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk,
+                                      D, float(scale), scale_mode, _p(live.eot), _stream()), "mmx_attn_fwd_live")
+        return o
+    o = out if out is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
     check(lib().mmx_attn_fwd(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
                              _p(mask), msb, msq, _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
                              _stream()), "mmx_attn_fwd")
@@ -1095,6 +1108,40 @@ def perturb_patches(images, ranks, counts, fill, out=None):
     check(lib().mmx_perturb_patches(_p(images), _p(ranks), _p(counts), _p(fill), _p(out), B, C, R, R // grid, S, _stream()),
           "mmx_perturb_patches")
     return out
+
+
+def perturb_tokens(ids, scores, counts, want_ranks=False, out=None):
+    """The S perturbed copies of B captions in one launch (``mmx_perturb_tokens``).  ``ids [B, N]`` int64 token ids, ``scores [B, N]``
+    fp32 (one per position), ``counts [S, N - 1]`` int32 on the device (``clip_text_perturbation.token_step_counts``) ->
+    ``(out_ids [S, B, N] int64, out_eot [S, B] int64)``, with ``want_ranks`` also ``ranks [B, N]`` int32.  A caption's EOT is the first
+    maximum of its ids, its words the positions between position 0 and EOT; step s keeps the ``counts[s][W]`` best-scored of its W
+    words (ONE stable descending order, the one of ``patch_ranks``) in their original order between the first token and EOT, zeros
+    behind; ``out_eot`` is where EOT lands (``== out_ids.argmax(-1)``).  ``2 <= N <= 256``, ``S <= 64``.  ``out``: contiguous
+    ``(out_ids, out_eot)`` or, with ``want_ranks``, ``(out_ids, out_eot, ranks)`` to write to."""
+    _dev(ids, scores, counts, *(out or ()))
+    if ids.dim() != 2 or ids.dtype != torch.int64 or scores.dtype != torch.float32 or scores.shape != ids.shape:
+        raise MMXError("perturb_tokens: ids [B, N] int64 and scores [B, N] fp32 expected, got %s %s / %s %s"
+                       % (tuple(ids.shape), ids.dtype, tuple(scores.shape), scores.dtype))
+    B, N = ids.shape
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != N - 1:
+        raise MMXError("perturb_tokens: counts must be [S, %d] int32 (one count per word count), got %s %s"
+                       % (N - 1, tuple(counts.shape), counts.dtype))
+    S = counts.shape[0]
+    ids, scores, counts = ids.contiguous(), scores.contiguous(), counts.contiguous()
+    if out is not None:
+        if len(out) != (3 if want_ranks else 2):
+            raise MMXError("perturb_tokens: out must be (out_ids, out_eot%s)" % (", ranks" if want_ranks else ""))
+        out_ids, out_eot, ranks = tuple(out) + (() if want_ranks else (None,))
+        for t, shape, dt in ((out_ids, (S, B, N), torch.int64), (out_eot, (S, B), torch.int64), (ranks, (B, N), torch.int32)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+                raise MMXError("perturb_tokens: out needs contiguous out_ids [S, B, N] int64, out_eot [S, B] int64, ranks [B, N] int32")
+    else:
+        out_ids = torch.empty(S, B, N, dtype=torch.int64, device=ids.device)
+        out_eot = torch.empty(S, B, dtype=torch.int64, device=ids.device)
+        ranks = torch.empty(B, N, dtype=torch.int32, device=ids.device) if want_ranks else None
+    check(lib().mmx_perturb_tokens(_p(ids), _p(scores), _p(counts), _p(out_ids), _p(out_eot), _p(ranks), B, N, S, _stream()),
+          "mmx_perturb_tokens")
+    return (out_ids, out_eot, ranks) if want_ranks else (out_ids, out_eot)
 
 
 def head_kernel_shape(n_q, n_k, head_dim, slab_dtype=torch.float32):
