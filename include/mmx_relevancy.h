@@ -107,6 +107,8 @@ const char* mmx_last_error(void);
  *                        | 0: dense forward, row-list backward (A / B runs); without "text_live_rows" it has no effect
  *   "text_live_attn"     1 (default) inside that forward route the attention takes the caption lengths too (mmx_attn_capture_fwd_live /
  *                        _bwd_live: no dead row of q / k / v is read, no zero fill of qkv) | 0: dense attention over a zero-filled qkv (A / B runs)
+ *   "text_live_rows_half" 0 (default) an fp16 body (the reference's convert_weights mode) keeps the dense text tower | 1: it takes the row-list
+ *                        route too, its GEMMs on mmx_gemm_rows_f16 / mmx_gemm_rows_bias_f16 (needs "text_live_rows" and "text_live_rows_fwd")
  *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
  *   "gemm_rows_tn"       0 (default: chosen from N and K) | 32 | 64: columns per workgroup tile of mmx_gemm_rows_f32 at 32 rows (same
  *                        products, another order of the k sum; 64-row tiles are always 64 wide)
@@ -258,6 +260,22 @@ int mmx_add_layernorm_fwd_rows(const void* x_dev, const void* y_dev, const void*
                                void* sum_dev, void* h_dev, void* mean_dev, void* rstd_dev, const void* rows_dev,
                                const void* count_dev, int cap_rows, int E, float eps, void* stream);
 int mmx_text_live_rows_fwd_enabled(void);
+/* The same two GEMMs for the reference's HALF-PRECISION mode (convert_weights, CLIP/clip/model.py:381-402: every nn.Linear weight in
+ * fp16; the causal mask of model.py:334-340 and the EOT read of model.py:360 as above) on v_mfma_f32_32x32x16_f16:
+ *   mmx_gemm_rows_f16           C[r] = half(A[r]) . W_h^T for the listed rows r.  A: [cap_rows, K] fp32 (rounded to fp16 in registers, round to
+ *                               nearest even: the bits of x.to(torch.float16)), W_h: [N, K] fp16 row-major (k fastest: an nn.Linear weight
+ *                               as stored for a forward, the fp16 copy of weight.t() for the backward's x @ weight), C: [cap_rows, N] fp32
+ *                               from fp32 accumulators.  Eligible: N % 8 == 0, K % 8 == 0, 16-byte aligned operands; MMX_ENOTSUP otherwise,
+ *                               nothing launched.  Unlisted rows of C are not written, ids outside [0, cap_rows) are skipped.
+ *   mmx_gemm_rows_bias_f16      the same + bias[n] (fp32) on the finished sum; act_dev != NULL ([cap_rows, N], not C): QuickGELU of C's listed
+ *                               rows is stored there as well, with the bits mmx_quick_gelu_fwd gives on C.
+ *   mmx_text_live_rows_half_enabled  1 iff options "text_live_rows_half" (default 0), "text_live_rows" and "text_live_rows_fwd" are all on.
+ * Tiles: 32 rows x 64 columns, 32 x 32 for N <= 512; option "gemm_rows_tn" (32 | 64) overrides the choice. */
+int mmx_gemm_rows_f16(const void* a_dev, const void* wh_dev, void* c_dev, const void* rows_dev, const void* count_dev,
+                      int cap_rows, int N, int K, void* stream);
+int mmx_gemm_rows_bias_f16(const void* a_dev, const void* wh_dev, const void* bias_dev, void* c_dev, void* act_dev,
+                           const void* rows_dev, const void* count_dev, int cap_rows, int N, int K, void* stream);
+int mmx_text_live_rows_half_enabled(void);
 
 /* The chain on VECTORS (rows-only DETR rules): when a caller returns single rows of R_q_i (`aggregated[:, target_index, :]`,
  * DETR/modules/ExplanationGenerator.py:180-182) the encoder product R_ii = (I + A_6) ... (I + A_1) (`:110-118`) is needed only

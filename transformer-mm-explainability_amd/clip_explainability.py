@@ -82,6 +82,10 @@ def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, 
     ``ops.set_option("text_live_rows", 0)`` switches both off process-wide.  Price: captions at the
     truncation limit (77 tokens) have no dead rows and the row-list GEMM then does the library GEMM's work (figures, once measured:
     ``profiles/text_backward_live_rows_probe.txt``); the switch is the answer for such inputs.
+    An fp16 body (``model.set_body_dtype(torch.float16)``, the reference's ``convert_weights`` mode) keeps its dense text tower unless
+    ``ops.set_option("text_live_rows_half", 1)`` (default 0): the same route then, with its GEMMs on the fp16 matrix cores
+    (``mmx_gemm_rows_f16``: activations rounded to fp16 inside the kernel, fp32 accumulation -- the dense fp16 path's roundings, another
+    order of the fp32 sums; figures: ``profiles/text_live_rows_half_probe.txt``).  bf16 bodies stay dense.
 
     ``overlap_towers`` (extra keyword, default on): image tower on a side stream, text tower on the current one (they
     only meet in the similarity head); ``False`` runs them back to back on the current stream.  Same results bit for bit.
@@ -198,9 +202,12 @@ class GraphedInterpret:
             # the row-list forward reads the cached TRANSPOSED copies of the text tower's weights, and the graph has their addresses:
             # keep them alive (an in-place weight update makes a later eager call replace the cache entries).  The replays go on
             # reading these copies -- weights changed after the capture need a new GraphedInterpret to be seen
+            # (an fp16 body on the route, option text_live_rows_half: the two cached fp16 copies instead)
+            half = getattr(txt, "forward_gemm_dtype", torch.float32) == torch.float16
             self._pinned_weights = [
-                ops.transposed_weight(w) for blk in txt.resblocks
-                for w in (blk.attn.in_proj_weight, blk.attn.out_proj.weight, blk.mlp.c_fc.weight, blk.mlp.c_proj.weight)]
+                copy for blk in txt.resblocks
+                for w in (blk.attn.in_proj_weight, blk.attn.out_proj.weight, blk.mlp.c_fc.weight, blk.mlp.c_proj.weight)
+                for copy in ((ops._converted(w, torch.float16), ops.transposed_half_weight(w)) if half else (ops.transposed_weight(w),))]
         self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
 
     def _reinstall(self):

@@ -230,11 +230,24 @@ class Transformer(nn.Module):
             self.__dict__["_causal_mask_check"] = cached = (key, ok)
         return cached[1]
 
-    def _row_gemm_weights_ok(self):
+    def _row_gemm_weights_ok(self, dtype=torch.float32):
         for blk in self.resblocks:
-            if not ops.gemm_rows_eligible(blk.mlp.c_proj.weight, blk.mlp.c_fc.weight, blk.attn.out_proj.weight, blk.attn.in_proj_weight):
+            if not ops.gemm_rows_eligible(blk.mlp.c_proj.weight, blk.mlp.c_fc.weight, blk.attn.out_proj.weight, blk.attn.in_proj_weight,
+                                          dtype=dtype):
                 return False
         return True
+
+    def _row_gemm_dtype(self, which):
+        """The GEMM dtype of the row-list route for ``which`` = ``"forward_gemm_dtype"`` / ``"backward_gemm_dtype"``: fp32, or fp16 for
+        the reference's half-precision body (``set_body_dtype(torch.float16)``: fp32 slabs, LayerNorms and attention around fp16 GEMMs,
+        which ``mmx_gemm_rows_f16`` runs on the list) when option ``text_live_rows_half`` is on; ``None``: the route is not offered
+        (bf16 bodies have a bf16 gradient stream and elementwise kernels of their own and stay dense)."""
+        dtype = getattr(self, which, torch.float32)
+        if dtype == torch.float32:
+            return dtype
+        if dtype == torch.float16 and self.capture_dtype == torch.float32 and ops.live_rows_half_enabled():
+            return dtype
+        return None
 
     def live_rows_for_forward(self, x, out_rows):
         """The row-list FORWARD (``forward_tape(live=...)``): under a causal mask row p of a sample depends on rows ``<= p`` of that
@@ -244,10 +257,10 @@ class Transformer(nn.Module):
         ``text_live_rows_fwd``.  Returns the ``ops.LiveRows`` of ``out_rows`` or ``None`` (dense forward)."""
         if out_rows is None or x.dim() != 3 or x.dtype != torch.float32 or x.shape[-1] % 4 or not x.is_cuda:
             return None
-        for what in ("forward_gemm_dtype", "backward_gemm_dtype", "capture_dtype"):
-            if getattr(self, what, torch.float32) != torch.float32:
-                return None
-        if self.layers < 1 or not ops.live_rows_forward_enabled() or not self.is_causal() or not self._row_gemm_weights_ok():
+        dtype = self._row_gemm_dtype("forward_gemm_dtype")       # fp32, or fp16 with option text_live_rows_half
+        if dtype is None or self._row_gemm_dtype("backward_gemm_dtype") != dtype or self.capture_dtype != torch.float32:
+            return None
+        if self.layers < 1 or not ops.live_rows_forward_enabled() or not self.is_causal() or not self._row_gemm_weights_ok(dtype):
             return None
         if x.shape[1] < self.resblocks[0].attn_mask.shape[-1]:
             # a trimmed text batch (``trim_text_padding``: the first max(eot) + 1 positions only) keeps the dense forward: most of its
@@ -296,9 +309,10 @@ class Transformer(nn.Module):
         top = self.layers - 1
         if dy_rows is None or dy_row_values is None or rel_row is not None or grouped or top <= first_grad_layer:
             return None
-        if getattr(self, "backward_gemm_dtype", torch.float32) != torch.float32 or dy_row_values.dtype != torch.float32:
+        dtype = self._row_gemm_dtype("backward_gemm_dtype")      # fp32, or fp16 with option text_live_rows_half
+        if dtype is None or dy_row_values.dtype != torch.float32:
             return None
-        if tape[top][0].shape[0] != B or E % 4 or not self.is_causal() or not self._row_gemm_weights_ok():
+        if tape[top][0].shape[0] != B or E % 4 or not self.is_causal() or not self._row_gemm_weights_ok(dtype):
             return None
         return ops.live_rows(dy_rows, N)
 
@@ -360,13 +374,14 @@ class Transformer(nn.Module):
         first = blocks[0].ln_1
         # bf16 body: what only feeds a GEMM (LayerNorm outputs, the MLP activation) leaves its kernel as bf16 -- no conversion passes
         hd = torch.bfloat16 if getattr(self, "forward_gemm_dtype", torch.float32) == torch.bfloat16 else torch.float32
+        gd = getattr(self, "forward_gemm_dtype", torch.float32)      # row-list route: the GEMM dtype of linear_rows (fp32 | fp16)
         _, h1, mean1, rstd1 = ln(x, None, first)
         for l, blk in enumerate(blocks):
             at = blk.attn
             if live is not None:
                 # (without live lengths in the attention: zeros, not LiveRows._out -- the dense attention reads every row of qkv)
                 qkv = ops.linear_rows(h1, at.in_proj_weight, at.in_proj_bias, live, out=None if live.attn else
-                                      torch.zeros(Bx, N, 3 * E, dtype=torch.float32, device=x.device))
+                                      torch.zeros(Bx, N, 3 * E, dtype=torch.float32, device=x.device), dtype=gd)
             else:
                 qkv = self._linear(h1, at.in_proj_weight, at.in_proj_bias)
             qkv = qkv.view(Bx, N, 3, at.num_heads, at.head_dim)
@@ -385,9 +400,10 @@ class Transformer(nn.Module):
                 blk.attn_probs, blk.attn_grad = buffers.layer_probs(l), buffers.layer_grads(l)
                 return x1 + mlp_out, tape
             if live is not None:
-                x1, h2, mean2, rstd2 = ln(x, ops.linear_rows(o.view(Bx, N, E), at.out_proj.weight, at.out_proj.bias, live), blk.ln_2)
-                m, act = ops.linear_rows(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, live, gelu=True)
-                mlp_out = ops.linear_rows(act, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, live)
+                x1, h2, mean2, rstd2 = ln(x, ops.linear_rows(o.view(Bx, N, E), at.out_proj.weight, at.out_proj.bias, live, dtype=gd),
+                                          blk.ln_2)
+                m, act = ops.linear_rows(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, live, gelu=True, dtype=gd)
+                mlp_out = ops.linear_rows(act, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, live, dtype=gd)
             else:
                 x1, h2, mean2, rstd2 = ln(x, self._linear(o.view(Bx, N, E), at.out_proj.weight, at.out_proj.bias), blk.ln_2)
                 m = self._linear(h2, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias)
@@ -542,6 +558,7 @@ class Transformer(nn.Module):
         # whole-head backward reads a bf16 d_o and writes bf16 dq | dk | dv around its exact-fp32 arithmetic (attention_head.hip, IOH;
         # round 4 -- before that two conversion passes per layer sat around it).
         stream16 = getattr(self, "backward_gemm_dtype", torch.float32) == torch.bfloat16
+        gd = getattr(self, "backward_gemm_dtype", torch.float32)     # row-list route: the GEMM dtype of gemm_rows (fp32 | fp16)
         head = self.resblocks[0].attn
         att16 = stream16 and (mma or (self.capture_dtype == torch.float32 and
                                       ops.head_kernel_shape(N, N, head.head_dim) and head.head_dim % 8 == 0))
@@ -581,11 +598,11 @@ class Transformer(nn.Module):
                 if att16:
                     d_o = d_o.to(torch.bfloat16)
             elif live is not None:
-                d_a = ops.gemm_rows(dx, blk.mlp.c_proj.weight, live)
+                d_a = ops.gemm_rows(dx, blk.mlp.c_proj.weight, live, dtype=gd)
                 d_m = ops.quick_gelu_bwd_rows(m, d_a, live)
-                d_h2 = ops.gemm_rows(d_m, blk.mlp.c_fc.weight, live)
+                d_h2 = ops.gemm_rows(d_m, blk.mlp.c_fc.weight, live, dtype=gd)
                 d_x1 = ops.layernorm_bwd_add_rows(d_h2, x1, mean2, rstd2, blk.ln_2.weight, dx, live)
-                d_o = ops.gemm_rows(d_x1, at.out_proj.weight, live, out=d_o_dense)
+                d_o = ops.gemm_rows(d_x1, at.out_proj.weight, live, out=d_o_dense, dtype=gd)
             elif stream16:
                 if dx_h is None:
                     dx_h = dx.to(torch.bfloat16)
@@ -625,7 +642,7 @@ class Transformer(nn.Module):
                 d_h1 = ops.backward_gemm_bf16(dq_in if att16 else dq_in.to(torch.bfloat16), at.in_proj_weight)
                 dx, dx_h = ops.layernorm_bwd_add_bf16(d_h1, x, mean1, rstd1, blk.ln_1.weight, d_x1)
             elif live is not None:
-                d_h1 = ops.gemm_rows(dqkv.view(B, N, 3 * E), at.in_proj_weight, live)
+                d_h1 = ops.gemm_rows(dqkv.view(B, N, 3 * E), at.in_proj_weight, live, dtype=gd)
                 dx = ops.layernorm_bwd_add_rows(d_h1, x, mean1, rstd1, blk.ln_1.weight, d_x1, live)
             else:
                 d_h1 = self._gemm(dqkv.view(B, N, 3 * E), at.in_proj_weight)

@@ -32,6 +32,7 @@ bool text_live_rows_option(const char* key, int value) {
     if (strcmp(key, "gemm_rows_tn") == 0 && (value == 0 || value == 32 || value == 64)) { g_gemm_rows_tn = value; return true; }
     return false;
 }
+int gemm_rows_tn_option() { return g_gemm_rows_tn; }
 
 // rows[0 .. count) = b * N + p for p <= clamp(eot[b], 0, N - 1), samples in order, positions in order; one workgroup.
 __global__ __launch_bounds__(256) void live_rows_kernel(const long long* __restrict__ eot, int B, int N, int* __restrict__ rows,

@@ -238,6 +238,8 @@ int chain_rows_layer_launch(const void* attn, const void* grad, const float* R_i
 bool bmm_f32_tiles_try(const float* A, const float* B, const float* Cin, float* C, int batch, int M, int N, int K, int trans_a,
                        int64_t sa, int64_t sb, int64_t sc, int nan_to_zero, int cin_is_row, hipStream_t s);
 bool text_live_rows_option(const char* key, int value);   // gemm_rows_f32.hip: options "text_live_rows", "text_live_rows_fwd", "gemm_rows_tm", "gemm_rows_tn"
+int gemm_rows_tn_option();                                 // gemm_rows_f32.hip: option "gemm_rows_tn" as set (0: from the shape)
+bool gemm_rows_half_option(const char* key, int value);   // gemm_rows_f16.hip: option "text_live_rows_half"
 int device_cu_count();   // compute units of the current device, cached
 int identity_async(float* R, int batch, int N, hipStream_t s);   // R[b] = I  (N x N, contiguous)
 

@@ -676,23 +676,47 @@ def _live_attn_check(what, live, B, Nq, Nk, probs):
                        % (what, live.batch, live.n_tokens, B, Nq, Nk, str(probs.dtype).replace("torch.", "")))
 
 
-def gemm_rows_eligible(*weights):
+def gemm_rows_eligible(*weights, dtype=torch.float32):
     """The eligibility rule of ``mmx_gemm_rows_f32`` for ``x @ weight``: fp32 contiguous 2-D weights, both widths multiples of 4
-    (16-byte rows), 16-byte aligned storage."""
-    return all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0
+    (16-byte rows), 16-byte aligned storage.  ``dtype=torch.float16`` (``mmx_gemm_rows_f16``, which reads a cached fp16 copy of the
+    same fp32 parameter): both widths multiples of 8 (16-byte rows of halves)."""
+    if dtype not in (torch.float32, torch.float16):
+        return False
+    m = 4 if dtype == torch.float32 else 8
+    return all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.shape[0] % m == 0 and w.shape[1] % m == 0
                and w.data_ptr() % 16 == 0 for w in weights)
 
 
-def gemm_rows(x, weight, live, out=None):
+def transposed_half_weight(weight):
+    """Cached fp16 copy of ``weight.t().contiguous()`` (beside ``transposed_weight``, until the parameter is modified in place): the
+    k-fastest operand ``mmx_gemm_rows_f16`` wants for the backward's ``x @ weight``.  The rounding is ``convert_weights``'
+    (CLIP/clip/model.py:381-402); transposing moves the rounded values, it does not change them."""
+    per_weight = _GEMM_WEIGHTS.get(id(weight))
+    if per_weight is None:
+        per_weight = _GEMM_WEIGHTS[id(weight)] = {}
+        weakref.finalize(weight, _GEMM_WEIGHTS.pop, id(weight), None)
+    hit = per_weight.get("t16")
+    if hit is None or hit[0] != weight._version or hit[1].device != weight.device:
+        hit = per_weight["t16"] = (weight._version, weight.detach().t().to(torch.float16).contiguous())
+    return hit[1]
+
+
+def gemm_rows(x, weight, live, out=None, dtype=torch.float32):
     """``out[r] = x[r] @ weight`` for the live rows ``r`` (``mmx_gemm_rows_f32``, exact fp32 on the MFMA); every other row of ``out``
-    is left alone.  ``x [B, N, K]``, ``weight [K, M]`` (an ``nn.Linear`` weight as stored), ``out [B, N, M]``."""
+    is left alone.  ``x [B, N, K]``, ``weight [K, M]`` (an ``nn.Linear`` weight as stored), ``out [B, N, M]``.
+    ``dtype=torch.float16`` (an fp16 body): ``mmx_gemm_rows_f16`` -- ``x`` rounded to fp16 inside the kernel, the cached fp16 copy of
+    ``weight.t()``, fp32 accumulation and an fp32 ``out``: the roundings of ``backward_gemm(x, weight, torch.float16)``."""
     _dev(x, weight, out)
     K, M = weight.shape
     if out is None:
         out = live._out(x, M)
     live._check("gemm_rows", x, out)
-    if x.shape[-1] != K or out.shape[-1] != M or not gemm_rows_eligible(weight):
-        raise MMXError("gemm_rows: x %s @ weight %s -> out %s" % (tuple(x.shape), tuple(weight.shape), tuple(out.shape)))
+    if x.shape[-1] != K or out.shape[-1] != M or not gemm_rows_eligible(weight, dtype=dtype):
+        raise MMXError("gemm_rows: x %s @ weight %s -> out %s (%s)" % (tuple(x.shape), tuple(weight.shape), tuple(out.shape), dtype))
+    if dtype == torch.float16:
+        check(lib().mmx_gemm_rows_f16(_p(x), _p(transposed_half_weight(weight)), _p(out), _p(live.rows), _p(live.count), live.cap, M, K,
+                                      _stream()), "mmx_gemm_rows_f16")
+        return out
     check(lib().mmx_gemm_rows_f32(_p(x), _p(weight), _p(out), _p(live.rows), _p(live.count), live.cap, M, K, _stream()),
           "mmx_gemm_rows_f32")
     return out
@@ -703,23 +727,37 @@ def live_rows_forward_enabled():
     return bool(lib().mmx_text_live_rows_fwd_enabled())
 
 
-def linear_rows(x, weight, bias, live, out=None, gelu=False, act_out=None):
+def live_rows_half_enabled():
+    """Options ``text_live_rows_half`` (default 0), ``text_live_rows`` and ``text_live_rows_fwd`` are all on: the text tower of an fp16
+    body may take the row list, its GEMMs on ``mmx_gemm_rows_f16`` / ``mmx_gemm_rows_bias_f16``."""
+    return bool(lib().mmx_text_live_rows_half_enabled())
+
+
+def linear_rows(x, weight, bias, live, out=None, gelu=False, act_out=None, dtype=torch.float32):
     """``out[r] = x[r] @ weight.t() + bias`` for the live rows ``r`` (``mmx_gemm_rows_bias_f32``: a forward ``nn.Linear`` on the tiles of
     ``gemm_rows``, fed with the cached ``transposed_weight``); every other row of ``out`` is left alone.  ``x [B, N, in]``, ``weight
     [out, in]``.  ``gelu``: returns ``(out, act)`` with ``act = QuickGELU(out)`` on the live rows, written by the same kernel -- the bits
-    ``quick_gelu_fwd(out)`` has there (``act_out``: the tensor to write it to)."""
+    ``quick_gelu_fwd(out)`` has there (``act_out``: the tensor to write it to).  ``dtype=torch.float16`` (an fp16 body):
+    ``mmx_gemm_rows_bias_f16`` -- ``x`` rounded to fp16 inside the kernel, the cached fp16 copy ``linear(..., torch.float16)`` uses (no
+    transposed copy), fp32 accumulation, fp32 bias and ``out``."""
     _dev(x, weight, bias, out, act_out)
     M, K = weight.shape
     if out is None:
         out = live._out(x, M)
     live._check("linear_rows", x, out)
-    if x.shape[-1] != K or out.shape[-1] != M or not gemm_rows_eligible(weight) or bias is None or bias.numel() != M:
-        raise MMXError("linear_rows: x %s @ weight %s^T + bias -> out %s" % (tuple(x.shape), tuple(weight.shape), tuple(out.shape)))
+    if x.shape[-1] != K or out.shape[-1] != M or not gemm_rows_eligible(weight, dtype=dtype) or bias is None or bias.numel() != M:
+        raise MMXError("linear_rows: x %s @ weight %s^T + bias -> out %s (%s)"
+                       % (tuple(x.shape), tuple(weight.shape), tuple(out.shape), dtype))
     act = (act_out if act_out is not None else live._out(x, M)) if gelu else None
     if act is not None:
         live._check("linear_rows", act)
         if act.shape[-1] != M or act.data_ptr() == out.data_ptr():
             raise MMXError("linear_rows: the activation needs a [.., %d] tensor of its own" % M)
+    if dtype == torch.float16:
+        check(lib().mmx_gemm_rows_bias_f16(_p(x), _p(_converted(weight, torch.float16).contiguous()), _p(_f32c(bias.detach())), _p(out),
+                                           _p(act), _p(live.rows), _p(live.count), live.cap, M, K, _stream()),
+              "mmx_gemm_rows_bias_f16")
+        return (out, act) if gelu else out
     check(lib().mmx_gemm_rows_bias_f32(_p(x), _p(transposed_weight(weight)), _p(_f32c(bias.detach())), _p(out), _p(act), _p(live.rows),
                                        _p(live.count), live.cap, M, K, _stream()), "mmx_gemm_rows_bias_f32")
     return (out, act) if gelu else out
