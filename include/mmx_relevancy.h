@@ -109,6 +109,8 @@ const char* mmx_last_error(void);
  *                        _bwd_live: no dead row of q / k / v is read, no zero fill of qkv) | 0: dense attention over a zero-filled qkv (A / B runs)
  *   "text_live_rows_half" 0 (default) an fp16 body (the reference's convert_weights mode) keeps the dense text tower | 1: it takes the row-list
  *                        route too, its GEMMs on mmx_gemm_rows_f16 / mmx_gemm_rows_bias_f16 (needs "text_live_rows" and "text_live_rows_fwd")
+ *   "clip_head_fused"    1 (default) CLIP interpret / interpret_grouped take the similarity head's gradients from mmx_clip_head_f32 (one
+ *                        launch) | 0: the autograd head over CLIP.logits (A / B runs; another rounding of the same formula)
  *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
  *   "gemm_rows_tn"       0 (default: chosen from N and K) | 32 | 64: columns per workgroup tile of mmx_gemm_rows_f32 at 32 rows (same
  *                        products, another order of the k sum; 64-row tiles are always 64 wide)
@@ -276,6 +278,22 @@ int mmx_gemm_rows_f16(const void* a_dev, const void* wh_dev, void* c_dev, const 
 int mmx_gemm_rows_bias_f16(const void* a_dev, const void* wh_dev, const void* bias_dev, void* c_dev, void* act_dev,
                            const void* rows_dev, const void* count_dev, int cap_rows, int N, int K, void* stream);
 int mmx_text_live_rows_half_enabled(void);
+
+/* CLIP's cosine-similarity head (CLIP/clip/model.py:369-378: normalise both features, logits_per_image = exp(logit_scale) * i^ . t^T)
+ * and the gradient of the caption notebook's scalar  sum_b logits_per_image[b, b]  (CLIP_explainability.ipynb cell 6:6-10) with
+ * respect to both un-normalised features, in closed form and ONE launch -- what the autograd head takes ~33 launches on B rows for.
+ * With i^ = i / |i|, t^ = t / |t|, c = i^ . t^, s = exp(logit_scale):
+ *     d_img[b] = s (t^_b - c_b i^) / |i|      d_txt[b] = s (i^ - c_b t^_b) / |t_b|      logit_diag[b] = s c_b
+ *   img_feat [Bi, D], txt_feat [B, D] fp32 contiguous; pair b reads image row 0 when Bi == 1 (one image for every caption), else row
+ *   b / img_group (Bi * img_group == B: img_group captions per image, caption-major as cell 6:3 repeats the images).
+ *   logit_scale: DEVICE address of the fp32 parameter (expf is applied in the kernel: no host read).
+ *   d_img [B, D], d_txt [B, D], logit_diag [B]: each may be NULL (not all three); none may alias a feature tensor.
+ *   1 <= D <= 4096, B >= 1.  One wave per pair, fixed summation order (two runs give the same bits), correctly rounded sqrt and
+ *   division, no atomics, no workspace.  MMX_EINVAL before any launch otherwise.
+ * mmx_clip_head_fused_enabled: option "clip_head_fused" (default 1). */
+int mmx_clip_head_f32(const void* img_feat_dev, const void* txt_feat_dev, const void* logit_scale_dev, void* d_img_dev,
+                      void* d_txt_dev, void* logit_diag_dev, int B, int D, int Bi, int img_group, void* stream);
+int mmx_clip_head_fused_enabled(void);
 
 /* The chain on VECTORS (rows-only DETR rules): when a caller returns single rows of R_q_i (`aggregated[:, target_index, :]`,
  * DETR/modules/ExplanationGenerator.py:180-182) the encoder product R_ii = (I + A_6) ... (I + A_1) (`:110-118`) is needed only

@@ -107,6 +107,8 @@ _PROTOTYPES = {
     "mmx_gemm_rows_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_gemm_rows_bias_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_text_live_rows_half_enabled": (_i, []),
+    "mmx_clip_head_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mmx_clip_head_fused_enabled": (_i, []),
     "mmx_chain_matvec": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mmx_chain_vecmat_workspace_bytes": (_sz, [_i, _i]),
     "mmx_chain_vecmat": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),

@@ -51,6 +51,31 @@ def _side_stream(device):
     return ops.side_stream(device)
 
 
+def _head_grads(model, img_feat, txt_feat, batch_size, img_group=1):
+    """``(d image_features, d text_features)`` of ``sum_i logits_per_image[i, i]`` (cell 6:6-10), one row per caption; caption i is
+    paired with image row 0 when ``img_feat`` holds one image, else with row ``i // img_group``.  fp32 features: ONE launch of the
+    closed form (``ops.clip_head_grads``; ``ops.set_option("clip_head_fused", 0)`` restores autograd, another rounding of the same
+    numbers).  Anything else: autograd over ``CLIP.logits`` on per-caption leaves, as the notebook does it."""
+    if (img_feat.dtype == torch.float32 and txt_feat.dtype == torch.float32 and img_feat.is_cuda and txt_feat.is_cuda
+            and model.logit_scale.dtype == torch.float32 and ops.clip_head_fused_enabled()):
+        d_img, d_txt, _ = ops.clip_head_grads(img_feat.detach().contiguous(), txt_feat.detach().contiguous(),
+                                              model.logit_scale.detach(), img_group)
+        return d_img, d_txt
+    with torch.enable_grad():
+        if img_feat.shape[0] == 1:
+            image_features = img_feat.detach().expand(batch_size, -1).contiguous().requires_grad_(True)   # per-sample leaves
+        elif img_group > 1:
+            image_features = img_feat.detach().repeat_interleave(img_group, 0).requires_grad_(True)       # cell 6:3
+        else:
+            image_features = img_feat.detach().contiguous().requires_grad_(True)
+        text_features = txt_feat.detach().requires_grad_(True)
+        logits_per_image, _ = model.logits(image_features, text_features)
+        # one_hot = sum_i logits_per_image[i, i]  (cell 6:6-10)  ->  d one_hot / d logits = I
+        eye = torch.eye(batch_size, dtype=torch.float32, device=txt_feat.device)
+        torch.autograd.backward(logits_per_image, grad_tensors=eye, inputs=[image_features, text_features])
+    return image_features.grad, text_features.grad
+
+
 def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, share_image_forward=True,
               trim_text_padding=False, _n_text=None, overlap_towers=True, image_chain_on_main=False):
     """CLIP_explainability.ipynb cell 6.  ``image``: ``[1,3,R,R]``, ``texts``: ``[B, context]`` token ids.
@@ -102,7 +127,7 @@ def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, 
         n_text = int(texts.argmax(dim=-1).max()) + 1                                      # one D2H read of the ids
     shared = share_image_forward and image.shape[0] == 1 and batch_size > 1
     # Both towers on the tape path (clip_model.Transformer.forward_tape / backward_tape): no autograd graph through the
-    # bodies, no weight gradients; only the cosine-similarity head (B x embed_dim features) goes through autograd.
+    # bodies, no weight gradients; the cosine-similarity head (B x embed_dim features) is one closed-form kernel (_head_grads).
     images = image.type(model.dtype) if shared or image.shape[0] == batch_size else \
         image.type(model.dtype).repeat(batch_size, 1, 1, 1)                                # cell 6:3
     # The two towers are independent up to the similarity head.  The image tower runs on a side stream: its shared
@@ -119,25 +144,19 @@ def interpret(image, texts, model, device, start_layer=-1, start_layer_text=-1, 
         img_feat, img_state = model.visual.forward_tape(images, batch_size, sl, grads=not row_mode)
     txt_feat, txt_state = model.encode_text_tape(texts, n_text, slt)
     main.wait_stream(side)
-    with torch.enable_grad():
-        image_features = img_feat.detach().expand(batch_size, -1).contiguous().requires_grad_(True)   # per-sample leaves
-        text_features = txt_feat.detach().requires_grad_(True)
-        logits_per_image, _ = model.logits(image_features, text_features)
-        # one_hot = sum_i logits_per_image[i, i]  (cell 6:6-10)  ->  d one_hot / d logits = I
-        eye = torch.eye(batch_size, dtype=torch.float32, device=texts.device)
-        torch.autograd.backward(logits_per_image, grad_tensors=eye, inputs=[image_features, text_features])
+    d_image_features, d_text_features = _head_grads(model, img_feat, txt_feat, batch_size)
     side.wait_stream(main)
     with torch.cuda.stream(side):
         vis = model.visual.transformer
         if row_mode:
-            image_relevance = model.visual.backward_tape(img_state, image_features.grad, sl, cls_row=True)[:, 1:]
+            image_relevance = model.visual.backward_tape(img_state, d_image_features, sl, cls_row=True)[:, 1:]
         else:
-            model.visual.backward_tape(img_state, image_features.grad, sl)
+            model.visual.backward_tape(img_state, d_image_features, sl)
             if not image_chain_on_main:
                 R = _plan(vis.buffers, sl, vis.layers, batch_size, vis.buffers.shared_probs and batch_size > 1,
                           getattr(vis, "half_chain", False)).launch()
                 image_relevance = R[:, 0, 1:]
-    model.backward_text_tape(txt_state, text_features.grad, slt)
+    model.backward_text_tape(txt_state, d_text_features, slt)
     txt = model.transformer
     R_text = _plan(txt.buffers, slt, txt.layers, batch_size, False, getattr(txt, "half_chain", False),
                    causal=_is_causal_tower(txt)).launch()
@@ -354,18 +373,13 @@ def interpret_grouped(images, texts, model, device, start_layer=-1, start_layer_
     slt = model.transformer.layers - 1 if start_layer_text == -1 else start_layer_text
     img_feat, img_state = model.visual.forward_tape(images.type(model.dtype), None, sl, grads=False)
     txt_feat, txt_state = model.encode_text_tape(texts, None, slt)
-    with torch.enable_grad():
-        # caption order: leaf row i holds image i // K (the reference's repeated images, cell 6:3)
-        image_features = img_feat.detach().repeat_interleave(K, 0).requires_grad_(True)
-        text_features = txt_feat.detach().requires_grad_(True)
-        logits_per_image, _ = model.logits(image_features, text_features)
-        eye = torch.eye(T, dtype=torch.float32, device=texts.device)           # one_hot = sum_i logits_per_image[i, i]
-        torch.autograd.backward(logits_per_image, grad_tensors=eye, inputs=[image_features, text_features])
+    # caption order: row i of both gradients belongs to caption i, paired with image i // K (the reference's repeated images, cell 6:3)
+    d_image_features, d_text_features = _head_grads(model, img_feat, txt_feat, T, img_group=K)
     # caption m*K + k -> target k*M + m (K-major, what the grouped backward addresses)
-    d_img = _k_major_rows(image_features.grad, M, K).reshape(T, -1)
+    d_img = _k_major_rows(d_image_features, M, K).reshape(T, -1)
     row = model.visual.backward_tape(img_state, d_img, sl, cls_row=True, targets_per_image=K)
     image_relevance = _k_major_rows(row, K, M).reshape(T, -1)[:, 1:]
-    model.backward_text_tape(txt_state, text_features.grad, slt)
+    model.backward_text_tape(txt_state, d_text_features, slt)
     txt = model.transformer
     R_text = _plan(txt.buffers, slt, txt.layers, T, False, getattr(txt, "half_chain", False),
                    causal=_is_causal_tower(txt)).launch()

@@ -517,8 +517,8 @@ class Transformer(nn.Module):
         ``row <- row + row . mean_h clamp(dP * P, 0)``, reduced inside the attention backward kernel.  No gradient slab is
         written, no A-bar / R matrix is formed; the final row is returned.
 
-        ``dy_rows`` (``[B]`` long, optional): promise that ``dy`` is zero outside row ``dy_rows[b]`` of sample ``b`` -- both
-        CLIP towers read their feature from ONE token (class token / EOT token).  The top block's MLP and ``out_proj``
+        ``dy_rows`` (``[B]`` long, or an int for the same row of every sample; optional): promise that ``dy`` is zero outside row
+        ``dy_rows[b]`` of sample ``b`` -- both CLIP towers read their feature from ONE token (class token / EOT token).  The top block's MLP and ``out_proj``
         vector-Jacobian products are row-wise, so they then run on those B rows instead of B*N (3 of the 4 GEMMs of
         that block); below the top block's attention the gradient is dense and everything runs in full.
         ``dy_row_values`` (``[B, E]``, with ``dy_rows``): those rows themselves -- ``dy`` may then be ``None`` (no dense zero
@@ -537,6 +537,9 @@ class Transformer(nn.Module):
         ``targets_per_image=K`` (fp32 body, row mode only): the tape holds M distinct samples and the B = K*M upstream gradients
         are K per sample in K-major order (target t explains sample t % M).  The elementwise steps broadcast the per-sample
         activations (modulo kernels); the capture op runs its grouped row mode (``ops.attn_capture_bwd(images=M)``)."""
+        if isinstance(dy_rows, int):          # the same row of every sample (a ViT's class token): a kept constant, no fill launch
+            ref = dy_row_values if dy_row_values is not None else dy
+            dy_rows = ops.const_rows(ref.shape[0], dy_rows, ref.device)
         if dy is None:
             if dy_rows is None or dy_row_values is None:
                 raise ValueError("backward_tape: dy=None needs dy_rows and dy_row_values")
@@ -660,13 +663,15 @@ class Transformer(nn.Module):
         ``images``: grouped mode, target b reads sample b % images of the tape."""
         x, mean1, rstd1, qkv, x1, mean2, rstd2, m, o_fwd = entry[:9]
         B = g.shape[0]
-        ar = torch.arange(B, device=g.device)
-        src = torch.zeros_like(rows) if shared else ar                     # sample index into the (shared) tape
-        if images is not None:
-            src = ar % images
         if len(entry) > 9:                                                   # forward_tape(out_rows=...): rows only on the tape
-            m_r, x1_r, mean2_r, rstd2_r = m[src], x1[src], mean2.reshape(-1)[src], rstd2.reshape(-1)[src]
-        else:
+            # [Bx, .] rows, Bx = B (one input per gradient), 1 (shared forward) or ``images`` (grouped, target t reads sample t % Bx):
+            # quick_gelu_bwd and layernorm_bwd_add broadcast a batch-1 / batch-M operand themselves -- no index, no copy
+            m_r, x1_r, mean2_r, rstd2_r = m, x1, mean2.reshape(-1), rstd2.reshape(-1)
+        else:                                                                # full [Bx, N, .] tensors: the row differs per sample
+            ar = torch.arange(B, device=g.device)
+            src = torch.zeros_like(rows) if shared else ar                   # sample index into the (shared) tape
+            if images is not None:
+                src = ar % images
             flat = src * N + rows                                            # row of the [Bx*N] statistics
             m_r, x1_r, mean2_r, rstd2_r = m[src, rows], x1[src, rows], mean2.reshape(-1)[flat], rstd2.reshape(-1)[flat]
         d_a = self._gemm(g, blk.mlp.c_proj.weight)
@@ -790,7 +795,7 @@ class VisualTransformer(nn.Module):
             rel_row = torch.zeros(B, y_shape[1], dtype=torch.float32, device=d_f.device)
             rel_row[:, 0] = 1.0                                              # e_0: row 0 of the identity R starts from
         return self.transformer.backward_tape(tape, None, first_grad_layer,
-                                              dy_rows=torch.zeros(B, dtype=torch.long, device=d_f.device), rel_row=rel_row,
+                                              dy_rows=0, rel_row=rel_row,
                                               dy_row_values=d_cls, targets_per_image=targets_per_image)
 
     def backward_shared(self, state, d_features, first_grad_layer=0):

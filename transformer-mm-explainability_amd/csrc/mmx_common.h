@@ -240,6 +240,7 @@ bool bmm_f32_tiles_try(const float* A, const float* B, const float* Cin, float* 
 bool text_live_rows_option(const char* key, int value);   // gemm_rows_f32.hip: options "text_live_rows", "text_live_rows_fwd", "gemm_rows_tm", "gemm_rows_tn"
 int gemm_rows_tn_option();                                 // gemm_rows_f32.hip: option "gemm_rows_tn" as set (0: from the shape)
 bool gemm_rows_half_option(const char* key, int value);   // gemm_rows_f16.hip: option "text_live_rows_half"
+bool clip_head_option(const char* key, int value);        // clip_head.hip: option "clip_head_fused"
 int device_cu_count();   // compute units of the current device, cached
 int identity_async(float* R, int batch, int N, hipStream_t s);   // R[b] = I  (N x N, contiguous)
 

@@ -1023,6 +1023,7 @@ extern "C" int mmx_set_option(const char* key, int value) {
     if (key && text_live_rows_option(key, value)) return MMX_OK;
     if (key && gemm_rows_half_option(key, value)) return MMX_OK;
     if (key && attn_head_live_option(key, value)) return MMX_OK;
+    if (key && clip_head_option(key, value)) return MMX_OK;
     if (key && strcmp(key, "self_chain_nt") == 0 && value >= 0 && value <= 1) {
         g_chain_nt = value;
         return MMX_OK;

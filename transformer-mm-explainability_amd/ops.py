@@ -624,6 +624,54 @@ def rows_add_(dense, rows, vals):
     return dense
 
 
+def clip_head_fused_enabled():
+    """Option ``clip_head_fused`` (default 1): CLIP ``interpret`` / ``interpret_grouped`` take the similarity head's gradients from
+    ``clip_head_grads``; 0 restores the autograd head over ``CLIP.logits``."""
+    return bool(lib().mmx_clip_head_fused_enabled())
+
+
+def clip_head_grads(img_feat, txt_feat, logit_scale, img_group=1, want_img=True, want_txt=True, want_diag=False):
+    """Gradients of ``sum_b logits_per_image[b, b]`` (CLIP_explainability.ipynb cell 6:6-10; ``CLIP.logits``, CLIP/clip/model.py:369-378)
+    with respect to the un-normalised features, in ONE launch (``mmx_clip_head_f32``) -> ``(d_img [B, D], d_txt [B, D], logit_diag [B])``,
+    ``None`` where not wanted.  ``img_feat [Bi, D]``: pair b reads row 0 when ``Bi == 1``, else row ``b // img_group``
+    (``Bi * img_group == B``); ``txt_feat [B, D]``; ``logit_scale``: the fp32 parameter itself, on the device (its ``exp`` is taken
+    in the kernel)."""
+    _dev(img_feat, txt_feat, logit_scale)
+    for name, t in (("img_feat", img_feat), ("txt_feat", txt_feat)):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise MMXError("clip_head_grads: %s must be fp32 contiguous [rows, D], got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if logit_scale.dtype != torch.float32 or logit_scale.numel() != 1:
+        raise MMXError("clip_head_grads: logit_scale must be one fp32 value on the device")
+    if img_feat.shape[1] != txt_feat.shape[1]:
+        raise MMXError("clip_head_grads: img_feat %s vs txt_feat %s" % (tuple(img_feat.shape), tuple(txt_feat.shape)))
+    B, D = txt_feat.shape
+    d_img = torch.empty_like(txt_feat) if want_img else None
+    d_txt = torch.empty_like(txt_feat) if want_txt else None
+    diag = torch.empty(B, dtype=torch.float32, device=txt_feat.device) if want_diag else None
+    check(lib().mmx_clip_head_f32(_p(img_feat), _p(txt_feat), _p(logit_scale), _p(d_img), _p(d_txt), _p(diag), B, D,
+                                  img_feat.shape[0], int(img_group), _stream()), "mmx_clip_head_f32")
+    return d_img, d_txt, diag
+
+
+_const_rows = {}
+
+
+def const_rows(batch, row, device):
+    """``[batch]`` long tensor holding ``row`` everywhere -- "the same token of every sample" (a ViT's class token) for ``rows_to_dense``
+    / ``rows_add_``.  A constant: built once per (device, batch, row) and kept, so no fill launch sits in a step (or in its hipGraph).
+    Built and waited for on the stream of the first call, so every later stream may read it; a first call inside a stream capture
+    gets a tensor of the capture's own (not kept)."""
+    key = (str(device), int(batch), int(row))
+    t = _const_rows.get(key)
+    if t is None:
+        t = torch.full((int(batch),), int(row), dtype=torch.long, device=device)
+        if torch.cuda.is_current_stream_capturing():
+            return t
+        torch.cuda.current_stream().synchronize()
+        _const_rows[key] = t
+    return t
+
+
 class LiveRows:
     """Device-side list of the live rows of a ``[B, N, *]`` gradient stream (``live_rows``): ``rows`` int32 ``[B * N]`` (the first
     ``count[0]`` entries are valid), ``count`` int32 ``[1]``; ``eot`` int64 ``[B]``: the last live position of every sample, what the list was
