@@ -754,7 +754,8 @@ int mmx_quick_gelu_bwd_bcast(const void* x_dev, const void* dy_dev, void* dx_dev
 
 /* LayerNorm input gradient + residual add with forward statistics shared by the batch (shared-forward backward of the
  * CLIP image tower / ViT): dx[r] = d_res[r] + LN'(dy[r]; x[r % x_rows], mean, rstd, gamma).  dy, d_res (may be NULL),
- * dx: [rows, E]; x: [x_rows, E]; mean, rstd: [x_rows]; gamma: [E]; fp32 contiguous, E % 4 == 0. */
+ * dx: [rows, E]; x: [x_rows, E]; mean, rstd: [x_rows]; gamma: [E]; fp32 contiguous, E % 4 == 0; dy, x, gamma, d_res and dx
+ * 16-byte aligned (MMX_EINVAL otherwise; the row-list form mmx_layernorm_bwd_add_rows asks the same). */
 int mmx_layernorm_bwd_add(const void* dy_dev, const void* x_dev, const void* mean_dev, const void* rstd_dev,
                           const void* gamma_dev, const void* d_res_dev, void* dx_dev, int64_t rows, int x_rows, int E,
                           void* stream);
@@ -762,7 +763,8 @@ int mmx_layernorm_bwd_add(const void* dy_dev, const void* x_dev, const void* mea
 /* Residual add fused with the LayerNorm that follows it in a pre-LN block (CLIP/clip/model.py:195-197: x = x + attn(...);
  * ... ln_2(x)): sum = x + y (written to sum_dev: the next residual), h = LayerNorm(sum) * gamma + beta, and the row
  * statistics mean / rstd that mmx_layernorm_bwd_add consumes.  y_dev == NULL: plain LayerNorm of x (sum_dev unused).
- * x, y, sum, h: [rows, E]; mean, rstd: [rows]; gamma, beta: [E]; fp32 contiguous, E % 4 == 0, E <= 4096. */
+ * x, y, sum, h: [rows, E]; mean, rstd: [rows]; gamma, beta: [E]; fp32 contiguous, E % 4 == 0, E <= 4096; x, y, gamma, beta, sum
+ * and h 16-byte aligned (a bf16 h: 8-byte; MMX_EINVAL otherwise; mmx_add_layernorm_fwd_rows asks the same). */
 int mmx_add_layernorm_fwd(const void* x_dev, const void* y_dev, const void* gamma_dev, const void* beta_dev,
                           void* sum_dev, void* h_dev, void* mean_dev, void* rstd_dev, int64_t rows, int E, float eps,
                           void* stream);

@@ -76,6 +76,12 @@ __global__ __launch_bounds__(256) void quick_gelu_bwd_kernel(const f32x4* __rest
 
 using namespace mmx;
 
+// every pointer a kernel takes 16-byte groups through (a null one, an optional operand, passes)
+template <typename... P>
+static bool aligned16(P... ptrs) {
+    return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & 15u) == 0;
+}
+
 static int gelu_grid(int64_t n4) {
     const int64_t blocks = (n4 + 255) / 256;
     return static_cast<int>(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks));
@@ -201,6 +207,8 @@ extern "C" int mmx_layernorm_bwd_add(const void* dy_dev, const void* x_dev, cons
     MMX_CHECK_ARG(dy_dev && x_dev && mean_dev && rstd_dev && gamma_dev && dx_dev, "mmx_layernorm_bwd_add: null pointer");
     MMX_CHECK_ARG(rows > 0 && x_rows > 0 && E > 0 && E % 4 == 0, "mmx_layernorm_bwd_add: rows=%ld x_rows=%d E=%d (E %% 4 must be 0)",
                   static_cast<long>(rows), x_rows, E);
+    MMX_CHECK_ARG(aligned16(dy_dev, x_dev, gamma_dev, d_res_dev, dx_dev),
+                  "mmx_layernorm_bwd_add: dy, x, gamma, d_res and dx must be 16-byte aligned");
     mmx::layernorm_bwd_add_kernel<false><<<static_cast<unsigned>((rows + 3) / 4), 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const float*>(dy_dev), static_cast<const float*>(x_dev), static_cast<const float*>(mean_dev),
         static_cast<const float*>(rstd_dev), static_cast<const float*>(gamma_dev), static_cast<const float*>(d_res_dev),
@@ -216,6 +224,8 @@ extern "C" int mmx_layernorm_bwd_add_rows(const void* dy_dev, const void* x_dev,
     MMX_CHECK_ARG(dy_dev && x_dev && mean_dev && rstd_dev && gamma_dev && dx_dev && rows_dev && count_dev,
                   "mmx_layernorm_bwd_add_rows: null pointer");
     MMX_CHECK_ARG(cap_rows > 0 && E > 0 && E % 4 == 0, "mmx_layernorm_bwd_add_rows: cap_rows=%d E=%d (E %% 4 must be 0)", cap_rows, E);
+    MMX_CHECK_ARG(aligned16(dy_dev, x_dev, gamma_dev, d_res_dev, dx_dev),
+                  "mmx_layernorm_bwd_add_rows: dy, x, gamma, d_res and dx must be 16-byte aligned");
     mmx::layernorm_bwd_add_kernel<true><<<static_cast<unsigned>((cap_rows + 3) / 4), 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const float*>(dy_dev), static_cast<const float*>(x_dev), static_cast<const float*>(mean_dev),
         static_cast<const float*>(rstd_dev), static_cast<const float*>(gamma_dev), static_cast<const float*>(d_res_dev),
@@ -308,6 +318,9 @@ extern "C" int mmx_add_layernorm_fwd_ex(const void* x_dev, const void* y_dev, co
     MMX_CHECK_ARG(rows > 0 && E > 0 && E % 4 == 0 && E <= 4096, "mmx_add_layernorm_fwd: rows=%ld E=%d (E %% 4 == 0, E <= 4096)",
                   static_cast<long>(rows), E);
     MMX_CHECK_ARG(h_dtype == MMX_F32 || h_dtype == MMX_BF16, "mmx_add_layernorm_fwd: h is fp32 or bf16");
+    MMX_CHECK_ARG(aligned16(x_dev, y_dev, gamma_dev, beta_dev, sum_dev) &&
+                      (reinterpret_cast<uintptr_t>(h_dev) & (h_dtype == MMX_BF16 ? 7u : 15u)) == 0,
+                  "mmx_add_layernorm_fwd: x, y, gamma, beta, sum and an fp32 h must be 16-byte aligned, a bf16 h 8-byte");
     const unsigned grid = static_cast<unsigned>((rows + 3) / 4);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float *x = static_cast<const float*>(x_dev), *y = static_cast<const float*>(y_dev);
@@ -333,6 +346,8 @@ extern "C" int mmx_add_layernorm_fwd_rows(const void* x_dev, const void* y_dev, 
     MMX_CHECK_ARG(!y_dev || sum_dev, "mmx_add_layernorm_fwd_rows: the sum x + y needs an output buffer");
     MMX_CHECK_ARG(cap_rows > 0 && E > 0 && E % 4 == 0 && E <= 4096, "mmx_add_layernorm_fwd_rows: cap_rows=%d E=%d (E %% 4 == 0, E <= 4096)",
                   cap_rows, E);
+    MMX_CHECK_ARG(aligned16(x_dev, y_dev, gamma_dev, beta_dev, sum_dev, h_dev),
+                  "mmx_add_layernorm_fwd_rows: x, y, gamma, beta, sum and h must be 16-byte aligned");
     const unsigned grid = static_cast<unsigned>((cap_rows + 3) / 4);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float *x = static_cast<const float*>(x_dev), *y = static_cast<const float*>(y_dev);

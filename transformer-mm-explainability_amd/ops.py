@@ -270,13 +270,16 @@ def quick_gelu_fwd(x, out_dtype=torch.float32):
     (a bf16 body: the activation only feeds the next GEMM): the kernel writes bf16, no conversion pass."""
     _dev(x)
     x = _f32c(x)
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise MMXError("quick_gelu_fwd: out_dtype is fp32 or bf16, got %s" % out_dtype)
     if out_dtype == torch.bfloat16 and x.numel() % 4 == 0:
         y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
         check(lib().mmx_quick_gelu_fwd_bf16(_p(x), _p(y), x.numel(), _stream()), "mmx_quick_gelu_fwd_bf16")
         return y
     y = torch.empty_like(x)
     check(lib().mmx_quick_gelu_fwd(_p(x), _p(y), x.numel(), _stream()), "mmx_quick_gelu_fwd")
-    return y
+    # (the bf16 kernel packs four elements a store; any other count takes the fp32 kernel, whose result is rounded once)
+    return y if out_dtype == torch.float32 else y.to(torch.bfloat16)
 
 
 def quick_gelu_bwd(x, dy):
@@ -305,6 +308,23 @@ def quick_gelu_bwd(x, dy):
     return dx
 
 
+def _affine(what, E, *vectors):
+    """The per-feature operands of a LayerNorm kernel (``gamma``, ``beta``) as fp32 contiguous tensors; the kernel reads ``E`` floats of each."""
+    out = []
+    for t in vectors:
+        if t.numel() != E:
+            raise MMXError("%s: a row has %d elements, gamma / beta %d" % (what, E, t.numel()))
+        out.append(_f32c(t))
+    return out
+
+
+def _row_stats(what, x_rows, mean, rstd):
+    """``mean`` / ``rstd`` of a LayerNorm backward as fp32 contiguous tensors; the kernel reads one of each per row of ``x``."""
+    if mean.numel() != x_rows or rstd.numel() != x_rows:
+        raise MMXError("%s: %d / %d statistics (mean / rstd) for the %d rows of x" % (what, mean.numel(), rstd.numel(), x_rows))
+    return _f32c(mean), _f32c(rstd)
+
+
 def add_layernorm(x, y, gamma, beta, eps=1e-5, h_dtype=torch.float32):
     """``s = x + y; h = LayerNorm(s)`` in one pass -> ``(s, h, mean, rstd)`` (``y=None``: ``s`` is ``x`` itself).
     ``mean`` / ``rstd``: ``[rows]`` fp32, what ``layernorm_bwd_add`` takes.  ``h_dtype=torch.bfloat16``: ``h`` leaves the kernel
@@ -317,11 +337,12 @@ def add_layernorm(x, y, gamma, beta, eps=1e-5, h_dtype=torch.float32):
         y = _f32c(y)
         if y.shape != x.shape:
             raise MMXError("add_layernorm: x %s vs y %s" % (tuple(x.shape), tuple(y.shape)))
+    gamma, beta = _affine("add_layernorm", E, gamma, beta)
     s = torch.empty_like(x) if y is not None else x
     h = torch.empty(x.shape, dtype=h_dtype, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    check(lib().mmx_add_layernorm_fwd_ex(_p(x), _p(y), _p(_f32c(gamma)), _p(_f32c(beta)), _p(s) if y is not None else _p(None),
+    check(lib().mmx_add_layernorm_fwd_ex(_p(x), _p(y), _p(gamma), _p(beta), _p(s) if y is not None else _p(None),
                                          _p(h), _p(mean), _p(rstd), rows, E, float(eps), _DTYPES[h_dtype], _stream()),
           "mmx_add_layernorm_fwd")
     return s, h, mean, rstd
@@ -334,8 +355,10 @@ def layernorm_bwd_add(dy, x, mean, rstd, gamma, d_res=None):
     dy, x = _f32c(dy), _f32c(x)
     E = dy.shape[-1]
     rows, x_rows = dy.numel() // E, x.numel() // E
+    mean, rstd = _row_stats("layernorm_bwd_add", x_rows, mean, rstd)
+    (gamma,) = _affine("layernorm_bwd_add", E, gamma)
     dx = torch.empty_like(dy)
-    check(lib().mmx_layernorm_bwd_add(_p(dy), _p(x), _p(_f32c(mean)), _p(_f32c(rstd)), _p(_f32c(gamma)),
+    check(lib().mmx_layernorm_bwd_add(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma),
                                       _p(_f32c(d_res)) if d_res is not None else _p(None), _p(dx), rows, x_rows, E,
                                       _stream()), "mmx_layernorm_bwd_add")
     return dx
@@ -352,7 +375,9 @@ def layernorm_bwd_add_bf16(dy, x, mean, rstd, gamma, d_res=None, want_f32=True):
     rows, x_rows = dy.numel() // E, x.numel() // E
     dx = torch.empty(dy.shape, dtype=torch.float32, device=dy.device) if want_f32 else None
     dx_h = torch.empty_like(dy)
-    check(lib().mmx_layernorm_bwd_add_bf16(_p(dy), _p(x), _p(_f32c(mean)), _p(_f32c(rstd)), _p(_f32c(gamma)),
+    mean, rstd = _row_stats("layernorm_bwd_add_bf16", x_rows, mean, rstd)
+    (gamma,) = _affine("layernorm_bwd_add_bf16", E, gamma)
+    check(lib().mmx_layernorm_bwd_add_bf16(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma),
                                            _p(_f32c(d_res)) if d_res is not None else _p(None), _p(dx), _p(dx_h), rows,
                                            x_rows, E, _stream()), "mmx_layernorm_bwd_add_bf16")
     return dx, dx_h
@@ -817,6 +842,7 @@ def add_layernorm_rows(x, y, gamma, beta, eps, live, out=None):
     _dev(x, y, gamma, beta)
     live._check("add_layernorm_rows", x, *([y] if y is not None else []))
     E = x.shape[-1]
+    gamma, beta = _affine("add_layernorm_rows", E, gamma, beta)
     if out is not None:
         s, h, mean, rstd = out
         _dev(s, h, mean, rstd)
@@ -829,7 +855,7 @@ def add_layernorm_rows(x, y, gamma, beta, eps, live, out=None):
         s = live._out(x, E) if y is not None else x
         h = live._out(x, E)
         mean, rstd = live._out(x, 1).view(-1), live._out(x, 1).view(-1)
-    check(lib().mmx_add_layernorm_fwd_rows(_p(x), _p(y), _p(_f32c(gamma)), _p(_f32c(beta)), _p(s) if y is not None else _p(None), _p(h),
+    check(lib().mmx_add_layernorm_fwd_rows(_p(x), _p(y), _p(gamma), _p(beta), _p(s) if y is not None else _p(None), _p(h),
                                            _p(mean), _p(rstd), _p(live.rows), _p(live.count), live.cap, E, float(eps), _stream()),
           "mmx_add_layernorm_fwd_rows")
     return s, h, mean, rstd
@@ -855,15 +881,14 @@ def layernorm_bwd_add_rows(dy, x, mean, rstd, gamma, d_res, live, out=None):
     ``out``: an fp32 contiguous tensor of ``dy``'s shape to write to."""
     _dev(dy, x, mean, rstd, gamma, d_res, out)
     live._check("layernorm_bwd_add_rows", dy, x, *([d_res] if d_res is not None else []))
-    mean, rstd = _f32c(mean), _f32c(rstd)
-    if mean.numel() != live.cap or rstd.numel() != live.cap:
-        raise MMXError("layernorm_bwd_add_rows: %d statistics for %d rows" % (mean.numel(), live.cap))
+    mean, rstd = _row_stats("layernorm_bwd_add_rows", live.cap, mean, rstd)
+    (gamma,) = _affine("layernorm_bwd_add_rows", dy.shape[-1], gamma)
     dx = out if out is not None else live._out(dy, dy.shape[-1])
     if out is not None:
         live._check("layernorm_bwd_add_rows", out)
         if out.shape != dy.shape:
             raise MMXError("layernorm_bwd_add_rows: dy %s -> out %s" % (tuple(dy.shape), tuple(out.shape)))
-    check(lib().mmx_layernorm_bwd_add_rows(_p(dy), _p(x), _p(mean), _p(rstd), _p(_f32c(gamma)), _p(d_res), _p(dx), _p(live.rows),
+    check(lib().mmx_layernorm_bwd_add_rows(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(d_res), _p(dx), _p(live.rows),
                                            _p(live.count), live.cap, dy.shape[-1], _stream()), "mmx_layernorm_bwd_add_rows")
     return dx
 
