@@ -213,7 +213,9 @@ int mmx_linear_f32(const void* x_dev, const void* wt_dev, const void* bias_dev, 
 
 /* One row per sample <-> a dense [B, N, E] fp32 tensor (the top block of a CLIP tower carries a gradient on ONE token per sample,
  * the class / EOT token: CLIP/clip/model.py:235, 360):  mmx_rows_to_dense: out[b, n, :] = (n == rows[b]) ? vals[b, :] : 0;
- * mmx_rows_add: dense[b, rows[b], :] += vals[b, :].  rows: int64 [B] (0 <= rows[b] < N), vals [B, E], E % 4 == 0, 16-byte aligned. */
+ * mmx_rows_add: dense[b, rows[b], :] += vals[b, :].  rows: int64 [B], vals [B, E], E % 4 == 0.  A rows[b] outside [0, N) names no row:
+ * sample b of out is all zero / sample b of dense is left as it is (nothing is read or written out of bounds).  vals and out / dense
+ * 16-byte aligned, rows 8-byte (MMX_EINVAL otherwise: there is no misaligned route). */
 int mmx_rows_to_dense(const void* vals_dev, const void* rows_dev, void* out_dev, int B, int N, int E, void* stream);
 int mmx_rows_add(void* dense_dev, const void* rows_dev, const void* vals_dev, int B, int N, int E, void* stream);
 
@@ -745,7 +747,9 @@ int mmx_quick_gelu_bwd(const void* x_dev, const void* dy_dev, void* dx_dev, int6
  * the shared-forward backward has ONE activation tensor for B upstream gradients. */
 /* bf16 gradient stream (BASELINE config 5's bf16 body): dy / dx bf16, x fp32 (broadcast over the batch as above; x_n % 8 == 0);
  * LayerNorm backward + residual with a bf16 upstream gradient, written as fp32 (`dx_dev`, the next residual) and / or bf16
- * (`dx_bf16_dev`, the next GEMM's operand) -- either may be NULL. */
+ * (`dx_bf16_dev`, the next GEMM's operand) -- either may be NULL.  Shapes as mmx_layernorm_bwd_add below; x, gamma, d_res and dx
+ * 16-byte aligned, the bf16 dy and dx_bf16 8-byte (MMX_EINVAL otherwise: there is no misaligned route, every kernel behind this entry
+ * takes 8- and 16-byte groups). */
 int mmx_quick_gelu_bwd_bcast_bf16(const void* x_dev, const void* dy_dev, void* dx_dev, int64_t n, int64_t x_n, void* stream);
 int mmx_layernorm_bwd_add_bf16(const void* dy_dev, const void* x_dev, const void* mean_dev, const void* rstd_dev,
                                const void* gamma_dev, const void* d_res_dev, void* dx_dev, void* dx_bf16_dev,

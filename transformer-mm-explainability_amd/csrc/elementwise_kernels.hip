@@ -578,6 +578,8 @@ __global__ __launch_bounds__(256) void rows_add_kernel(f32x4* __restrict__ dense
 extern "C" int mmx_rows_to_dense(const void* vals_dev, const void* rows_dev, void* out_dev, int B, int N, int E, void* stream) {
     MMX_CHECK_ARG(vals_dev && rows_dev && out_dev && B > 0 && N > 0 && E > 0 && E % 4 == 0 && B <= 65535,
                   "mmx_rows_to_dense: bad argument (B=%d N=%d E=%d, E %% 4 must be 0)", B, N, E);
+    MMX_CHECK_ARG(aligned16(vals_dev, out_dev) && (reinterpret_cast<uintptr_t>(rows_dev) & 7u) == 0,
+                  "mmx_rows_to_dense: vals and out must be 16-byte aligned, the int64 rows 8-byte");
     const int64_t per = static_cast<int64_t>(N) * (E / 4);
     const dim3 grid(static_cast<unsigned>(per / 256 + 1 > 64 ? 64 : per / 256 + 1), B);
     mmx::rows_to_dense_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(
@@ -589,6 +591,8 @@ extern "C" int mmx_rows_to_dense(const void* vals_dev, const void* rows_dev, voi
 extern "C" int mmx_rows_add(void* dense_dev, const void* rows_dev, const void* vals_dev, int B, int N, int E, void* stream) {
     MMX_CHECK_ARG(dense_dev && rows_dev && vals_dev && B > 0 && N > 0 && E > 0 && E % 4 == 0 && B <= 65535,
                   "mmx_rows_add: bad argument (B=%d N=%d E=%d, E %% 4 must be 0)", B, N, E);
+    MMX_CHECK_ARG(aligned16(dense_dev, vals_dev) && (reinterpret_cast<uintptr_t>(rows_dev) & 7u) == 0,
+                  "mmx_rows_add: dense and vals must be 16-byte aligned, the int64 rows 8-byte");
     mmx::rows_add_kernel<<<dim3((E / 4 + 255) / 256, B), 256, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<f32x4*>(dense_dev), static_cast<const long long*>(rows_dev), static_cast<const f32x4*>(vals_dev), N, E / 4);
     MMX_LAUNCH_CHECK("rows_add_kernel");
@@ -624,11 +628,12 @@ extern "C" int mmx_layernorm_bwd_add_bf16(const void* dy_dev, const void* x_dev,
                   "mmx_layernorm_bwd_add_bf16: null pointer");
     MMX_CHECK_ARG(rows > 0 && x_rows > 0 && E > 0 && E % 4 == 0, "mmx_layernorm_bwd_add_bf16: rows=%ld x_rows=%d E=%d (E %% 4 must be 0)",
                   static_cast<long>(rows), x_rows, E);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(dy_dev) | reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
-                           reinterpret_cast<uintptr_t>(d_res_dev) | reinterpret_cast<uintptr_t>(dx_dev) |
-                           reinterpret_cast<uintptr_t>(dx_bf16_dev)) & 15u) == 0;
+    // no misaligned route: the generic kernel takes the same u32x2 / f32x4 groups as the row-resident ones
+    MMX_CHECK_ARG(aligned16(x_dev, gamma_dev, d_res_dev, dx_dev) &&
+                      ((reinterpret_cast<uintptr_t>(dy_dev) | reinterpret_cast<uintptr_t>(dx_bf16_dev)) & 7u) == 0,
+                  "mmx_layernorm_bwd_add_bf16: x, gamma, d_res and dx must be 16-byte aligned, the bf16 dy and dx 8-byte");
 #define MMX_LN_ROW(ITER)                                                                                                          \
-    if (aligned && E == 256 * ITER) {                                                                                            \
+    if (E == 256 * ITER) {                                                                                                       \
         mmx::layernorm_bwd_add_bf16_row_kernel<ITER><<<static_cast<unsigned>((rows + 3) / 4), 256, 0,                             \
                                                        static_cast<hipStream_t>(stream)>>>(                                      \
             static_cast<const unsigned short*>(dy_dev), static_cast<const float*>(x_dev), static_cast<const float*>(mean_dev),   \

@@ -325,6 +325,20 @@ def _row_stats(what, x_rows, mean, rstd):
     return _f32c(mean), _f32c(rstd)
 
 
+def _bwd_rows(what, dy, x, d_res):
+    """The row counts of a LayerNorm backward, checked before a pointer leaves: ``x`` and ``d_res`` have ``dy``'s row width, ``d_res``
+    ``dy``'s row count (the kernel reads row ``r`` of both), and ``x``'s rows tile ``dy``'s (row ``r`` reads ``x``'s row ``r % x_rows``)."""
+    E = dy.shape[-1] if dy.dim() else 0
+    if E == 0 or x.dim() == 0 or x.shape[-1] != E:
+        raise MMXError("%s: dy %s and x %s differ in their last dimension" % (what, tuple(dy.shape), tuple(x.shape)))
+    rows, x_rows = dy.numel() // E, x.numel() // E
+    if x_rows == 0 or rows % x_rows:
+        raise MMXError("%s: the %d rows of x do not tile the %d rows of dy" % (what, x_rows, rows))
+    if d_res is not None and (d_res.dim() == 0 or d_res.shape[-1] != E or d_res.numel() != dy.numel()):
+        raise MMXError("%s: d_res %s is not dy's %d rows of %d" % (what, tuple(d_res.shape), rows, E))
+    return E, rows, x_rows
+
+
 def add_layernorm(x, y, gamma, beta, eps=1e-5, h_dtype=torch.float32):
     """``s = x + y; h = LayerNorm(s)`` in one pass -> ``(s, h, mean, rstd)`` (``y=None``: ``s`` is ``x`` itself).
     ``mean`` / ``rstd``: ``[rows]`` fp32, what ``layernorm_bwd_add`` takes.  ``h_dtype=torch.bfloat16``: ``h`` leaves the kernel
@@ -353,8 +367,7 @@ def layernorm_bwd_add(dy, x, mean, rstd, gamma, d_res=None):
     ``x`` ``[1, N, E]`` (or ``[B, N, E]``), ``mean``/``rstd`` matching ``x``'s rows."""
     _dev(dy, x, mean, rstd, gamma, d_res)
     dy, x = _f32c(dy), _f32c(x)
-    E = dy.shape[-1]
-    rows, x_rows = dy.numel() // E, x.numel() // E
+    E, rows, x_rows = _bwd_rows("layernorm_bwd_add", dy, x, d_res)
     mean, rstd = _row_stats("layernorm_bwd_add", x_rows, mean, rstd)
     (gamma,) = _affine("layernorm_bwd_add", E, gamma)
     dx = torch.empty_like(dy)
@@ -371,8 +384,7 @@ def layernorm_bwd_add_bf16(dy, x, mean, rstd, gamma, d_res=None, want_f32=True):
     if dy.dtype != torch.bfloat16:
         raise MMXError("layernorm_bwd_add_bf16: dy must be bf16")
     dy, x = dy.contiguous(), _f32c(x)
-    E = dy.shape[-1]
-    rows, x_rows = dy.numel() // E, x.numel() // E
+    E, rows, x_rows = _bwd_rows("layernorm_bwd_add_bf16", dy, x, d_res)
     dx = torch.empty(dy.shape, dtype=torch.float32, device=dy.device) if want_f32 else None
     dx_h = torch.empty_like(dy)
     mean, rstd = _row_stats("layernorm_bwd_add_bf16", x_rows, mean, rstd)
@@ -625,7 +637,8 @@ def matmul(a, b, add_to=None, trans_a=False, nan_to_zero=False):
 
 
 def rows_to_dense(vals, rows, n_tokens):
-    """``out [B, n_tokens, E]`` = zeros with ``out[b, rows[b]] = vals[b]`` in ONE launch (``mmx_rows_to_dense``)."""
+    """``out [B, n_tokens, E]`` = zeros with ``out[b, rows[b]] = vals[b]`` in ONE launch (``mmx_rows_to_dense``); a ``rows[b]`` outside
+    ``[0, n_tokens)`` names no row: sample ``b`` is all zero."""
     _dev(vals, rows)
     vals, rows = _f32c(vals), rows.to(torch.long).contiguous()
     if vals.dim() != 2 or rows.numel() != vals.shape[0]:
@@ -637,7 +650,8 @@ def rows_to_dense(vals, rows, n_tokens):
 
 
 def rows_add_(dense, rows, vals):
-    """``dense[b, rows[b]] += vals[b]`` in place (``mmx_rows_add``); ``dense [B, N, E]`` fp32 contiguous."""
+    """``dense[b, rows[b]] += vals[b]`` in place (``mmx_rows_add``); ``dense [B, N, E]`` fp32 contiguous.  A ``rows[b]`` outside
+    ``[0, N)`` leaves sample ``b`` as it is."""
     _dev(dense, rows, vals)
     if dense.dtype != torch.float32 or not dense.is_contiguous():
         raise MMXError("rows_add_: dense must be fp32 contiguous")
@@ -881,6 +895,7 @@ def layernorm_bwd_add_rows(dy, x, mean, rstd, gamma, d_res, live, out=None):
     ``out``: an fp32 contiguous tensor of ``dy``'s shape to write to."""
     _dev(dy, x, mean, rstd, gamma, d_res, out)
     live._check("layernorm_bwd_add_rows", dy, x, *([d_res] if d_res is not None else []))
+    _bwd_rows("layernorm_bwd_add_rows", dy, x, d_res)
     mean, rstd = _row_stats("layernorm_bwd_add_rows", live.cap, mean, rstd)
     (gamma,) = _affine("layernorm_bwd_add_rows", dy.shape[-1], gamma)
     dx = out if out is not None else live._out(dy, dy.shape[-1])
