@@ -1,7 +1,8 @@
 """Sharded LXMERT perturbation evaluation on synthetic data -- the shape of ``lxmert/lxmert/perturbation.py``'s main
 loop (BASELINE.json config 4) on this package: one process per GPU, samples sharded rank-strided, batches of items of
 ANY question length (padded; the schedule kernel takes per-sample lengths) explained from ONE captured hipGraph and
-perturbed as one batch, ONE all-gather of the per-sample step accuracies at the end.
+perturbed as one batch, ONE all-gather of the per-sample step accuracies at the end.  The "ours" family without LRP and the
+rollout / raw_attn / attn_gradcam baselines run that way; the LRP methods and ablation_no_aggregation explain one item per call.
 
     python examples/lxmert_perturbation_eval.py --num-samples 512                      # one GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29511 \\
@@ -36,13 +37,16 @@ def synthetic_item(k, regions, feat_dim, vocab, answers):
 
 
 # methods of the reference's --method flag (lxmert/lxmert/perturbation.py:216-245).  The first group is explained a whole
-# batch at a time (rule flags of GeneratorOurs.generate_ours_batch); the others run the reference's per-item generator call
+# batch at a time (rule flags of GeneratorOurs.generate_ours_batch), and so are the three attention-only baselines of
+# BATCHED_BASELINES (GeneratorBaselines.generate_*_batch, replayed from GraphedBaselinesBatch; --per-item-baselines puts them back
+# on the per-item route for A / B runs); the others run the reference's per-item generator call
 # (lxmert_explainability.GeneratorOurs / GeneratorBaselines / GeneratorOursAblationNoAggregation; the LRP ones on the body's
 # own relprop pass) followed by the same batched perturbation of that one item.
 BATCHED_METHODS = {"ours_no_lrp": {}, "ours_no_lrp_no_norm": {"normalize_self_attention": False},
                    "ablation_no_self_in_10": {"apply_self_in_rule_10": False}}
 OTHER_METHODS = {"ours_with_lrp", "rollout", "partial_lrp", "transformer_att", "raw_attn", "attn_gradcam",
                  "ours_with_lrp_no_normalization", "ablation_no_aggregation"}
+BATCHED_BASELINES = {"rollout", "raw_attn", "attn_gradcam"}       # of OTHER_METHODS: no LRP pass, batched kernels exist
 
 
 class ItemUsage:
@@ -92,9 +96,12 @@ def main():
                     help="round-5 host path: batch assembly and blocking host-to-device copies on the launching thread")
     ap.add_argument("--bucket-by-length", action="store_true",
                     help="round-1 behaviour: group items by question length, eager explain pass per group")
+    ap.add_argument("--per-item-baselines", action="store_true",
+                    help="rollout / raw_attn / attn_gradcam on the per-item route (one batch-1 explain call per item), for A/B runs")
     args = ap.parse_args()
     args.text, args.positive = args.is_text_pert, args.is_positive_pert
-    per_item = args.method not in BATCHED_METHODS
+    batched_baseline = args.method in BATCHED_BASELINES and not args.per_item_baselines
+    per_item = args.method not in BATCHED_METHODS and not batched_baseline
     if per_item:
         args.max_batch, args.bucket_by_length = 1, True                # one item per explain call, its own length
     rule_flags = BATCHED_METHODS.get(args.method, {})
@@ -107,6 +114,7 @@ def main():
     model = lm.LxmertForQuestionAnswering(cfg).to(dev).eval()
     indices = sharding.perturbation_sample_indices(args.dataset_len, args.num_samples)      # same list on every rank
     gen = le.GeneratorOurs(type("Usage", (), {"model": model})())
+    base_gen = le.GeneratorBaselines(type("Usage", (), {"model": model})())
     pert = lp.LxmertPerturbation(model)
     run_cfg = {"evaluator": "lxmert_perturbation", "method": args.method, "test": "text" if args.text else "image",
                "positive": bool(args.positive), "steps": list(lp.PERT_STEPS), "dataset_len": args.dataset_len}
@@ -151,7 +159,12 @@ def main():
             usage_item = dict(batch)
             R_t_t, R_t_i = (r.unsqueeze(0) for r in graphed["explain"](usage_item))
         elif args.bucket_by_length:
-            R_t_t, R_t_i = gen.generate_ours_batch(batch, **rule_flags)
+            R_t_t, R_t_i = getattr(base_gen, "generate_%s_batch" % args.method)(batch) if batched_baseline else \
+                gen.generate_ours_batch(batch, **rule_flags)
+        elif batched_baseline:
+            if "run" not in graphed:           # captured once, like the graph of "ours" below
+                graphed["run"] = le.GraphedBaselinesBatch(model, batch, args.method)
+            R_t_t, R_t_i = graphed["run"](batch)
         else:
             if "run" not in graphed:           # captured once; serves every later batch whatever its question lengths
                 graphed["run"] = le.GraphedGenerateOursBatch(model, batch, **rule_flags)
@@ -172,7 +185,7 @@ def main():
     per_sample = sharding.evaluate_sharded(indices, length_of, process_batch,
                                            len(lp.PERT_STEPS), max_batch=args.max_batch, store=store, device=gather_dev,
                                            load_batch=None if args.no_prefetch else load_batch, prefetch_device=dev, stats=stats)
-    if "run" in graphed:
+    if "run" in graphed and not batched_baseline:
         graphed["run"].finish()                # the last batch's handle_residual word
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0

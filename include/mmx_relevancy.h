@@ -384,6 +384,47 @@ int mmx_rollout_chain(const void* const* layers, int n_layers, int B, int N, int
                       void* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The attention-only baselines of the bi-modal model for a PADDED batch of ragged questions (csrc/bimodal_baselines.hip).  The
+ * reference explains one question per call (lxmert/lxmert/perturbation.py:216-245), so it never pads; here every slab is the fp32
+ * [B, H, Nq, Nk] capture slab of a padded batch and every length a DEVICE array of B int32 (NULL = the full extent).  A length
+ * outside 1..N is CLAMPED to that range inside the kernel before it is used: it never bounds a loop or forms an address unclamped.
+ * Sample b is computed from its LIVE block only -- the leading q_len[b] x k_len[b] entries -- and everything outside that block is
+ * written as exact zero.  Fixed summation orders, no atomics: two calls give the same bits, and sample b's output depends neither on
+ * B nor on its position in the batch.  Sizes per modality: 1..48 (as mmx_lxmert_schedule).  Every argument is checked before any
+ * HIP call: null required pointers, B / H <= 0, sizes outside 1..48, n_text < 2, n_img < 1, tables longer than
+ * MMX_BASELINES_MAX_TABLE, a workspace smaller than the query says and outputs that overlap an input (or each other) return
+ * MMX_EINVAL with a message in mmx_last_error().
+ *
+ * mmx_head_mean_live: out [B, Nq, Nk].
+ *   grad_dev == NULL: the plain head mean mean_h attn[b, h] (lxmert/lxmert/src/ExplanationGenerator.py:528-529, :534-535).
+ *   grad_dev given:   GradCAM (lxmert/lxmert/src/ExplanationGenerator.py:542-547): clamp(mean_h(attn[b, h] * w[b, h]), 0) with
+ *                     w[b, h] = the mean of grad[b, h] over the LIVE block: the sum and the divisor are both those of the live block
+ *                     (the gradient of a padded batch is not zero at padded key columns, although the probability is).
+ *   flags: MMX_HEAD_MEAN_ZERO_CLS writes out[b, 0, 0] = 0 ("disregard the [CLS] token", :539, :592).  One launch, one workgroup per sample.
+ *
+ * mmx_lxmert_rollout: generate_rollout (lxmert/lxmert/src/ExplanationGenerator.py:595-665 with compute_rollout_attention :5-15).
+ *   text_attn: HOST table of n_text >= 2 device slabs [B, H, T, T]: the language layers, then every x-layer's lang_self_att, the
+ *              LAST x-layer's being the last entry;  img_attn: HOST table of n_img >= 1 slabs [B, H, I, I]: r_layers, then
+ *              visn_self_att of every x-layer but the last;  cross_attn_dev: the last x-layer's visual_attention slab [B, H, T, I].
+ *   Per sample, t = clamp(text_len[b], 1, T):  A^_l = (mean_h A_l[:t, :t] + I) / its row sums;  R' = A^_{n_text-2} ... A^_0;
+ *   R_ii = the same product over the image table;  R_ti = R'^T . (C . R_ii), C the head mean of the cross slab's rows < t (:656);
+ *   R_tt = A^_{n_text-1} . R' (:662), R_tt[0, 0] = 0 (:665).
+ *   outputs fp32: R_tt [B, T, T], R_ti [B, T, I] (zero beyond t), optional R_ii [B, I, I].
+ *   workspace: mmx_lxmert_rollout_workspace_bytes(...) bytes (0 for arguments the entry would refuse), 16-byte aligned, caller-owned,
+ *   stream-ordered.
+ *   Two plain launches ordered by the stream (no ticket, no spin-wait): B x (n_text + n_img + 1) workgroups take the head means
+ *   (+ I, normalised) of every slab, read exactly once, into the workspace; one workgroup per sample then runs the products from
+ *   LDS on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32; no reduced-precision product anywhere). */
+#define MMX_BASELINES_MAX_TABLE 32
+#define MMX_HEAD_MEAN_ZERO_CLS 1u
+int mmx_head_mean_live(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int Nq, int Nk,
+                       const void* q_len_dev, const void* k_len_dev, unsigned flags, void* stream);
+size_t mmx_lxmert_rollout_workspace_bytes(int n_text, int n_img, int B, int T, int I);
+int mmx_lxmert_rollout(const void* const* text_attn, int n_text, const void* const* img_attn, int n_img,
+                       const void* cross_attn_dev, int B, int H, int T, int I, const void* text_len_dev, void* R_tt_dev,
+                       void* R_ti_dev, void* R_ii_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * On-device post-processing of relevancy maps (one workgroup per map, no host round trip):
  *  mmx_heatmap_bilinear_minmax: [B, g, g] patch maps -> bilinear upsample to [B, S, S] (torch interpolate semantics,
  *    align_corners=False) + min-max normalisation; replaces CLIP_explainability.ipynb cell 7:14-18 and

@@ -1,0 +1,365 @@
+// The attention-only baselines of the bi-modal (LXMERT-style) model for a PADDED batch of ragged questions: raw attention,
+// attention GradCAM and rollout (lxmert/lxmert/src/ExplanationGenerator.py:508-540, :542-593, :595-665 with :5-15).
+//
+// The reference explains one question per call, so nothing of it is ever padded.  In a padded batch the probability slabs are zero
+// at padded key columns, but the GRADIENT slabs are not (dP = dO . V^T has a value wherever V has a row), and padded query rows hold
+// whatever the body computed for a pad token.  Every kernel here therefore works on sample b's LIVE block only -- the leading
+// q_len[b] x k_len[b] entries -- for the sums AND for the divisors, and writes exact zeros everywhere else.  Lengths are device
+// int32 arrays; a value outside 1..N is clamped to that range before it bounds a loop or forms an address.
+//
+//   head_mean_live_kernel   one workgroup per sample: mean_h P[b, h] on the live block, or GradCAM clamp(mean_h(P[b, h] w[b, h]), 0)
+//                           with w[b, h] = the mean of G[b, h] over the live block (a wave per head, lanes striding the live block,
+//                           xor butterfly).
+//   rollout_means_kernel    workgroup (b, k) of B x (n_text + n_img + 1): the head mean of block k of sample b (16-byte loads at
+//                           4-byte alignment, heads in order), + I and row normalisation on the live block for the self-attention
+//                           blocks, written ONCE to the workspace, zero outside the live block.  Every slab is read exactly once.
+//   rollout_chain_kernel    one workgroup per sample: the two left-multiplied products and R_ti = R'^T (C R_ii) with every matrix
+//                           in LDS, on the exact-fp32 MFMA tiles of bimodal_tile.h; the next block is in flight (registers) while
+//                           the current product runs.
+// The two rollout kernels are two plain launches: stream order is the only synchronisation (no tickets, no spinning).  Fixed
+// summation orders, no atomics: two runs give the same bits, and sample b's result depends neither on B nor on b.
+#include "mmx_common.h"
+#include "bimodal_tile.h"
+
+namespace mmx {
+
+constexpr int kBlMax = 48;          // tokens per modality (== kBmMax of bimodal_kernels.hip, ops.LXMERT_FUSED_MAX_TOKENS)
+constexpr int kBlMaxTable = MMX_BASELINES_MAX_TABLE;
+constexpr int kHmThreads = 256;
+constexpr int kHmPer = (kBlMax * kBlMax + kHmThreads - 1) / kHmThreads;   // live entries one thread owns (9)
+constexpr int kRcThreads = 512;
+constexpr int kRcWaves = kRcThreads / 64;
+
+// the clamped length of sample b: NEVER used unclamped
+__device__ __forceinline__ int live_len(const int* len, int b, int N) { return len ? min(max(len[b], 1), N) : N; }
+
+__device__ __forceinline__ float wave_sum_bl(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ __launch_bounds__(kHmThreads) void head_mean_live_kernel(const float* __restrict__ attn, const float* __restrict__ grad,
+                                                                    float* __restrict__ out, int H, int Nq, int Nk,
+                                                                    const int* q_len, const int* k_len, unsigned flags) {
+    __shared__ float w_lds[64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = live_len(q_len, b, Nq), k = live_len(k_len, b, Nk);
+    const int hs = Nq * Nk, live = q * k;
+    const float* P = attn + static_cast<int64_t>(b) * H * hs;
+    const float* G = grad ? grad + static_cast<int64_t>(b) * H * hs : nullptr;
+    float* O = out + static_cast<int64_t>(b) * hs;
+
+    // thread tid owns the live entries n = tid, tid + 256, ... (n counts the live block row by row)
+    float acc[kHmPer];
+    int off[kHmPer];
+#pragma unroll
+    for (int u = 0; u < kHmPer; ++u) {
+        const int n = tid + u * kHmThreads;
+        const int i = n / k;
+        off[u] = n < live ? i * Nk + (n - i * k) : -1;
+        acc[u] = 0.f;
+    }
+    if (!G) {
+        for (int h = 0; h < H; ++h)
+#pragma unroll
+            for (int u = 0; u < kHmPer; ++u)
+                if (off[u] >= 0) acc[u] += P[static_cast<int64_t>(h) * hs + off[u]];
+    } else {
+        const float cnt = static_cast<float>(live);
+        for (int h0 = 0; h0 < H; h0 += 64) {
+            const int nh = min(64, H - h0);
+            for (int hh = wave; hh < nh; hh += kHmThreads / 64) {        // w[b, h]: one wave per head, the live block only
+                const float* Gh = G + static_cast<int64_t>(h0 + hh) * hs;
+                float s = 0.f;
+                int i = lane / k, j = lane - i * k;
+                for (int n = lane; n < live; n += 64) {
+                    s += Gh[i * Nk + j];
+                    j += 64;
+                    while (j >= k) { j -= k; ++i; }
+                }
+                s = wave_sum_bl(s);
+                if (lane == 0) w_lds[hh] = s / cnt;
+            }
+            __syncthreads();
+            for (int hh = 0; hh < nh; ++hh) {
+                const float w = w_lds[hh];
+#pragma unroll
+                for (int u = 0; u < kHmPer; ++u)
+                    if (off[u] >= 0) acc[u] += P[static_cast<int64_t>(h0 + hh) * hs + off[u]] * w;
+            }
+            __syncthreads();
+        }
+    }
+    const float fH = static_cast<float>(H);
+    for (int e = tid; e < hs; e += kHmThreads) {                          // everything outside the live block: exact zeros
+        const int i = e / Nk, j = e - i * Nk;
+        if (i >= q || j >= k) O[e] = 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kHmPer; ++u) {
+        if (off[u] < 0) continue;
+        float v = acc[u] / fH;
+        if (G) v = relu_nan(v);
+        if ((flags & MMX_HEAD_MEAN_ZERO_CLS) && off[u] == 0) v = 0.f;
+        O[off[u]] = v;
+    }
+}
+
+struct RolloutArgs {
+    const float* text[kBlMaxTable];    // [B, H, T, T]; the last entry is the last x-layer's language self-attention
+    const float* img[kBlMaxTable];     // [B, H, I, I]
+    const float* cross;                // [B, H, T, I]
+    int n_text, n_img, B, H, T, I;
+    const int* text_len;
+    float* ws;                         // [B][nblk][bs]: blocks in the order text, img, cross, row stride = the block's padded key count
+    int bs;
+    float *R_tt, *R_ti, *R_ii;
+};
+
+constexpr int kRmLd = kBlMax + 1;
+
+__global__ __launch_bounds__(kHmThreads) void rollout_means_kernel(const RolloutArgs a) {
+    __shared__ float m[kBlMax * kRmLd];
+    __shared__ float rs[kBlMax];
+    const int tid = threadIdx.x;
+    const int nblk = a.n_text + a.n_img + 1;
+    const int b = blockIdx.x / nblk, k = blockIdx.x - b * nblk;
+    const int t = live_len(a.text_len, b, a.T);
+    const bool is_text = k < a.n_text, is_cross = k == nblk - 1;
+    const float* __restrict__ src = is_text ? a.text[k] : is_cross ? a.cross : a.img[k - a.n_text];
+    const int Nq = is_text || is_cross ? a.T : a.I, Nk = is_text ? a.T : a.I;
+    const int lq = is_text || is_cross ? t : a.I, lk = is_text ? t : a.I;
+    const int H = a.H, hs = Nq * Nk;
+    const int64_t sample = static_cast<int64_t>(b) * H * hs, slab_end = static_cast<int64_t>(a.B) * H * hs;
+    const float fH = static_cast<float>(H);
+
+    for (int c = tid; c * 4 < hs; c += kHmThreads) {
+        const int p = c * 4;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        if (sample + static_cast<int64_t>(H - 1) * hs + p + 3 < slab_end) {     // the 16-byte loads stay inside the slab
+            int h = 0;
+            for (; h + 6 <= H; h += 6) {
+                f32x4 v[6];
+#pragma unroll
+                for (int u = 0; u < 6; ++u) v[u] = ldg4_u(src + sample + static_cast<int64_t>(h + u) * hs + p);
+#pragma unroll
+                for (int u = 0; u < 6; ++u) s += v[u];
+            }
+            for (; h < H; ++h) s += ldg4_u(src + sample + static_cast<int64_t>(h) * hs + p);
+        } else {
+            for (int e = 0; e < 4 && p + e < hs; ++e)
+                for (int h = 0; h < H; ++h) s[e] += src[sample + static_cast<int64_t>(h) * hs + p + e];
+        }
+        int row = p / Nk, col = p - row * Nk;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (p + e < hs) m[row * kRmLd + col] = s[e] / fH;
+            if (++col == Nk) { col = 0; ++row; }
+        }
+    }
+    __syncthreads();
+    if (!is_cross && tid < lq) {                 // row sums of (A_bar + I) over the live block, columns in order
+        float s = 0.f;
+        for (int j = 0; j < lk; ++j) s += m[tid * kRmLd + j] + (j == tid ? 1.f : 0.f);
+        rs[tid] = s;
+    }
+    __syncthreads();
+    float* dst = a.ws + (static_cast<int64_t>(b) * nblk + k) * a.bs;
+    for (int e = tid; e < hs; e += kHmThreads) {
+        const int i = e / Nk, j = e - i * Nk;
+        float v = 0.f;
+        if (i < lq && j < lk) v = is_cross ? m[i * kRmLd + j] : (m[i * kRmLd + j] + (i == j ? 1.f : 0.f)) / rs[i];
+        dst[e] = v;
+    }
+}
+
+__global__ __launch_bounds__(kRcThreads) void rollout_chain_kernel(const RolloutArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    const int PT = a.T, I = a.I;
+    const int t = live_len(a.text_len, b, PT);
+    const int nblk = a.n_text + a.n_img + 1;
+    const int m16 = max(PT, I), D16 = ((m16 + 15) >> 4) << 4, LD = D16 + 4, MS = D16 * LD;
+    auto mat = [&](int i) { return M2{smem + i * MS, LD}; };
+    // 0 the staged block  1, 2 the text product (ping-pong; then R' and R_tt, then C . R_ii)  3, 4 the image product (then R_ti)
+    const M2 S = mat(0);
+    M2 curT = mat(1), nxtT = mat(2), curI = mat(3), nxtI = mat(4);
+    for (int e = tid; e < 5 * MS; e += kRcThreads) smem[e] = 0.f;
+    __syncthreads();
+
+    const float* wsb = a.ws + static_cast<int64_t>(b) * nblk * a.bs;
+    auto block_hs = [&](int k) { return k < a.n_text ? PT * PT : k == nblk - 1 ? PT * I : I * I; };
+    f32x4 pre[2];
+    auto issue = [&](int k) {                   // workspace -> registers: <= 2 chunks per lane (48 x 48 / 4 / 512)
+        const int hs = block_hs(k);
+        const f32x4* src = reinterpret_cast<const f32x4*>(wsb + static_cast<int64_t>(k) * a.bs);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int c = tid + u * kRcThreads;
+            pre[u] = (c * 4 < hs) ? src[c] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto commit = [&](int k, M2 dst) {          // registers -> LDS (the block is already zero outside its live part)
+        const int hs = block_hs(k), pk = k < a.n_text ? PT : I;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int c = tid + u * kRcThreads;
+            if (c * 4 < hs) {
+                int row = c * 4 / pk, col = c * 4 - row * pk;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (c * 4 + e < hs) dst.at(row, col) = pre[u][e];
+                    if (++col == pk) { col = 0; ++row; }
+                }
+            }
+        }
+    };
+    const int li = lane & 15, lk4 = (lane >> 4) * 4;
+    // D[:M, :N] = A . B (A: M x K, or K x M with ta), 16 x 16 tiles dealt to the waves
+    auto product = [&](bool ta, M2 A, int M, int K, M2 Bm, int N, M2 D) {
+        const int tr = (M + 15) >> 4, tc = (N + 15) >> 4;
+        for (int tl = wave; tl < tr * tc; tl += kRcWaves) {
+            const int ti = tl / tc, i0 = ti * 16, j0 = (tl - ti * tc) * 16;
+            const f32x4 acc = ta ? bm_tile<true>(A, Bm, i0, j0, K, lane) : bm_tile<false>(A, Bm, i0, j0, K, lane);
+            const int col = j0 + li;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = i0 + lk4 + r;
+                if (row < M && col < N) D.at(row, col) = acc[r];
+            }
+        }
+    };
+
+    issue(0);
+    for (int k = 0; k < nblk; ++k) {
+        const bool first_t = k == 0, first_i = k == a.n_text;
+        commit(k, first_t ? curT : first_i ? curI : S);
+        if (k + 1 < nblk) issue(k + 1);
+        lds_barrier();
+        if (first_t || first_i) continue;        // a product starts from its first matrix
+        if (k < a.n_text - 1) {                  // R' <- A_k . R'
+            product(false, S, t, t, curT, t, nxtT);
+            lds_barrier();
+            const M2 x = curT; curT = nxtT; nxtT = x;
+        } else if (k == a.n_text - 1) {          // R_tt = A_last . R'  (R' stays in curT for R_ti)
+            product(false, S, t, t, curT, t, nxtT);
+            lds_barrier();
+            for (int e = tid; e < PT * PT; e += kRcThreads) {
+                const int i = e / PT, j = e - i * PT;
+                a.R_tt[static_cast<int64_t>(b) * PT * PT + e] = (i < t && j < t && e != 0) ? nxtT.at(i, j) : 0.f;   // [0, 0]: the [CLS] token (:665)
+            }
+            lds_barrier();
+        } else if (k < nblk - 1) {               // R_ii <- A_k . R_ii
+            product(false, S, I, I, curI, I, nxtI);
+            lds_barrier();
+            const M2 x = curI; curI = nxtI; nxtI = x;
+        } else {                                 // R_ti = R'^T . (C . R_ii)  (:656)
+            product(false, S, t, I, curI, I, nxtT);
+            lds_barrier();
+            product(true, curT, t, t, nxtT, I, nxtI);
+            lds_barrier();
+        }
+    }
+    for (int e = tid; e < PT * I; e += kRcThreads) {
+        const int i = e / I, j = e - i * I;
+        a.R_ti[static_cast<int64_t>(b) * PT * I + e] = (i < t) ? nxtI.at(i, j) : 0.f;
+    }
+    if (a.R_ii)
+        for (int e = tid; e < I * I; e += kRcThreads) a.R_ii[static_cast<int64_t>(b) * I * I + e] = curI.at(e / I, e % I);
+}
+
+}  // namespace mmx
+
+using namespace mmx;
+
+static inline size_t bl_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+static inline int bl_block_floats(int T, int I) {
+    const int m = T > I ? T : I;
+    return ((m * m + 3) / 4) * 4;
+}
+// [a, a + na) and [b, b + nb) share a byte (a null pointer overlaps nothing)
+static inline bool bl_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+extern "C" int mmx_head_mean_live(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int Nq, int Nk,
+                                  const void* q_len_dev, const void* k_len_dev, unsigned flags, void* stream) {
+    MMX_CHECK_ARG(attn_dev && out_dev, "mmx_head_mean_live: null pointer");
+    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_head_mean_live: B=%d H=%d (both >= 1)", B, H);
+    MMX_CHECK_ARG(Nq >= 1 && Nq <= kBlMax && Nk >= 1 && Nk <= kBlMax, "mmx_head_mean_live: Nq=%d Nk=%d outside 1..%d", Nq, Nk, kBlMax);
+    MMX_CHECK_ARG((flags & ~static_cast<unsigned>(MMX_HEAD_MEAN_ZERO_CLS)) == 0, "mmx_head_mean_live: unknown flags 0x%x", flags);
+    const size_t out_bytes = sizeof(float) * static_cast<size_t>(B) * Nq * Nk, in_bytes = out_bytes * static_cast<size_t>(H);
+    const size_t len_bytes = sizeof(int) * static_cast<size_t>(B);
+    MMX_CHECK_ARG(!bl_overlap(out_dev, out_bytes, attn_dev, in_bytes) && !bl_overlap(out_dev, out_bytes, grad_dev, in_bytes) &&
+                      !bl_overlap(out_dev, out_bytes, q_len_dev, len_bytes) && !bl_overlap(out_dev, out_bytes, k_len_dev, len_bytes),
+                  "mmx_head_mean_live: the output may not alias an input");
+    head_mean_live_kernel<<<static_cast<unsigned>(B), kHmThreads, 0, static_cast<hipStream_t>(stream)>>>(
+        static_cast<const float*>(attn_dev), static_cast<const float*>(grad_dev), static_cast<float*>(out_dev), H, Nq, Nk,
+        static_cast<const int*>(q_len_dev), static_cast<const int*>(k_len_dev), flags);
+    MMX_LAUNCH_CHECK("head_mean_live_kernel");
+    return MMX_OK;
+}
+
+extern "C" size_t mmx_lxmert_rollout_workspace_bytes(int n_text, int n_img, int B, int T, int I) {
+    if (n_text < 2 || n_img < 1 || n_text > kBlMaxTable || n_img > kBlMaxTable || B < 1 || T < 1 || I < 1 || T > kBlMax || I > kBlMax)
+        return 0;
+    return bl_align256(sizeof(float) * static_cast<size_t>(B) * (n_text + n_img + 1) * bl_block_floats(T, I));
+}
+
+extern "C" int mmx_lxmert_rollout(const void* const* text_attn, int n_text, const void* const* img_attn, int n_img,
+                                  const void* cross_attn_dev, int B, int H, int T, int I, const void* text_len_dev, void* R_tt_dev,
+                                  void* R_ti_dev, void* R_ii_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    MMX_CHECK_ARG(text_attn && img_attn && cross_attn_dev && R_tt_dev && R_ti_dev && workspace_dev, "mmx_lxmert_rollout: null pointer");
+    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_lxmert_rollout: B=%d H=%d (both >= 1)", B, H);
+    MMX_CHECK_ARG(T >= 1 && T <= kBlMax && I >= 1 && I <= kBlMax, "mmx_lxmert_rollout: T=%d I=%d outside 1..%d", T, I, kBlMax);
+    MMX_CHECK_ARG(n_text >= 2 && n_img >= 1, "mmx_lxmert_rollout: n_text=%d (>= 2: the last entry is the last language block) n_img=%d (>= 1)",
+                  n_text, n_img);
+    MMX_CHECK_ARG(n_text <= kBlMaxTable && n_img <= kBlMaxTable, "mmx_lxmert_rollout: at most %d slabs per table (n_text=%d n_img=%d)",
+                  kBlMaxTable, n_text, n_img);
+    const size_t need = mmx_lxmert_rollout_workspace_bytes(n_text, n_img, B, T, I);
+    MMX_CHECK_ARG(workspace_bytes >= need, "mmx_lxmert_rollout: workspace of %zu bytes needed (mmx_lxmert_rollout_workspace_bytes), got %zu",
+                  need, workspace_bytes);
+    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_lxmert_rollout: the workspace must be 16-byte aligned");
+    RolloutArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int l = 0; l < n_text; ++l) {
+        MMX_CHECK_ARG(text_attn[l], "mmx_lxmert_rollout: null pointer in the text table (entry %d)", l);
+        a.text[l] = static_cast<const float*>(text_attn[l]);
+    }
+    for (int l = 0; l < n_img; ++l) {
+        MMX_CHECK_ARG(img_attn[l], "mmx_lxmert_rollout: null pointer in the image table (entry %d)", l);
+        a.img[l] = static_cast<const float*>(img_attn[l]);
+    }
+    const size_t f = sizeof(float), nb = static_cast<size_t>(B);
+    const void* outs[4] = {R_tt_dev, R_ti_dev, R_ii_dev, workspace_dev};
+    const size_t out_bytes[4] = {f * nb * T * T, f * nb * T * I, f * nb * I * I, need};
+    bool alias = false;
+    for (int o = 0; o < 4; ++o) {
+        for (int l = 0; l < n_text; ++l) alias |= bl_overlap(outs[o], out_bytes[o], text_attn[l], f * nb * H * T * T);
+        for (int l = 0; l < n_img; ++l) alias |= bl_overlap(outs[o], out_bytes[o], img_attn[l], f * nb * H * I * I);
+        alias |= bl_overlap(outs[o], out_bytes[o], cross_attn_dev, f * nb * H * T * I);
+        alias |= bl_overlap(outs[o], out_bytes[o], text_len_dev, sizeof(int) * nb);
+        for (int p = o + 1; p < 4; ++p) alias |= bl_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p]);
+    }
+    MMX_CHECK_ARG(!alias, "mmx_lxmert_rollout: an output or the workspace may not alias an input or another output");
+    a.cross = static_cast<const float*>(cross_attn_dev);
+    a.n_text = n_text; a.n_img = n_img; a.B = B; a.H = H; a.T = T; a.I = I;
+    a.text_len = static_cast<const int*>(text_len_dev);
+    a.ws = static_cast<float*>(workspace_dev);
+    a.bs = bl_block_floats(T, I);
+    a.R_tt = static_cast<float*>(R_tt_dev); a.R_ti = static_cast<float*>(R_ti_dev); a.R_ii = static_cast<float*>(R_ii_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nblk = n_text + n_img + 1;
+    rollout_means_kernel<<<static_cast<unsigned>(B) * nblk, kHmThreads, 0, s>>>(a);
+    MMX_LAUNCH_CHECK("rollout_means_kernel");
+    const int m = T > I ? T : I, D16 = ((m + 15) / 16) * 16;
+    const size_t lds = sizeof(float) * 5 * static_cast<size_t>(D16) * (D16 + 4);     // <= 49 920 bytes
+    rollout_chain_kernel<<<static_cast<unsigned>(B), kRcThreads, lds, s>>>(a);
+    MMX_LAUNCH_CHECK("rollout_chain_kernel");
+    return MMX_OK;
+}

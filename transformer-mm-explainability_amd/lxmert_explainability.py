@@ -262,7 +262,9 @@ class GeneratorOursAblationNoAggregation:
 
 class GeneratorBaselines:
     """Attention-only baselines of the reference (:368-665): raw attention, attention GradCAM, rollout.
-    ``generate_transformer_attr`` / ``generate_partial_lrp`` read LRP cams: they need a body with ``relprop`` (module docstring)."""
+    ``generate_transformer_attr`` / ``generate_partial_lrp`` read LRP cams: they need a body with ``relprop`` (module docstring).
+    ``generate_rollout_batch`` / ``generate_raw_attn_batch`` / ``generate_attn_gradcam_batch`` explain a padded batch of ragged
+    questions in one pass (``csrc/bimodal_baselines.hip``); ``GraphedBaselinesBatch`` replays them from one hipGraph."""
 
     def __init__(self, model_usage, save_visualization=False):
         self.model_usage = model_usage
@@ -318,6 +320,70 @@ class GeneratorBaselines:
         cams_text.append(self._head_mean(blk.lang_self_att.self))
         self.R_t_t = compute_rollout_attention(cams_text)
         self.R_t_t[0, 0] = 0
+        return self.R_t_t, self.R_t_i
+
+    # ---- the three attention-only baselines for a padded batch of ragged questions (per-item forms above: unchanged)
+    use_tape = True   # the *_batch methods: hand-written forward / backward of the body when it offers one (else the hook route)
+
+    def _batch_pass(self, model_inputs, backward=False, index=None):
+        """ONE forward of the padded batch [+ ONE backward with B one-hot seeds] -> ``(model, text_len)``; ``text_len`` is
+        ``attention_mask.sum(1)`` as a device int32 tensor (``None`` without a mask).  Nothing synchronises with the host."""
+        model = self.model_usage.model
+        T, I = model_inputs["input_ids"].shape[1], model_inputs["visual_feats"].shape[1]
+        if max(T, I) > ops.LXMERT_FUSED_MAX_TOKENS:
+            raise NotImplementedError("the batched baselines run LDS-resident kernels (T, I <= %d)" % ops.LXMERT_FUSED_MAX_TOKENS)
+
+        def seeds(output):
+            idx = output.argmax(dim=-1) if index is None else torch.as_tensor(index, device=output.device).reshape(-1)
+            return torch.zeros_like(output).scatter_(1, idx.reshape(-1, 1), 1.0)
+
+        if self.use_tape and hasattr(model, "forward_tape"):
+            output, state = model.forward_tape(**model_inputs)
+            if backward:
+                model.backward_tape(state, seeds(output))
+        elif backward:
+            output = rules.forward_for_backward(model, lambda: model(**model_inputs).question_answering_score)
+            model.zero_grad()
+            torch.sum(seeds(output) * output).backward(retain_graph=True)
+        else:
+            with torch.no_grad():
+                model(**model_inputs)
+        mask = model_inputs.get("attention_mask")
+        return model, (mask.sum(dim=1).to(torch.int32) if mask is not None else None)
+
+    def generate_raw_attn_batch(self, model_inputs):
+        """``generate_raw_attn`` (reference :508-540) for B padded samples: one forward, two launches.  ``model_inputs`` as
+        ``GeneratorOurs.generate_ours_batch`` (padded ``input_ids``, left-aligned ``attention_mask``).  Returns
+        ``(R_t_t [B, T, T], R_t_i [B, T, I])``, zero beyond each sample's question length."""
+        model, text_len = self._batch_pass(model_inputs)
+        blk = model.lxmert.encoder.x_layers[-1]
+        self.R_t_i = ops.head_mean_live(blk.visual_attention.att.get_attn().detach(), q_len=text_len)
+        self.R_t_t = ops.head_mean_live(blk.lang_self_att.self.get_attn().detach(), q_len=text_len, k_len=text_len, zero_cls=True)
+        return self.R_t_t, self.R_t_i
+
+    def generate_attn_gradcam_batch(self, model_inputs, index=None):
+        """``generate_attn_gradcam`` (reference :549-593) for B padded samples: one forward, one backward with B one-hot seeds
+        (``index``: ``None`` = the arg-max answer per sample, picked on the device, or ``[B]`` answer ids), two launches.  The
+        gradient's head weights are means over each sample's LIVE block: the padded batch's dP is not zero at padded keys."""
+        model, text_len = self._batch_pass(model_inputs, backward=True, index=index)
+        blk = model.lxmert.encoder.x_layers[-1]
+        att, sa = blk.visual_attention.att, blk.lang_self_att.self
+        self.R_t_i = ops.attn_gradcam_live(att.get_attn().detach(), att.get_attn_gradients().detach(), q_len=text_len)
+        self.R_t_t = ops.attn_gradcam_live(sa.get_attn().detach(), sa.get_attn_gradients().detach(), q_len=text_len,
+                                           k_len=text_len, zero_cls=True)
+        return self.R_t_t, self.R_t_i
+
+    def generate_rollout_batch(self, model_inputs):
+        """``generate_rollout`` (reference :595-665) for B padded samples: one forward and ``mmx_lxmert_rollout`` (two launches).
+        Returns ``(R_t_t, R_t_i)``; ``self.R_i_i [B, I, I]`` holds the image rollout."""
+        model, text_len = self._batch_pass(model_inputs)
+        enc = model.lxmert.encoder
+        xs = list(enc.x_layers)
+        text = [b.attention.self.get_attn().detach() for b in enc.layer] + [b.lang_self_att.self.get_attn().detach() for b in xs]
+        img = [b.attention.self.get_attn().detach() for b in enc.r_layers] + \
+              [b.visn_self_att.self.get_attn().detach() for b in xs[:-1]]
+        self.R_t_t, self.R_t_i, self.R_i_i = ops.lxmert_rollout(text, img, xs[-1].visual_attention.att.get_attn().detach(),
+                                                                text_len=text_len)
         return self.R_t_t, self.R_t_i
 
     def generate_transformer_attr(self, input, index=None, method_name="transformer_attr"):
@@ -425,3 +491,54 @@ class GraphedGenerateOursBatch:
             self._diag_pending = None
             done.synchronize()
             assert float(slot[0]) >= 0
+
+
+class GraphedBaselinesBatch:
+    """``GeneratorBaselines.generate_rollout_batch`` / ``generate_raw_attn_batch`` / ``generate_attn_gradcam_batch`` captured once
+    into a hipGraph and replayed, the way ``GraphedGenerateOursBatch`` replays ``generate_ours_batch``: the kernels take per-sample
+    question lengths from the device, so ONE graph captured at a padded length serves every batch of that shape.
+
+        run = GraphedBaselinesBatch(model, example_inputs, "rollout")     # "rollout" | "raw_attn" | "attn_gradcam"
+        R_t_t, R_t_i = run(inputs)                                        # the graph's own output buffers
+    """
+
+    METHODS = ("rollout", "raw_attn", "attn_gradcam")
+
+    def __init__(self, model, example_inputs, method, index=None, warmup=2):
+        if method not in self.METHODS:
+            raise ValueError("method must be one of %s, got %r" % (self.METHODS, method))
+        self.method = method
+        self.static = {k: v.clone() for k, v in example_inputs.items()}
+        self.static_index = None if index is None else torch.as_tensor(index, device=self.static["input_ids"].device).clone()
+        self.gen = GeneratorBaselines(type("Usage", (), {"model": model})())
+        if method == "rollout":
+            self._call = lambda: self.gen.generate_rollout_batch(self.static)
+        elif method == "raw_attn":
+            self._call = lambda: self.gen.generate_raw_attn_batch(self.static)
+        else:
+            self._call = lambda: self.gen.generate_attn_gradcam_batch(self.static, self.static_index)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._call()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(self.graph):
+            self.outputs = self._call()
+            self.R_i_i = getattr(self.gen, "R_i_i", None)
+        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+
+    def __call__(self, inputs=None, index=None):
+        if inputs is not None:
+            for k, v in inputs.items():
+                if v.shape != self.static[k].shape:
+                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
+                                     % (k, tuple(v.shape), tuple(self.static[k].shape)))
+                self.static[k].copy_(v)
+        if index is not None:
+            if self.static_index is None:
+                raise ValueError("the graph was captured with index=None (arg-max answers)")
+            self.static_index.copy_(torch.as_tensor(index))
+        self.graph.replay()
+        return self.outputs

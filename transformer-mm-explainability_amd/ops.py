@@ -1075,6 +1075,81 @@ def lxmert_schedule(lang, vis, x_lang_cross, x_img_cross, x_lang_self, x_img_sel
     return R_tt, R_ti, R_ii, R_it
 
 
+# ------------------------------------------------------------------------------------------- bi-modal baselines, padded batches
+def _lengths(what, lens, B):
+    """A per-sample length array for the C-ABI: ``None`` or a device ``int32 [B]`` tensor (clamped to the extent by the kernel)."""
+    if lens is None:
+        return None
+    _dev(lens)
+    lens = lens.to(dtype=torch.int32).contiguous()
+    if lens.numel() != B:
+        raise MMXError("%s: a length array needs one entry per sample (%d), got %d" % (what, B, lens.numel()))
+    return lens
+
+
+def _slab(what, t):
+    _dev(t)
+    if t.dtype != torch.float32 or t.dim() != 4:
+        raise MMXError("%s: fp32 [B, H, Nq, Nk] capture slabs only, got %s %s" % (what, t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def _head_mean_live(what, attn, grad, q_len, k_len, zero_cls):
+    attn = _slab(what, attn)
+    B, H, Nq, Nk = attn.shape
+    if grad is not None:
+        grad = _slab(what, grad)
+        if grad.shape != attn.shape:
+            raise MMXError("%s: gradient slab %s does not match %s" % (what, tuple(grad.shape), tuple(attn.shape)))
+    q_len, k_len = _lengths(what, q_len, B), _lengths(what, k_len, B)
+    out = torch.empty(B, Nq, Nk, dtype=torch.float32, device=attn.device)
+    check(lib().mmx_head_mean_live(_p(attn), _p(grad), _p(out), B, H, Nq, Nk, _p(q_len), _p(k_len),
+                                   _lib.HEAD_MEAN_ZERO_CLS if zero_cls else 0, _stream()), "mmx_head_mean_live")
+    return out
+
+
+def head_mean_live(attn, q_len=None, k_len=None, zero_cls=False):
+    """``mean_h attn[b, h]`` on sample b's leading ``q_len[b] x k_len[b]`` block of a padded ``[B, H, Nq, Nk]`` fp32 slab, exact
+    zeros outside it -> ``[B, Nq, Nk]``.  Lengths: device int tensors ``[B]`` or ``None`` (the full extent); ``zero_cls``:
+    ``out[b, 0, 0] = 0``.  One launch, nothing synchronises."""
+    return _head_mean_live("head_mean_live", attn, None, q_len, k_len, zero_cls)
+
+
+def attn_gradcam_live(attn, grad, q_len=None, k_len=None, zero_cls=False):
+    """GradCAM of a padded batch: ``clamp(mean_h(attn[b, h] * w[b, h]), 0)`` with ``w[b, h]`` the mean of ``grad[b, h]`` over sample
+    b's LIVE block only (a padded batch's gradient is not zero at padded key columns).  Arguments as ``head_mean_live``."""
+    return _head_mean_live("attn_gradcam_live", attn, grad, q_len, k_len, zero_cls)
+
+
+def lxmert_rollout(text_attn, img_attn, cross_attn, text_len=None):
+    """Rollout of a padded LXMERT batch in two launches.  ``text_attn``: the fp32 ``[B, H, T, T]`` slabs of the language layers, then
+    every x-layer's language self-attention (the last x-layer's LAST); ``img_attn``: ``[B, H, I, I]`` slabs of ``r_layers``, then the
+    image self-attention of every x-layer but the last; ``cross_attn``: the last x-layer's ``[B, H, T, I]`` slab; ``text_len``: device
+    int ``[B]`` or ``None``.  Returns ``(R_tt [B, T, T], R_ti [B, T, I], R_ii [B, I, I])``."""
+    what = "lxmert_rollout"
+    text = [_slab(what, t) for t in text_attn]
+    img = [_slab(what, t) for t in img_attn]
+    cross = _slab(what, cross_attn)
+    B, H, T, I = cross.shape
+    if any(t.shape != (B, H, T, T) for t in text) or any(t.shape != (B, H, I, I) for t in img):
+        raise MMXError("lxmert_rollout: the tables do not match the cross slab %s" % (tuple(cross.shape),))
+    text_len = _lengths(what, text_len, B)
+    dev = cross.device
+    R_tt = torch.empty(B, T, T, dtype=torch.float32, device=dev)
+    R_ti = torch.empty(B, T, I, dtype=torch.float32, device=dev)
+    R_ii = torch.empty(B, I, I, dtype=torch.float32, device=dev)
+    tt, _k0 = _lib.ptr_table([t.data_ptr() for t in text])
+    ti, _k1 = _lib.ptr_table([t.data_ptr() for t in img])
+    need = lib().mmx_lxmert_rollout_workspace_bytes(len(text), len(img), B, T, I)
+    if need == 0:
+        raise MMXError("lxmert_rollout: needs 2..%d text slabs, 1..%d image slabs and T, I <= %d (got %d, %d, T=%d, I=%d)"
+                       % (_lib.BASELINES_MAX_TABLE, _lib.BASELINES_MAX_TABLE, LXMERT_FUSED_MAX_TOKENS, len(text), len(img), T, I))
+    ws = _workspace(need, dev, tag="lxmert_rollout")        # grow-only scratch: pinned_state keeps it alive for graphs
+    check(lib().mmx_lxmert_rollout(tt, len(text), ti, len(img), _p(cross), B, H, T, I, _p(text_len), _p(R_tt), _p(R_ti),
+                                   _p(R_ii), _p(ws), need, _stream()), "mmx_lxmert_rollout")
+    return R_tt, R_ti, R_ii
+
+
 # ------------------------------------------------------------------------------------------- rollout
 def rollout_chain(layers, normalize):
     """``layers``: list of ``[B, N, N]`` (or ``[N, N]``) fp32 maps, already sliced to ``start_layer:``."""
