@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Host emulation of ``gemm_rows_f32_kernel``: cuts the kernel out of ``csrc/gemm_rows_f32.hip``, compiles it with
-``tools/host/gemm_rows_emu.cpp`` for the CPU (clang++, C++20) and runs the slab-count and row-list edge cases of
-``tests/test_gpu_gemm_rows_pipeline.py`` on all three tiles and epilogues.  ``--cxxflag FLAG`` (repeatable) adds a compiler flag: with the
-host compiler's thread sanitizer switched on, the run reports any LDS access that no barrier of the kernel orders.  No GPU.
+"""Host emulation of ``gemm_rows_f32_kernel`` and ``gemm_rows_f16_kernel``: compiles ``tools/host/gemm_rows_emu.cpp``, which includes
+``csrc/gemm_rows_core.h`` and the two ``.hip`` files as they ship (``MMX_GEMM_ROWS_EMU`` leaves out their launches and C entries), for the
+CPU (clang++, C++20) and runs the slab-count and row-list edge cases of ``tests/test_gpu_gemm_rows_pipeline.py`` (fp32: three tiles) and of
+``tests/test_gpu_gemm_rows_half.py`` (fp16: both tiles) through all three epilogues.  ``--cxxflag FLAG`` (repeatable) adds a compiler
+flag: with the host compiler's thread sanitizer switched on, the run reports any LDS access that no barrier of the kernels orders.  No GPU.
 ``python tools/emu_gemm_rows.py [--cxx PATH] [--cxxflag FLAG ...]``"""
 import argparse
 import os
@@ -11,7 +12,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP = os.path.join(ROOT, "transformer-mm-explainability_amd", "csrc", "gemm_rows_f32.hip")
+CSRC = os.path.join(ROOT, "transformer-mm-explainability_amd", "csrc")
 
 
 def main():
@@ -19,14 +20,9 @@ def main():
     ap.add_argument("--cxxflag", action="append", default=[])
     ap.add_argument("--cxx", default=os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"))
     args = ap.parse_args()
-    text = open(HIP).read()
-    start = text.index("template <int TM, int TN, int BK, int PF, int EPI>")
-    end = text.index("// The tile of a launch:")
     with tempfile.TemporaryDirectory() as tmp:
-        with open(os.path.join(tmp, "gemm_rows_kernel.inc"), "w") as f:
-            f.write(text[start:end])
         exe = os.path.join(tmp, "gemm_rows_emu")
-        cmd = [args.cxx, "-std=c++20", "-O1", "-g", "-pthread", "-Wno-deprecated-declarations", "-I", tmp,
+        cmd = [args.cxx, "-std=c++20", "-O1", "-g", "-pthread", "-x", "c++", "-I", CSRC,
                os.path.join(ROOT, "tools", "host", "gemm_rows_emu.cpp"), "-o", exe]
         cmd[1:1] = args.cxxflag
         subprocess.run(cmd, check=True)

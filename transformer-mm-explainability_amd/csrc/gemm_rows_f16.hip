@@ -1,7 +1,7 @@
 // K_gemm_rows_f16: C[r] = half(A[r]) . W for the rows r of a device-side list on v_mfma_f32_32x32x16_f16, fp32 accumulators and fp32
 // output -- the GEMMs of a causally masked tower in the reference's own half-precision mode (convert_weights, CLIP/clip/model.py:381-402;
 // the mask of model.py:334-340 and the EOT read of model.py:360 make every row past a caption's EOT token dead, 89 % of the rows at
-// caption lengths).  Same contract as gemm_rows_f32.hip: the grid is sized for the capacity, the count is read on the device, a
+// caption lengths).  Same contract as gemm_rows_f32.hip, on the same skeleton (gemm_rows_core.h): the grid is sized for the capacity, the count is read on the device, a
 // workgroup past it returns before any barrier, a row id goes through the list once, ids outside [0, cap) name no row, unlisted rows
 // are neither read nor written, EPI 0 / 1 / 2 = plain | + bias | + bias and QuickGELU of it to a second tensor, one launch for every
 // input (a hipGraph replays it).  No scratch, no atomics, no workspace.
@@ -34,11 +34,10 @@
 //     hold 16 rows that are distinct mod 16, so their slots cover the 64 banks once (MI355X LDS: bank = (a / 4) mod 64 for b128
 //     reads) -- conflict-free without a swizzle.  The ds_write_b128 of 8 consecutive lanes are 128 contiguous bytes of one tile row.
 //   * a thread converts the 8 floats of two adjacent 16-byte loads and stores them as one 16-byte LDS chunk.
-#include "mmx_common.h"
+#include "gemm_rows_core.h"
 
 namespace mmx {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // option "text_live_rows_half": 0 (default) an fp16 body keeps its dense text tower | 1: it takes the row-list route on this kernel
@@ -68,17 +67,10 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f16_kernel(const float* __re
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave % WC, wk = wave / WC;
-    const int M = min(*count, cap);
-    const int tiles_n = (N + TN - 1) / TN;
-    const int bx = blockIdx.x % tiles_n, by = blockIdx.x / tiles_n;
-    const int m0 = by * TM, n0 = bx * TN;
-    if (m0 >= M) return;                             // (workgroup-uniform: no barrier has been reached)
-
-    auto dense_row = [&](int gm) {
-        const int r = gm < M ? rows[gm] : -1;
-        return static_cast<unsigned>(r) < static_cast<unsigned>(cap) ? r : -1;   // an id outside the tensor is no row at all
-    };
-    if (tid < TM) rid[tid] = dense_row(m0 + tid);    // (published by the barrier in front of the first slab)
+    const RowsTilePos p = rows_tile_pos<TM, TN>(rows, count, cap, N);
+    if (p.empty()) return;
+    p.publish<TM>(rid);
+    const int m0 = p.m0, n0 = p.n0;
 
     f32x16 acc;
 #pragma unroll
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f16_kernel(const float* __re
     const _Float16* pb[CB];
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
-        const int arow = dense_row(m0 + cr + i * RS);
+        const int arow = p.dense_row(m0 + cr + i * RS);
         oka[i] = arow >= 0;
         pa[i] = A + static_cast<int64_t>(oka[i] ? arow : 0) * K;
     }
@@ -150,65 +142,8 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f16_kernel(const float* __re
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[g], f.b[g], acc, 0, 0, 0);
     };
 
-    const int nslab = (K + BK - 1) / BK;
-    fetch(0, ring[0]);
-    stash(0, 0, ring[0]);
-#pragma unroll
-    for (int j = 1; j <= PF; ++j) fetch(j, ring[j % PF]);   // slabs 1 .. PF in flight (set 0 is free again)
-    lds_barrier();
-    Frag cur;
-    read_frag(cur, 0);
-    // slab s: stash slab s + 1 (every wave left stage (s + 1) & 1, slab s - 1, before the barrier of slab s - 1: lds_barrier() waits
-    // for the wave's reads), half of the MFMAs, the barrier, the reads of slab s + 1, the other half
-    auto step = [&](int s, Slab& x, bool refill) {
-        __builtin_amdgcn_sched_barrier(0);           // (keeps the selects of the later slabs' registers, and with them their waits, out of this step)
-        stash((s + 1) & 1, s + 1, x);
-        if (refill) fetch(s + 1 + PF, x);
-        mfma_half(cur, 0);
-        lds_barrier();
-        Frag nxt;
-        read_frag(nxt, (s + 1) & 1);
-        mfma_half(cur, 1);
-        cur = nxt;
-    };
-    int s = 0;
-    for (; s + PF < nslab; s += PF)                  // steady state: one basic block, no test between the PF steps
-#pragma unroll
-        for (int j = 0; j < PF; ++j) step(s + j, ring[(j + 1) % PF], true);
-#pragma unroll
-    for (int j = 0; j < PF - 1; ++j) {               // at most PF - 1 steps are left, and nothing they would request is inside K
-        if (s + j + 1 >= nslab) break;
-        step(s + j, ring[(j + 1) % PF], false);
-    }
-    mfma_half(cur, 0);
-    mfma_half(cur, 1);
-    {                                                // the k shares of a tile meet: wk > 0 hand their accumulators to wk = 0, added in order
-        if (wk > 0)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) red[(((wk - 1) * WC + wc) * 16 + v) * 64 + lane] = acc[v];
-        lds_barrier();
-        if (wk > 0) return;
-#pragma unroll
-        for (int q = 0; q < WK - 1; ++q)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[v] += red[((q * WC + wc) * 16 + v) * 64 + lane];
-    }
-    const int gn = n0 + wc * 32 + li;
-    if (gn >= N) return;
-    float bv = 0.f;
-    if constexpr (EPI != 0) bv = bias[gn];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int r = rid[(v >> 2) * 8 + lg * 4 + (v & 3)];
-        if (r < 0) continue;
-        if constexpr (EPI == 0) {
-            C[static_cast<int64_t>(r) * N + gn] = acc[v];
-        } else {
-            const float m = acc[v] + bv;
-            C[static_cast<int64_t>(r) * N + gn] = m;
-            if constexpr (EPI == 2) C2[static_cast<int64_t>(r) * N + gn] = quick_gelu_f(m);
-        }
-    }
+    rows_k_pipeline<PF, true, Frag>(ring, (K + BK - 1) / BK, fetch, stash, read_frag, mfma_half);   // (true: the fence of "Choices")
+    rows_finish<EPI, WK, WC>(acc, red, p, rid, 0, wc, wk, wc, lane, N, C, bias, C2);
 }
 
 // The tile of a launch, from option "gemm_rows_tn" and the shape only (the live count stays on the device): 32 rows x 64 columns,
@@ -218,13 +153,16 @@ static int half_tile_tn(int N) {
     return tn ? tn : (N <= 512 ? 32 : 64);
 }
 
+}  // namespace mmx
+
+#ifndef MMX_GEMM_ROWS_EMU   // (the host emulation takes the kernel, not the launches)
+namespace mmx {
 template <int EPI>
 static int launch_gemm_rows_half(const char* what, hipStream_t s, const void* a_dev, const void* wh_dev, void* c_dev, const void* rows_dev,
                                  const void* count_dev, int cap_rows, int N, int K, const void* bias_dev, void* act_dev) {
     const int tn = half_tile_tn(N);
-    const int64_t wgs = static_cast<int64_t>((N + tn - 1) / tn) * ((cap_rows + 31) / 32);
-    MMX_CHECK_ARG(wgs < (1ll << 31), "%s: cap_rows=%d x N=%d is too large a grid", what, cap_rows, N);
-    const unsigned g = static_cast<unsigned>(wgs);
+    const unsigned g = rows_grid(what, 32, tn, cap_rows, N);
+    if (!g) return MMX_EINVAL;
     const float* A = static_cast<const float*>(a_dev);
     const _Float16* Wh = static_cast<const _Float16*>(wh_dev);
     float *C = static_cast<float*>(c_dev), *C2 = static_cast<float*>(act_dev);
@@ -238,14 +176,6 @@ static int launch_gemm_rows_half(const char* what, hipStream_t s, const void* a_
     return MMX_OK;
 }
 
-static bool half_operands_ok(const char* what, const void* a, const void* w, const void* c, int N, int K) {
-    if (N % 8 || K % 8 || ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(c)) & 15u)) {
-        set_error("%s: N=%d and K=%d must be multiples of 8 and the operands 16-byte aligned", what, N, K);
-        return false;
-    }
-    return true;
-}
-
 }  // namespace mmx
 
 using namespace mmx;
@@ -254,7 +184,7 @@ extern "C" int mmx_gemm_rows_f16(const void* a_dev, const void* wh_dev, void* c_
                                  int cap_rows, int N, int K, void* stream) {
     MMX_CHECK_ARG(a_dev && wh_dev && c_dev && rows_dev && count_dev, "mmx_gemm_rows_f16: null pointer");
     MMX_CHECK_ARG(cap_rows > 0 && N > 0 && K > 0, "mmx_gemm_rows_f16: cap_rows=%d N=%d K=%d", cap_rows, N, K);
-    if (!half_operands_ok("mmx_gemm_rows_f16", a_dev, wh_dev, c_dev, N, K)) return MMX_ENOTSUP;
+    if (!rows_operands_ok("mmx_gemm_rows_f16", a_dev, wh_dev, c_dev, N, K, 8)) return MMX_ENOTSUP;
     return launch_gemm_rows_half<0>("mmx_gemm_rows_f16", static_cast<hipStream_t>(stream), a_dev, wh_dev, c_dev, rows_dev, count_dev,
                                     cap_rows, N, K, nullptr, nullptr);
 }
@@ -264,7 +194,7 @@ extern "C" int mmx_gemm_rows_bias_f16(const void* a_dev, const void* wh_dev, con
     MMX_CHECK_ARG(a_dev && wh_dev && bias_dev && c_dev && rows_dev && count_dev, "mmx_gemm_rows_bias_f16: null pointer");
     MMX_CHECK_ARG(cap_rows > 0 && N > 0 && K > 0, "mmx_gemm_rows_bias_f16: cap_rows=%d N=%d K=%d", cap_rows, N, K);
     MMX_CHECK_ARG(act_dev != c_dev, "mmx_gemm_rows_bias_f16: the activation needs a buffer of its own");
-    if (!half_operands_ok("mmx_gemm_rows_bias_f16", a_dev, wh_dev, c_dev, N, K)) return MMX_ENOTSUP;
+    if (!rows_operands_ok("mmx_gemm_rows_bias_f16", a_dev, wh_dev, c_dev, N, K, 8)) return MMX_ENOTSUP;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (act_dev)
         return launch_gemm_rows_half<2>("mmx_gemm_rows_bias_f16", s, a_dev, wh_dev, c_dev, rows_dev, count_dev, cap_rows, N, K, bias_dev,
@@ -274,3 +204,4 @@ extern "C" int mmx_gemm_rows_bias_f16(const void* a_dev, const void* wh_dev, con
 }
 
 extern "C" int mmx_text_live_rows_half_enabled(void) { return g_text_live_rows_half && mmx_text_live_rows_fwd_enabled(); }
+#endif

@@ -3,23 +3,15 @@
 // token, so every gradient row past it is an exact zero; 89 % of the rows at caption lengths), plus the kernel that builds the list.
 //
 // The product uses the tiles of bmm_f32_tiles.hip (k-fastest A tile read with one ds_read_b128 per four MFMA steps, n-fastest B tile, 16-byte
-// global loads, two LDS stages with one barrier per K slab and PF slabs requested ahead into registers); its K loop is its own (see the
-// kernel).  What differs:
-//   * M is a DEVICE-side count: the grid is sized for the capacity (every row of the dense tensor), a workgroup whose row tile starts
-//     at or beyond the count returns at once.  Nothing is read back, the launch is the same for every input (hipGraph replays it).
-//   * a thread's A row address goes through the list once, before the K loop; output rows are scattered back to the same dense
-//     layout, unlisted rows are neither read nor written.
+// global loads, two LDS stages with one barrier per K slab and PF slabs requested ahead into registers); its K loop, the row list and
+// the epilogue are those of gemm_rows_core.h, shared with gemm_rows_f16.hip.  What differs from bmm_f32_tiles.hip besides them:
 //   * few rows must still spread over the chip: TM = 32 rows x 64 columns per workgroup, the four waves as 2 column halves x 2 shares of
 //     every K slab (their accumulators meet in LDS at the end, added in a fixed order); 32 x 32: four shares of one MFMA tile, twice the
 //     workgroups; TM = 64 is the 2 x 2 layout of bmm_f32_tiles.hip.
-//   * workgroups are NOT made XCD-contiguous: the live tiles are the first few of the capacity grid, and the plain round-robin spreads
-//     exactly those over the eight XCDs.
 // W is the nn.Linear parameter as stored ([out, in] = [K, N] row-major here), used as x @ weight like ops.backward_gemm.
-#include "mmx_common.h"
+#include "gemm_rows_core.h"
 
 namespace mmx {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static int g_text_live_rows = 1;   // option "text_live_rows": 1 (default) the row-list backward route is offered | 0: mmx_live_rows declines
 static int g_gemm_rows_tm = 32;    // option "gemm_rows_tm": rows per workgroup tile, 32 (default) or 64 (A / B runs)
@@ -62,19 +54,7 @@ __global__ __launch_bounds__(256) void live_rows_kernel(const long long* __restr
     if (threadIdx.x == 0) *count = base;
 }
 
-// EPI: what happens to a finished row of the product on its way out.  0: stored as it is (the backward's input-gradient GEMMs) |
-// 1: + bias[n] (a forward nn.Linear, W then being the cached [in, out] copy of the weight) | 2: + bias[n], stored to C, and
-// QuickGELU of it stored to C2 (c_fc: the backward's tape wants the pre-activation, c_proj the activation; quick_gelu_f is the
-// device function of quick_gelu_fwd_kernel, so C2 has the bits ops.quick_gelu_fwd(C) would have).
-//
-// The K loop is a software pipeline without a predicate in its steady state:
-//   * global loads are issued unconditionally, PF slabs ahead, from an address clamped into the tensor (row 0 for a tile row
-//     that names no dense row, the last chunk / last row of K past the end); what must not count is replaced by zeros when the
-//     registers go to LDS.  No branch surrounds a load, so the wait in front of the ds_write is a counted vmcnt.
-//   * a wave holds the MFMA operands of the current slab in registers.  It issues the first half of the slab's MFMAs, passes the
-//     one barrier of the slab (the next slab is then complete in the other LDS stage), requests the next slab's operands and
-//     issues the second half of the MFMAs while those reads are under way.
-//   * the last slab is peeled out of the loop (nothing left to stash or to read ahead).
+// The fp32 operands on the skeleton of gemm_rows_core.h.  EPI 1 / 2 (+ bias): W is the cached [in, out] copy of the nn.Linear weight.
 template <int TM, int TN, int BK, int PF, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __restrict__ A, const float* __restrict__ W,
                                                                float* __restrict__ C, const int* __restrict__ rows,
@@ -95,17 +75,10 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave % WC, wr = (wave / WC) % WR, wk = wave / (WC * WR);
-    const int M = min(*count, cap);
-    const int tiles_n = (N + TN - 1) / TN;
-    const int bx = blockIdx.x % tiles_n, by = blockIdx.x / tiles_n;
-    const int m0 = by * TM, n0 = bx * TN;
-    if (m0 >= M) return;                             // (workgroup-uniform: no barrier has been reached)
-
-    auto dense_row = [&](int gm) {
-        const int r = gm < M ? rows[gm] : -1;
-        return static_cast<unsigned>(r) < static_cast<unsigned>(cap) ? r : -1;   // an id outside the tensor is no row at all
-    };
-    if (tid < TM) rid[tid] = dense_row(m0 + tid);    // (published by the barrier in front of the first slab)
+    const RowsTilePos p = rows_tile_pos<TM, TN>(rows, count, cap, N);
+    if (p.empty()) return;
+    p.publish<TM>(rid);
+    const int m0 = p.m0, n0 = p.n0;
 
     f32x16 acc;
 #pragma unroll
@@ -118,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
     const float* pa[CA];
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
-        const int arow = dense_row(m0 + ar + i * RA);
+        const int arow = p.dense_row(m0 + ar + i * RA);
         oka[i] = arow >= 0;
         pa[i] = A + static_cast<int64_t>(oka[i] ? arow : 0) * K;
     }
@@ -166,65 +139,8 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
             for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[g][t], f.b[g][t], acc, 0, 0, 0);
     };
 
-    const int nslab = (K + BK - 1) / BK;
-    fetch(0, ring[0]);
-    stash(0, 0, ring[0]);
-#pragma unroll
-    for (int j = 1; j <= PF; ++j) fetch(j, ring[j % PF]);   // slabs 1 .. PF in flight (set 0 is free again)
-    lds_barrier();
-    Frag cur;
-    read_frag(cur, 0);
-    // slab s: stash slab s + 1 (every wave left stage (s + 1) & 1, slab s - 1, before the barrier of slab s - 1: lds_barrier() waits
-    // for the wave's reads), half of the MFMAs, the barrier, the reads of slab s + 1, the other half
-    auto step = [&](int s, Slab& x, bool refill) {
-        stash((s + 1) & 1, s + 1, x);
-        if (refill) fetch(s + 1 + PF, x);
-        mfma_half(cur, 0);
-        lds_barrier();
-        Frag nxt;
-        read_frag(nxt, (s + 1) & 1);
-        mfma_half(cur, 1);
-        cur = nxt;
-    };
-    int s = 0;
-    for (; s + PF < nslab; s += PF)                  // steady state: one basic block, no test between the PF steps
-#pragma unroll
-        for (int j = 0; j < PF; ++j) step(s + j, ring[(j + 1) % PF], true);
-#pragma unroll
-    for (int j = 0; j < PF - 1; ++j) {               // at most PF - 1 steps are left, and nothing they would request is inside K
-        if (s + j + 1 >= nslab) break;
-        step(s + j, ring[(j + 1) % PF], false);
-    }
-    mfma_half(cur, 0);
-    mfma_half(cur, 1);
-    if constexpr (WK > 1) {                          // the k shares of a tile meet: wk > 0 hand their accumulators to wk = 0, added in order
-        const int tile = wr * WC + wc;
-        if (wk > 0)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) red[(((wk - 1) * WR * WC + tile) * 16 + v) * 64 + lane] = acc[v];
-        lds_barrier();
-        if (wk > 0) return;
-#pragma unroll
-        for (int q = 0; q < WK - 1; ++q)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[v] += red[((q * WR * WC + tile) * 16 + v) * 64 + lane];
-    }
-    const int gn = n0 + wc * 32 + li;
-    if (m0 + wr * 32 >= M || gn >= N) return;
-    float bv = 0.f;
-    if constexpr (EPI != 0) bv = bias[gn];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int r = rid[wr * 32 + (v >> 2) * 8 + lg * 4 + (v & 3)];
-        if (r < 0) continue;
-        if constexpr (EPI == 0) {
-            C[static_cast<int64_t>(r) * N + gn] = acc[v];
-        } else {
-            const float m = acc[v] + bv;
-            C[static_cast<int64_t>(r) * N + gn] = m;
-            if constexpr (EPI == 2) C2[static_cast<int64_t>(r) * N + gn] = quick_gelu_f(m);
-        }
-    }
+    rows_k_pipeline<PF, false, Frag>(ring, (K + BK - 1) / BK, fetch, stash, read_frag, mfma_half);
+    rows_finish<EPI, WK, WR * WC>(acc, red, p, rid, wr, wc, wk, wr * WC + wc, lane, N, C, bias, C2);
 }
 
 // The tile of a launch: rows x columns per workgroup, chosen from the options and the shape only (the live count stays on the device).
@@ -234,14 +150,14 @@ static RowsTile rows_tile(int N, int K) {
     const int tn = g_gemm_rows_tn ? g_gemm_rows_tn : 64;
     return {32, tn};
 }
-static int64_t rows_grid(RowsTile t, int cap_rows, int N) {
-    return static_cast<int64_t>((N + t.tn - 1) / t.tn) * ((cap_rows + t.tm - 1) / t.tm);
-}
 
+}  // namespace mmx
+
+#ifndef MMX_GEMM_ROWS_EMU   // (the host emulation takes the kernel, not the launches)
+namespace mmx {
 template <int EPI>
-static void launch_gemm_rows(RowsTile t, int64_t wgs, hipStream_t s, const float* A, const float* W, float* C, const int* rows,
+static void launch_gemm_rows(RowsTile t, unsigned g, hipStream_t s, const float* A, const float* W, float* C, const int* rows,
                              const int* count, int cap_rows, int N, int K, const float* bias, float* C2) {
-    const unsigned g = static_cast<unsigned>(wgs);
     if (t.tm == 64)
         gemm_rows_f32_kernel<64, 64, 32, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
     else if (t.tn == 32)
@@ -271,14 +187,10 @@ extern "C" int mmx_gemm_rows_f32(const void* a_dev, const void* w_dev, void* c_d
                                  int cap_rows, int N, int K, void* stream) {
     MMX_CHECK_ARG(a_dev && w_dev && c_dev && rows_dev && count_dev, "mmx_gemm_rows_f32: null pointer");
     MMX_CHECK_ARG(cap_rows > 0 && N > 0 && K > 0, "mmx_gemm_rows_f32: cap_rows=%d N=%d K=%d", cap_rows, N, K);
-    if (N % 4 || K % 4 ||
-        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(c_dev)) & 15u)) {
-        set_error("mmx_gemm_rows_f32: N=%d and K=%d must be multiples of 4 and the operands 16-byte aligned", N, K);
-        return MMX_ENOTSUP;
-    }
+    if (!rows_operands_ok("mmx_gemm_rows_f32", a_dev, w_dev, c_dev, N, K, 4)) return MMX_ENOTSUP;
     const RowsTile tm = rows_tile(N, K);
-    const int64_t wgs = rows_grid(tm, cap_rows, N);
-    MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
+    const unsigned wgs = rows_grid("mmx_gemm_rows_f32", tm.tm, tm.tn, cap_rows, N);
+    if (!wgs) return MMX_EINVAL;
     launch_gemm_rows<0>(tm, wgs, static_cast<hipStream_t>(stream), static_cast<const float*>(a_dev), static_cast<const float*>(w_dev),
                         static_cast<float*>(c_dev), static_cast<const int*>(rows_dev), static_cast<const int*>(count_dev), cap_rows, N, K,
                         nullptr, nullptr);
@@ -293,14 +205,10 @@ extern "C" int mmx_gemm_rows_bias_f32(const void* a_dev, const void* wt_dev, con
     MMX_CHECK_ARG(a_dev && wt_dev && bias_dev && c_dev && rows_dev && count_dev, "mmx_gemm_rows_bias_f32: null pointer");
     MMX_CHECK_ARG(cap_rows > 0 && N > 0 && K > 0, "mmx_gemm_rows_bias_f32: cap_rows=%d N=%d K=%d", cap_rows, N, K);
     MMX_CHECK_ARG(act_dev != c_dev, "mmx_gemm_rows_bias_f32: the activation needs a buffer of its own");
-    if (N % 4 || K % 4 ||
-        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(wt_dev) | reinterpret_cast<uintptr_t>(c_dev)) & 15u)) {
-        set_error("mmx_gemm_rows_bias_f32: N=%d and K=%d must be multiples of 4 and the operands 16-byte aligned", N, K);
-        return MMX_ENOTSUP;
-    }
+    if (!rows_operands_ok("mmx_gemm_rows_bias_f32", a_dev, wt_dev, c_dev, N, K, 4)) return MMX_ENOTSUP;
     const RowsTile tm = rows_tile(N, K);
-    const int64_t wgs = rows_grid(tm, cap_rows, N);
-    MMX_CHECK_ARG(wgs < (1ll << 31), "mmx_gemm_rows_bias_f32: cap_rows=%d x N=%d is too large a grid", cap_rows, N);
+    const unsigned wgs = rows_grid("mmx_gemm_rows_bias_f32", tm.tm, tm.tn, cap_rows, N);
+    if (!wgs) return MMX_EINVAL;
     const float *A = static_cast<const float*>(a_dev), *W = static_cast<const float*>(wt_dev), *bias = static_cast<const float*>(bias_dev);
     const int *rows = static_cast<const int*>(rows_dev), *count = static_cast<const int*>(count_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -311,3 +219,4 @@ extern "C" int mmx_gemm_rows_bias_f32(const void* a_dev, const void* wt_dev, con
     MMX_LAUNCH_CHECK("gemm_rows_f32_kernel<bias>");
     return MMX_OK;
 }
+#endif

@@ -398,15 +398,22 @@ def layernorm_bwd_add_bf16(dy, x, mean, rstd, gamma, d_res=None, want_f32=True):
 _GEMM_WEIGHTS = {}   # id(parameter) -> {dtype: (version, converted copy)}; the entry is dropped when the parameter dies
 
 
-def _converted(weight, dtype):
+def _cached_weight(weight, key, make):
+    """``make()``'s tensor for ``weight`` under ``key``: built again after an in-place modification of the parameter or its move to
+    another device, ``(copy, True)`` then."""
     per_weight = _GEMM_WEIGHTS.get(id(weight))
     if per_weight is None:
         per_weight = _GEMM_WEIGHTS[id(weight)] = {}
         weakref.finalize(weight, _GEMM_WEIGHTS.pop, id(weight), None)
-    hit = per_weight.get(dtype)
-    if hit is None or hit[0] != weight._version or hit[1].device != weight.device:
-        hit = per_weight[dtype] = (weight._version, weight.detach().to(dtype))
-    return hit[1]
+    hit = per_weight.get(key)
+    fresh = hit is None or hit[0] != weight._version or hit[1].device != weight.device
+    if fresh:
+        hit = per_weight[key] = (weight._version, make())
+    return hit[1], fresh
+
+
+def _converted(weight, dtype):
+    return _cached_weight(weight, dtype, lambda: weight.detach().to(dtype))[0]
 
 
 def transposed_weight(weight):
@@ -414,34 +421,22 @@ def transposed_weight(weight):
     a Linear with few outputs and many inputs (DETR's ``linear2``: 256 -> 2048 on the way back) gets a poor library kernel in its
     natural NN layout (64x64x16 tiles: 140 us at 9500 rows); as ``F.linear(dY, W^T)`` the heuristic picks a 256-wide one
     (104 us) -- profiles/r03_detr_probe.txt."""
-    per_weight = _GEMM_WEIGHTS.get(id(weight))
-    if per_weight is None:
-        per_weight = _GEMM_WEIGHTS[id(weight)] = {}
-        weakref.finalize(weight, _GEMM_WEIGHTS.pop, id(weight), None)
-    hit = per_weight.get("t")
-    if hit is None or hit[0] != weight._version or hit[1].device != weight.device:
-        hit = per_weight["t"] = (weight._version, weight.detach().t().contiguous())
-    return hit[1]
+    return _cached_weight(weight, "t", lambda: weight.detach().t().contiguous())[0]
 
 
 def sign_split_weight(weight, transposed=False):
     """Cached ``[clamp(W, min=0) | clamp(W, max=0)]`` (``[out, 2 in]``, until the parameter is modified in place): the weight
     operand of both GEMMs of the fused ``Linear.relprop`` (``lrp_linear``); ``transposed``: its contiguous ``[2 in, out]`` form."""
-    per_weight = _GEMM_WEIGHTS.get(id(weight))
-    if per_weight is None:
-        per_weight = _GEMM_WEIGHTS[id(weight)] = {}
-        weakref.finalize(weight, _GEMM_WEIGHTS.pop, id(weight), None)
-    hit = per_weight.get("pn")
-    if hit is None or hit[0] != weight._version or hit[1].device != weight.device:
+    def split():
         w = weight.detach().float()
-        hit = per_weight["pn"] = (weight._version, torch.cat((w.clamp(min=0), w.clamp(max=0)), dim=1).contiguous())
-        per_weight.pop("pnT", None)
+        return torch.cat((w.clamp(min=0), w.clamp(max=0)), dim=1).contiguous()
+
+    pn, fresh = _cached_weight(weight, "pn", split)
+    if fresh:
+        _GEMM_WEIGHTS[id(weight)].pop("pnT", None)   # (the transposed copy follows its source)
     if not transposed:
-        return hit[1]
-    hit_t = per_weight.get("pnT")
-    if hit_t is None or hit_t[0] != weight._version or hit_t[1].device != weight.device:
-        hit_t = per_weight["pnT"] = (weight._version, hit[1].t().contiguous())
-    return hit_t[1]
+        return pn
+    return _cached_weight(weight, "pnT", lambda: pn.t().contiguous())[0]
 
 
 def lrp_fusable(*tensors):
@@ -778,14 +773,7 @@ def transposed_half_weight(weight):
     """Cached fp16 copy of ``weight.t().contiguous()`` (beside ``transposed_weight``, until the parameter is modified in place): the
     k-fastest operand ``mmx_gemm_rows_f16`` wants for the backward's ``x @ weight``.  The rounding is ``convert_weights``'
     (CLIP/clip/model.py:381-402); transposing moves the rounded values, it does not change them."""
-    per_weight = _GEMM_WEIGHTS.get(id(weight))
-    if per_weight is None:
-        per_weight = _GEMM_WEIGHTS[id(weight)] = {}
-        weakref.finalize(weight, _GEMM_WEIGHTS.pop, id(weight), None)
-    hit = per_weight.get("t16")
-    if hit is None or hit[0] != weight._version or hit[1].device != weight.device:
-        hit = per_weight["t16"] = (weight._version, weight.detach().t().to(torch.float16).contiguous())
-    return hit[1]
+    return _cached_weight(weight, "t16", lambda: weight.detach().t().to(torch.float16).contiguous())[0]
 
 
 def gemm_rows(x, weight, live, out=None, dtype=torch.float32):
