@@ -379,7 +379,8 @@ def test_detr_ni950_rules_vs_oracle():
 def test_bf16_backward_third_generation_equals_second(N, B, need):
     """``attention_bf16_v3.hip`` (shared forward + bf16 gradient stream + row-relevancy mode: the cfg-5 path; bf16 images of
     the shared operands prepared once per call, padded / transposed probability images, 4 waves per SIMD) runs the SAME
-    tile arithmetic in the SAME order as the second generation (``attention_bf16.hip``, pinned on the oracle above), so dq /
+    tile arithmetic in the SAME order as the second generation (``attention_bf16.hip``, pinned on the oracle above and, per element on
+    counted float64 bounds with all three generations held to the reference directly, by ``tests/test_gpu_attention_bf16.py``), so dq /
     dk / dv (bf16) agree up to isolated last-place flips and the carried relevancy row to 1e-6 (``attn_bf16_v3`` = 0 is the
     second generation, 2 the third-generation pair, 3 -- the default since round 6 -- the third-generation query side with the
     fourth-generation key side ``attn_bwd_kv_v4_kernel``)."""
