@@ -7,6 +7,8 @@ forward, ONE all-gather of the per-sample step accuracies at the end.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29513 \\
         examples/visualbert_pert_eval.py --num-samples 10000 --text                   # one rank per GPU, RCCL
 
+``--explain-batch B`` (``raw_attn`` / ``attn_gradcam`` / ``rollout`` only; default 1, the per-item route): the relevancy rows of B items come from
+ONE padded batch (``SelfAttentionGenerator.generate_*_batch``, ``unpad_row``); every item is then perturbed as before.
 ``--reference-exact``: the reference loop stops only AFTER item ``num_samples + 1`` (its test is ``i > num_samples``) and
 still divides the accumulated accuracies by ``num_samples``; with the flag the printed numbers use
 exactly that accounting, without it ``num_samples`` items are evaluated and averaged.
@@ -70,6 +72,9 @@ def main():
     ap.add_argument("--positive", dest="is_positive_pert", action="store_true", help="alias of --is-positive-pert True")
     ap.add_argument("--reference-exact", action="store_true")
     ap.add_argument("--resume-dir", default=None)
+    ap.add_argument("--explain-batch", type=int, default=1,
+                    help="raw_attn / attn_gradcam / rollout only: explain this many items in ONE padded batch (one forward [+ one "
+                         "backward] and two or three launches), then perturb each item as before.  1 (default): one item per call")
     args = ap.parse_args()
     args.text, args.positive = args.is_text_pert, args.is_positive_pert
     rank, world, dev, gather_dev = sharding.init_evaluator_process()
@@ -89,9 +94,35 @@ def main():
                    "partial_lrp": gen.generate_partial_lrp, "raw_attn": gen.generate_raw_attn,
                    "attn_gradcam": gen.generate_attn_gradcam, "rollout": gen.generate_rollout}[args.method]
 
+    explain_batch = {"raw_attn": gen.generate_raw_attn_batch, "attn_gradcam": gen.generate_attn_gradcam_batch,
+                     "rollout": gen.generate_rollout_batch}.get(args.method) if args.explain_batch > 1 else None
+    ahead = {}                                  # id -> (item on the device, its relevancy row), explained a batch at a time
+    todo = []
+
+    def explained(k):
+        """Item ``k`` and its row.  The batched route explains the next ``--explain-batch`` ids of this rank's shard, in the order
+        ``evaluate`` will ask for them, in one padded batch (``synthetic_item`` pads every question to the same width)."""
+        if explain_batch is None:
+            item = {name: t.to(dev) for name, t in synthetic_item(k).items()}
+            return item, method_expl(dict(item)).detach()
+        if k not in ahead:
+            ahead.clear()
+            if not todo:                                # this rank's ids that ``evaluate`` will visit: its shard minus what a resumed
+                done = store.done() if store is not None else ()          # run already holds (read once, as ``evaluate`` does)
+                todo.extend(j for j in order if j not in done)
+            at = todo.index(k)
+            chunk = todo[at:at + args.explain_batch]
+            items = [{name: t.to(dev) for name, t in synthetic_item(j).items()} for j in chunk]
+            batch = {name: torch.cat([it[name] for it in items]) for name in ("input_ids", "input_mask", "segment_ids", "image_feature_0")}
+            scores = explain_batch(batch).detach()
+            lens = batch["input_mask"].sum(1).tolist()                    # one host read per batch (the perturbation reads it per item)
+            width = batch["input_mask"].shape[1]
+            for b, (j, it) in enumerate(zip(chunk, items)):
+                ahead[j] = (it, vb.unpad_row(scores, b, int(lens[b]), padded_text=width))
+        return ahead.pop(k)
+
     def step_accuracies_of(k):
-        item = {name: t.to(dev) for name, t in synthetic_item(k).items()}
-        cam = method_expl(dict(item)).detach()
+        item, cam = explained(k)
         run = pert.perturbation_text if args.text else pert.perturbation_image
         return pert.accuracy(run(item, cam, args.positive), item["targets"][0])
 
@@ -99,6 +130,8 @@ def main():
            "positive": bool(args.positive), "reference_exact": bool(args.reference_exact)}
     store = sharding.PartialScores(args.resume_dir, rank, config=cfg) if args.resume_dir else None
     ids = list(range(args.dataset_len))         # the loader order (mmf's sampler is sequential for evaluation)
+    n_eval = min(len(ids), args.num_samples + 1 if args.reference_exact else args.num_samples)
+    order = list(sharding.shard_indices(ids[:n_eval]))                    # this rank's ids, in the order ``evaluate`` visits them
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     table, printed = evaluate(ids, step_accuracies_of, args.num_samples, args.reference_exact, store=store, device=gather_dev)

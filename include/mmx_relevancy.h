@@ -425,6 +425,51 @@ int mmx_lxmert_rollout(const void* const* text_attn, int n_text, const void* con
                        void* R_ti_dev, void* R_ii_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The attention-only baselines of the single-stream (VisualBERT-style) model for a PADDED batch of ragged questions
+ * (csrc/selfattn_baselines.hip).  The reference explains one question per call and trims its text padding
+ * (VisualBERT/mmf/models/visual_bert.py:578-588), so it never pads; here every slab is the fp32 [B, H, N, N] capture slab of a padded
+ * batch whose sequence is [T text positions | V regions], N = T + V, and text_len / vis_len are DEVICE arrays of B int32 (NULL = the
+ * full extent), CLAMPED inside the kernel to 2..T and 1..V before any use.  Sample b's live index set is
+ * L_b = [0, t_b) u [T, T + v_b), n_b = t_b + v_b -- the text padding sits in the MIDDLE of the sequence -- and all three methods return
+ * ONE row of their N x N map: the row of the token the 'vqa' pooler reads, c_b = t_b - 2 (cls_index = input_mask.sum(1) - 2,
+ * VisualBERT/mmf/models/transformers/backends/ExplanationGenerator.py:160, :178, :209).  Every output is [B, N] fp32 in the padded
+ * layout, exact zero outside L_b and at column c_b (cls_per_token_score[:, cls_index] = 0, :162, :180, :211).  Fixed summation
+ * orders, no atomics: two calls give the same bits, and sample b's output depends neither on B nor on its position in the batch.
+ * Limits: T >= 2, V >= 1, N <= 256, tables of at most MMX_BASELINES_MAX_TABLE slabs.  Every argument is checked before any HIP
+ * call: null required pointers, B / H <= 0, sizes outside the limits, a table that is too long or has a null entry, a workspace that
+ * is too small or not 16-byte aligned, an output or workspace that overlaps an input or the other one return MMX_EINVAL with a
+ * message in mmx_last_error().  The workspace queries return 0 for arguments the entries refuse.
+ *
+ * mmx_selfattn_row_live:
+ *   grad_dev == NULL: raw attention (ExplanationGenerator.py:155-166): out[b, j] = (sum_h attn[b, h, c_b, j]) / H for j in L_b; one
+ *                     launch that reads one row per head; no workspace (workspace_dev may be NULL).
+ *   grad_dev given:   attention GradCAM (ExplanationGenerator.py:200-211) on the live block only:
+ *                     w[b, h] = (sum of grad[b, h] over L_b x L_b) / float(n_b^2) (the sum first, then one division),
+ *                     cam = max(0, (sum_h attn[b, h] w[b, h]) / H) on L_b x L_b (a NaN stays a NaN), mn / mx its minimum / maximum there,
+ *                     out[b, j] = (cam[c_b, j] - mn) / (mx - mn): a plain division, NaN when mx == mn as in the reference.  The
+ *                     gradient of a padded batch is not zero at padded keys and padded query rows hold garbage: sums, divisor, minimum
+ *                     and maximum use L_b only.  Three plain launches ordered by the stream: B x H workgroups for w, B x ceil(N / 8)
+ *                     for cam / min / max of a strip of rows, B for the row; attn and grad are each read at most once.
+ *                     workspace: mmx_selfattn_row_live_workspace_bytes(B, H, T, V) bytes, 16-byte aligned, caller-owned.
+ *
+ * mmx_selfattn_rollout_row: generate_rollout (ExplanationGenerator.py:168-180) with compute_rollout_attention (:5-17), which adds I,
+ *   does NOT normalise the rows and multiplies from the left.  Only row c_b of (I + A_{L-1}) ... (I + A_0) is returned, A_l the head
+ *   mean (sum_h attn_l[b, h]) / H, so a row vector is carried from the top table entry down: x = e_{c_b}; x <- x + x . A_l for
+ *   l = n_layers - 1 ... 0.  attn_table: HOST table of n_layers >= 1 device slabs, already sliced to start_layer:.
+ *   Two plain launches: B x n_layers x ceil(N^2 / 2048) workgroups take the head means into the workspace (every slab read once, 16-byte
+ *   loads, chunks of padded query rows skipped; rows of the workspace are ceil(N / 4) * 4 floats apart); one workgroup per sample then
+ *   runs the n_layers vector-matrix steps in plain fp32 FMA with x in LDS.  Its row loads are unconditional, aligned and from clamped
+ *   addresses, so eight rows per lane -- the next layer's included -- stay in flight behind counted waits (vmcnt(7)).
+ *   workspace: mmx_selfattn_rollout_row_workspace_bytes(n_layers, B, T, V) bytes, 16-byte aligned, caller-owned, stream-ordered. */
+size_t mmx_selfattn_row_live_workspace_bytes(int B, int H, int T, int V);
+int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int T, int V,
+                          const void* text_len_dev, const void* vis_len_dev, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+size_t mmx_selfattn_rollout_row_workspace_bytes(int n_layers, int B, int T, int V);
+int mmx_selfattn_rollout_row(const void* const* attn_table, int n_layers, int B, int H, int T, int V, const void* text_len_dev,
+                             const void* vis_len_dev, void* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * On-device post-processing of relevancy maps (one workgroup per map, no host round trip):
  *  mmx_heatmap_bilinear_minmax: [B, g, g] patch maps -> bilinear upsample to [B, S, S] (torch interpolate semantics,
  *    align_corners=False) + min-max normalisation; replaces CLIP_explainability.ipynb cell 7:14-18 and

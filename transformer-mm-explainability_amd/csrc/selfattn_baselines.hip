@@ -1,0 +1,394 @@
+// The attention-only baselines of the single-stream (VisualBERT-style) model for a PADDED batch of ragged questions: raw attention,
+// attention GradCAM and rollout (VisualBERT/mmf/models/transformers/backends/ExplanationGenerator.py:155-166, :200-211, :168-180 with
+// :5-17).  All three return ONE row of an N x N map -- the row of the token the 'vqa' pooler reads, c_b = t_b - 2 -- so nothing here
+// ever forms an N x N product.
+//
+// The sequence of a padded batch is [text | text padding | regions | region padding]: N = T + V, sample b's live index set is
+// L_b = [0, t_b) u [T, T + v_b), n_b = t_b + v_b.  Lengths are device int32 arrays, clamped to 2..T and 1..V before any use.  The
+// probability slabs are exact zero at padded key columns, the GRADIENT slabs are not, and padded query rows hold whatever the body
+// computed for a pad token: every sum, divisor, minimum and maximum is taken over L_b x L_b only, and every output is exact zero
+// outside L_b and at column c_b.
+//
+//   sa_raw_row_kernel      one workgroup per sample: (sum_h P[b, h, c_b, j]) / H, one row per head.
+//   sa_gradcam_w_kernel    workgroup (b, h): w[b, h] = (sum of G[b, h] over L_b x L_b) / float(n_b^2) -> workspace.
+//   sa_gradcam_cam_kernel  workgroup (b, strip of 8 rows): cam = relu((sum_h P[b, h] w[b, h]) / H) on the strip's live rows, its
+//                          minimum and maximum and -- in the strip that holds it -- row c_b -> workspace.
+//   sa_gradcam_out_kernel  one workgroup per sample: the minimum / maximum over the strips, (row - mn) / (mx - mn).
+//   sa_rollout_means_kernel  workgroup (b, layer, strip of 2048 floats): the head mean of every chunk that touches a live row, read
+//                          with 16-byte loads, heads in order, written once to the workspace.
+//   sa_rollout_row_kernel  one workgroup per sample: x = e_c, x <- x + x . A_l from the top table entry down; x sits in LDS, wave w
+//                          takes the live rows w, w + 4, ... (a lane owns four columns).  Every lane loads 16 aligned bytes per row
+//                          UNCONDITIONALLY from a clamped address (lanes past the row's end repeat its last chunk, items past the
+//                          live rows repeat the last live row times zero), so eight loads and eight FMAs form one basic block and
+//                          the waits are counted: a ring of eight rows per lane stays in flight, across the layer boundary too.
+// Plain launches ordered by the stream (no tickets, no spinning), fixed summation orders, no atomics: two runs give the same bits,
+// and sample b's result depends neither on B nor on b.
+#include "mmx_common.h"
+
+namespace mmx {
+
+constexpr int kSaMaxN = 256;                    // T + V (128 text positions + 100 regions must fit)
+constexpr int kSaMaxTable = MMX_BASELINES_MAX_TABLE;
+constexpr int kSaThreads = 256;
+constexpr int kSaWaves = kSaThreads / 64;
+constexpr int kSaStripRows = 8;                 // rows of one cam / min-max workgroup (two per wave)
+constexpr int kSaMeanChunks = 2;                // 16-byte chunks per thread of a head-mean workgroup
+constexpr int kSaMeanStrip = kSaThreads * kSaMeanChunks * 4;     // floats per head-mean workgroup
+constexpr int kSaRing = 8;                      // row loads in flight per lane of the row kernel
+
+// the clamped lengths of sample b: NEVER used unclamped
+__device__ __forceinline__ int sa_text_len(const int* len, int b, int T) { return len ? min(max(len[b], 2), T) : T; }
+__device__ __forceinline__ int sa_vis_len(const int* len, int b, int V) { return len ? min(max(len[b], 1), V) : V; }
+__device__ __forceinline__ bool sa_live(int j, int t, int T, int v) { return j < t || (j >= T && j < T + v); }
+// floats between two rows of a head-mean matrix in the rollout workspace: N rounded up to whole 16-byte chunks
+__host__ __device__ __forceinline__ int sa_row_stride(int N) { return (N + 3) & ~3; }
+// the k-th live index, k < t + v
+__device__ __forceinline__ int sa_live_at(int k, int t, int T) { return k < t ? k : T + (k - t); }
+
+__device__ __forceinline__ float wave_sum_sa(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// torch's min / max: a NaN wins
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
+
+// columns 4 lane .. 4 lane + 3 of one row of N floats (zeros beyond N); p points at the row
+__device__ __forceinline__ f32x4 sa_row4(const float* __restrict__ p, int lane, int N) {
+    const int j0 = lane * 4;
+    f32x4 r = {0.f, 0.f, 0.f, 0.f};
+    if (j0 + 3 < N) {
+        r = ldg4_u(p + j0);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (j0 + e < N) r[e] = p[j0 + e];
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(kSaThreads) void sa_raw_row_kernel(const float* __restrict__ attn, float* __restrict__ out, int H, int T,
+                                                                int V, const int* text_len, const int* vis_len) {
+    const int b = blockIdx.x, j = threadIdx.x, N = T + V;
+    if (j >= N) return;
+    const int t = sa_text_len(text_len, b, T), v = sa_vis_len(vis_len, b, V), c = t - 2;
+    float r = 0.f;
+    if (sa_live(j, t, T, v) && j != c) {
+        const float* P = attn + (static_cast<int64_t>(b) * H * N + c) * N + j;
+        float s = 0.f;
+        for (int h = 0; h < H; ++h) s += P[static_cast<int64_t>(h) * N * N];
+        r = s / static_cast<float>(H);
+    }
+    out[static_cast<int64_t>(b) * N + j] = r;
+}
+
+__global__ __launch_bounds__(kSaThreads) void sa_gradcam_w_kernel(const float* __restrict__ grad, float* __restrict__ w, int T, int V,
+                                                                  const int* text_len, const int* vis_len, int H) {
+    __shared__ float part[kSaWaves];
+    const int bh = blockIdx.x, b = bh / H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = T + V;
+    const int t = sa_text_len(text_len, b, T), v = sa_vis_len(vis_len, b, V), n = t + v;
+    const float* G = grad + static_cast<int64_t>(bh) * N * N;
+    bool lv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lv[e] = sa_live(lane * 4 + e, t, T, v);
+    float s = 0.f;
+    for (int k = wave; k < n; k += kSaWaves) {                       // live rows only; padded columns are loaded and dropped
+        const f32x4 g = sa_row4(G + static_cast<int64_t>(sa_live_at(k, t, T)) * N, lane, N);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += lv[e] ? g[e] : 0.f;
+    }
+    s = wave_sum_sa(s);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+        float total = part[0];
+#pragma unroll
+        for (int u = 1; u < kSaWaves; ++u) total += part[u];
+        w[bh] = total / static_cast<float>(n * n);                   // the sum first, then ONE division by the live count
+    }
+}
+
+__global__ __launch_bounds__(kSaThreads) void sa_gradcam_cam_kernel(const float* __restrict__ attn, const float* __restrict__ w,
+                                                                    float* __restrict__ mm, float* __restrict__ row, int H, int T,
+                                                                    int V, int strips, const int* text_len, const int* vis_len) {
+    __shared__ float p_mn[kSaWaves], p_mx[kSaWaves];
+    const int b = blockIdx.x / strips, s = blockIdx.x - b * strips;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, N = T + V;
+    const int t = sa_text_len(text_len, b, T), v = sa_vis_len(vis_len, b, V), c = t - 2;
+    const float* P = attn + static_cast<int64_t>(b) * H * N * N;
+    const float* wb = w + static_cast<int64_t>(b) * H;
+    const float fH = static_cast<float>(H);
+    const float inf = __builtin_inff();
+    bool lv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lv[e] = sa_live(lane * 4 + e, t, T, v);
+    float mn = inf, mx = -inf;
+    for (int i = s * kSaStripRows + wave; i < min((s + 1) * kSaStripRows, N); i += kSaWaves) {
+        if (!sa_live(i, t, T, v)) continue;                          // (wave-uniform)
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < H; ++h) acc += sa_row4(P + (static_cast<int64_t>(h) * N + i) * N, lane, N) * wb[h];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float cam = relu_nan(acc[e] / fH);
+            if (lv[e]) {
+                mn = min_nan(mn, cam);
+                mx = max_nan(mx, cam);
+            }
+            if (i == c && lane * 4 + e < N) row[static_cast<int64_t>(b) * N + lane * 4 + e] = lv[e] ? cam : 0.f;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mn = min_nan(mn, __shfl_xor(mn, off));
+        mx = max_nan(mx, __shfl_xor(mx, off));
+    }
+    if (lane == 0) { p_mn[wave] = mn; p_mx[wave] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int u = 1; u < kSaWaves; ++u) { mn = min_nan(mn, p_mn[u]); mx = max_nan(mx, p_mx[u]); }
+        mm[2 * static_cast<int64_t>(blockIdx.x)] = mn;               // a strip without a live row: +inf / -inf, the neutral pair
+        mm[2 * static_cast<int64_t>(blockIdx.x) + 1] = mx;
+    }
+}
+
+__global__ __launch_bounds__(kSaThreads) void sa_gradcam_out_kernel(const float* __restrict__ mm, const float* __restrict__ row,
+                                                                    float* __restrict__ out, int T, int V, int strips,
+                                                                    const int* text_len, const int* vis_len) {
+    const int b = blockIdx.x, j = threadIdx.x, N = T + V;
+    if (j >= N) return;
+    const int t = sa_text_len(text_len, b, T), v = sa_vis_len(vis_len, b, V), c = t - 2;
+    float r = 0.f;
+    if (sa_live(j, t, T, v) && j != c) {
+        const float* m = mm + 2 * static_cast<int64_t>(b) * strips;
+        float mn = m[0], mx = m[1];
+        for (int s = 1; s < strips; ++s) { mn = min_nan(mn, m[2 * s]); mx = max_nan(mx, m[2 * s + 1]); }
+        r = (row[static_cast<int64_t>(b) * N + j] - mn) / (mx - mn);  // no guard: mx == mn gives NaN, as in the reference
+    }
+    out[static_cast<int64_t>(b) * N + j] = r;
+}
+
+struct SaRolloutArgs {
+    const float* attn[kSaMaxTable];    // [B, H, N, N], already sliced to start_layer:
+    int n_layers, B, H, T, V, strips;
+    const int *text_len, *vis_len;
+    float* ws;                         // [B][n_layers][N][NP] head means, NP = sa_row_stride(N); rows of padded queries and the
+                                       // NP - N floats behind a row are never written, and never used
+    float* out;
+};
+
+__global__ __launch_bounds__(kSaThreads) void sa_rollout_means_kernel(const SaRolloutArgs a) {
+    const int tid = threadIdx.x, N = a.T + a.V, hs = N * N, H = a.H;
+    int w = blockIdx.x;
+    const int s = w % a.strips; w /= a.strips;
+    const int l = w % a.n_layers, b = w / a.n_layers;
+    const int t = sa_text_len(a.text_len, b, a.T), v = sa_vis_len(a.vis_len, b, a.V);
+    const float* __restrict__ src = a.attn[l] + static_cast<int64_t>(b) * H * hs;
+    const int NP = sa_row_stride(N);
+    float* dst = a.ws + (static_cast<int64_t>(b) * a.n_layers + l) * N * NP;
+    const float fH = static_cast<float>(H);
+#pragma unroll
+    for (int u = 0; u < kSaMeanChunks; ++u) {
+        const int p = s * kSaMeanStrip + (u * kSaThreads + tid) * 4;
+        if (p >= hs) continue;
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) any |= p + e < hs && sa_live((p + e) / N, t, a.T, v);
+        if (!any) continue;                                          // a chunk of padded query rows: neither read nor written
+        f32x4 m = {0.f, 0.f, 0.f, 0.f};
+        if (p + 3 < hs) {                                            // the 16-byte loads stay inside the head's own N x N block
+            int h = 0;
+            for (; h + 6 <= H; h += 6) {
+                f32x4 x[6];
+#pragma unroll
+                for (int q = 0; q < 6; ++q) x[q] = ldg4_u(src + static_cast<int64_t>(h + q) * hs + p);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) m += x[q];
+            }
+            for (; h < H; ++h) m += ldg4_u(src + static_cast<int64_t>(h) * hs + p);
+        } else {
+            for (int e = 0; p + e < hs; ++e)
+                for (int h = 0; h < H; ++h) m[e] += src[static_cast<int64_t>(h) * hs + p + e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (p + e < hs) {
+                const int row = (p + e) / N;
+                dst[row * NP + (p + e - row * N)] = m[e] / fH;       // rows of the workspace start on 16-byte boundaries
+            }
+    }
+}
+
+__global__ __launch_bounds__(kSaThreads) void sa_rollout_row_kernel(const SaRolloutArgs a) {
+    __shared__ float x[kSaMaxN];
+    __shared__ float part[kSaWaves][kSaMaxN];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, N = a.T + a.V, NP = sa_row_stride(N), L = a.n_layers;
+    const int64_t ls = static_cast<int64_t>(N) * NP;
+    const int t = sa_text_len(a.text_len, b, a.T), v = sa_vis_len(a.vis_len, b, a.V), n = t + v, c = t - 2;
+    // items of a layer and wave: live rows wave, wave + 4, ..., padded to a multiple of the ring so that a layer ends where an
+    // unrolled block ends; an item past the live rows loads a valid row (the last live one) and is multiplied by zero
+    const int m8 = (((n + kSaWaves - 1) / kSaWaves + kSaRing - 1) / kSaRing) * kSaRing;
+    // every lane loads 16 aligned bytes of its row; lanes past the row's end repeat the last chunk and are dropped at the end
+    const float* base = a.ws + static_cast<int64_t>(b) * L * ls + min(lane * 4, NP - 4);
+    x[tid] = tid == c ? 1.f : 0.f;
+    __syncthreads();
+
+    // the loader walks the flat (layer, item) sequence kSaRing items ahead of the FMAs; past the last layer it repeats layer 0
+    int pl = L - 1, pk = 0;
+    auto fetch = [&](int u) -> f32x4 {
+        const int k = min(wave + kSaWaves * (pk + u), n - 1);
+        return *reinterpret_cast<const f32x4*>(base + max(pl, 0) * ls + static_cast<int64_t>(sa_live_at(k, t, a.T)) * NP);
+    };
+    auto advance = [&]() {
+        pk += kSaRing;
+        if (pk == m8) { pk = 0; --pl; }
+    };
+    f32x4 ring[kSaRing];
+#pragma unroll
+    for (int u = 0; u < kSaRing; ++u) ring[u] = fetch(u);
+    advance();
+    for (int l = L - 1; l >= 0; --l) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int kk0 = 0; kk0 < m8; kk0 += kSaRing) {                // one basic block: eight loads issued, eight rows consumed
+#pragma unroll
+            for (int u = 0; u < kSaRing; ++u) {
+                const int k = wave + kSaWaves * (kk0 + u);
+                const float xi = x[sa_live_at(min(k, n - 1), t, a.T)];
+                acc += ring[u] * (k < n ? xi : 0.f);
+                __builtin_amdgcn_sched_barrier(0);                   // the FMA stays in front of the refill of ITS register: no
+                ring[u] = fetch(u);                                  // renamed ring, no copies (and no drain) at the loop's end
+            }
+            advance();
+        }
+        // the layer is done: x <- x + the four waves' partial rows (the next layer's first rows are already in flight)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[wave][lane * 4 + e] = lane * 4 + e < N ? acc[e] : 0.f;
+        lds_barrier();
+        const float y = x[tid] + ((part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]));
+        x[tid] = sa_live(tid, t, a.T, v) ? y : 0.f;                  // (entry tid is read here by its own thread only)
+        lds_barrier();
+    }
+    if (tid < N) a.out[static_cast<int64_t>(b) * N + tid] = (sa_live(tid, t, a.T, v) && tid != c) ? x[tid] : 0.f;
+}
+
+}  // namespace mmx
+
+using namespace mmx;
+
+static inline size_t sa_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+static inline bool sa_sizes_ok(int T, int V) { return T >= 2 && V >= 1 && T <= kSaMaxN && V <= kSaMaxN && T + V <= kSaMaxN; }
+static inline int sa_cam_strips(int N) { return (N + kSaStripRows - 1) / kSaStripRows; }
+// [a, a + na) and [b, b + nb) share a byte (a null pointer overlaps nothing)
+static inline bool sa_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// workspace of the GradCAM form: w [B, H] | (min, max) [B, strips, 2] | row c_b of cam [B, N], each part 256-byte aligned
+extern "C" size_t mmx_selfattn_row_live_workspace_bytes(int B, int H, int T, int V) {
+    if (B < 1 || H < 1 || !sa_sizes_ok(T, V)) return 0;
+    const size_t f = sizeof(float), nb = static_cast<size_t>(B), N = static_cast<size_t>(T + V);
+    return sa_align256(f * nb * H) + sa_align256(f * nb * sa_cam_strips(T + V) * 2) + sa_align256(f * nb * N);
+}
+
+extern "C" int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int T, int V,
+                                     const void* text_len_dev, const void* vis_len_dev, void* workspace_dev, size_t workspace_bytes,
+                                     void* stream) {
+    MMX_CHECK_ARG(attn_dev && out_dev, "mmx_selfattn_row_live: null pointer");
+    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_selfattn_row_live: B=%d H=%d (both >= 1)", B, H);
+    MMX_CHECK_ARG(sa_sizes_ok(T, V), "mmx_selfattn_row_live: T=%d V=%d outside T >= 2, V >= 1, T + V <= %d", T, V, kSaMaxN);
+    const size_t need = grad_dev ? mmx_selfattn_row_live_workspace_bytes(B, H, T, V) : 0;
+    if (grad_dev) {
+        MMX_CHECK_ARG(workspace_dev, "mmx_selfattn_row_live: null pointer (the GradCAM form needs a workspace)");
+        MMX_CHECK_ARG(workspace_bytes >= need,
+                      "mmx_selfattn_row_live: workspace of %zu bytes needed (mmx_selfattn_row_live_workspace_bytes), got %zu", need,
+                      workspace_bytes);
+        MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0,
+                      "mmx_selfattn_row_live: the workspace must be 16-byte aligned");
+    }
+    const int N = T + V;
+    const size_t f = sizeof(float), nb = static_cast<size_t>(B);
+    const size_t out_bytes = f * nb * N, in_bytes = f * nb * H * N * N, len_bytes = sizeof(int) * nb;
+    const void* outs[2] = {out_dev, grad_dev ? workspace_dev : nullptr};
+    const size_t out_sizes[2] = {out_bytes, need};
+    bool alias = sa_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
+    for (int o = 0; o < 2; ++o)
+        alias |= sa_overlap(outs[o], out_sizes[o], attn_dev, in_bytes) || sa_overlap(outs[o], out_sizes[o], grad_dev, in_bytes) ||
+                 sa_overlap(outs[o], out_sizes[o], text_len_dev, len_bytes) || sa_overlap(outs[o], out_sizes[o], vis_len_dev, len_bytes);
+    MMX_CHECK_ARG(!alias, "mmx_selfattn_row_live: the output or the workspace may not alias an input or each other");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float* P = static_cast<const float*>(attn_dev);
+    const int* tl = static_cast<const int*>(text_len_dev);
+    const int* vl = static_cast<const int*>(vis_len_dev);
+    float* out = static_cast<float*>(out_dev);
+    if (!grad_dev) {
+        sa_raw_row_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(P, out, H, T, V, tl, vl);
+        MMX_LAUNCH_CHECK("sa_raw_row_kernel");
+        return MMX_OK;
+    }
+    const int strips = sa_cam_strips(N);
+    char* ws = static_cast<char*>(workspace_dev);
+    float* w = reinterpret_cast<float*>(ws);
+    float* mm = reinterpret_cast<float*>(ws + sa_align256(f * nb * H));
+    float* row = reinterpret_cast<float*>(ws + sa_align256(f * nb * H) + sa_align256(f * nb * strips * 2));
+    sa_gradcam_w_kernel<<<static_cast<unsigned>(B) * H, kSaThreads, 0, s>>>(static_cast<const float*>(grad_dev), w, T, V, tl, vl, H);
+    MMX_LAUNCH_CHECK("sa_gradcam_w_kernel");
+    sa_gradcam_cam_kernel<<<static_cast<unsigned>(B) * strips, kSaThreads, 0, s>>>(P, w, mm, row, H, T, V, strips, tl, vl);
+    MMX_LAUNCH_CHECK("sa_gradcam_cam_kernel");
+    sa_gradcam_out_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(mm, row, out, T, V, strips, tl, vl);
+    MMX_LAUNCH_CHECK("sa_gradcam_out_kernel");
+    return MMX_OK;
+}
+
+extern "C" size_t mmx_selfattn_rollout_row_workspace_bytes(int n_layers, int B, int T, int V) {
+    if (n_layers < 1 || n_layers > kSaMaxTable || B < 1 || !sa_sizes_ok(T, V)) return 0;
+    const size_t N = static_cast<size_t>(T + V);
+    return sa_align256(sizeof(float) * static_cast<size_t>(B) * n_layers * N * sa_row_stride(T + V));
+}
+
+extern "C" int mmx_selfattn_rollout_row(const void* const* attn_table, int n_layers, int B, int H, int T, int V,
+                                        const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev,
+                                        size_t workspace_bytes, void* stream) {
+    MMX_CHECK_ARG(attn_table && out_dev && workspace_dev, "mmx_selfattn_rollout_row: null pointer");
+    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_selfattn_rollout_row: B=%d H=%d (both >= 1)", B, H);
+    MMX_CHECK_ARG(sa_sizes_ok(T, V), "mmx_selfattn_rollout_row: T=%d V=%d outside T >= 2, V >= 1, T + V <= %d", T, V, kSaMaxN);
+    MMX_CHECK_ARG(n_layers >= 1 && n_layers <= kSaMaxTable, "mmx_selfattn_rollout_row: n_layers=%d outside 1..%d", n_layers, kSaMaxTable);
+    const size_t need = mmx_selfattn_rollout_row_workspace_bytes(n_layers, B, T, V);
+    MMX_CHECK_ARG(workspace_bytes >= need,
+                  "mmx_selfattn_rollout_row: workspace of %zu bytes needed (mmx_selfattn_rollout_row_workspace_bytes), got %zu", need,
+                  workspace_bytes);
+    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_selfattn_rollout_row: the workspace must be 16-byte aligned");
+    SaRolloutArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int l = 0; l < n_layers; ++l) {
+        MMX_CHECK_ARG(attn_table[l], "mmx_selfattn_rollout_row: null pointer in the table (entry %d)", l);
+        a.attn[l] = static_cast<const float*>(attn_table[l]);
+    }
+    const int N = T + V;
+    const size_t f = sizeof(float), nb = static_cast<size_t>(B);
+    const void* outs[2] = {out_dev, workspace_dev};
+    const size_t out_sizes[2] = {f * nb * N, need};
+    bool alias = sa_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
+    for (int o = 0; o < 2; ++o) {
+        for (int l = 0; l < n_layers; ++l) alias |= sa_overlap(outs[o], out_sizes[o], attn_table[l], f * nb * H * N * N);
+        alias |= sa_overlap(outs[o], out_sizes[o], text_len_dev, sizeof(int) * nb);
+        alias |= sa_overlap(outs[o], out_sizes[o], vis_len_dev, sizeof(int) * nb);
+    }
+    MMX_CHECK_ARG(!alias, "mmx_selfattn_rollout_row: the output or the workspace may not alias an input or each other");
+    a.n_layers = n_layers; a.B = B; a.H = H; a.T = T; a.V = V;
+    a.strips = (N * N + kSaMeanStrip - 1) / kSaMeanStrip;
+    a.text_len = static_cast<const int*>(text_len_dev);
+    a.vis_len = static_cast<const int*>(vis_len_dev);
+    a.ws = static_cast<float*>(workspace_dev);
+    a.out = static_cast<float*>(out_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    sa_rollout_means_kernel<<<static_cast<unsigned>(B) * n_layers * a.strips, kSaThreads, 0, s>>>(a);
+    MMX_LAUNCH_CHECK("sa_rollout_means_kernel");
+    sa_rollout_row_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(a);
+    MMX_LAUNCH_CHECK("sa_rollout_row_kernel");
+    return MMX_OK;
+}

@@ -1138,6 +1138,74 @@ def lxmert_rollout(text_attn, img_attn, cross_attn, text_len=None):
     return R_tt, R_ti, R_ii
 
 
+# ------------------------------------------------------------------------------------------- single-stream baselines, padded batches
+SELFATTN_MAX_TOKENS = _lib.SELFATTN_MAX_TOKENS       # T + V of mmx_selfattn_row_live / mmx_selfattn_rollout_row
+
+
+def _selfattn_shape(what, attn, n_text):
+    """``(B, H, T, V)`` of a ``[B, H, N, N]`` slab whose sequence is ``n_text`` padded text positions followed by regions."""
+    B, H, N, Nk = attn.shape
+    if n_text is None:
+        raise MMXError("%s: n_text (the padded text width T; V = N - T) is required" % what)
+    T = int(n_text)
+    if N != Nk or T < 2 or N - T < 1 or N > _lib.SELFATTN_MAX_TOKENS:
+        raise MMXError("%s: needs square slabs with T >= 2, V = N - T >= 1 and N <= %d (got %s, n_text=%d)"
+                       % (what, _lib.SELFATTN_MAX_TOKENS, tuple(attn.shape), T))
+    return B, H, T, N - T
+
+
+def _selfattn_row(what, attn, grad, text_len, vis_len, n_text):
+    attn = _slab(what, attn)
+    B, H, T, V = _selfattn_shape(what, attn, n_text)
+    ws, need = None, 0
+    if grad is not None:
+        grad = _slab(what, grad)
+        if grad.shape != attn.shape:
+            raise MMXError("%s: gradient slab %s does not match %s" % (what, tuple(grad.shape), tuple(attn.shape)))
+        need = lib().mmx_selfattn_row_live_workspace_bytes(B, H, T, V)
+        ws = _workspace(need, attn.device, tag="selfattn_row")       # grow-only scratch: pinned_state keeps it alive for graphs
+    text_len, vis_len = _lengths(what, text_len, B), _lengths(what, vis_len, B)
+    out = torch.empty(B, T + V, dtype=torch.float32, device=attn.device)
+    check(lib().mmx_selfattn_row_live(_p(attn), _p(grad), _p(out), B, H, T, V, _p(text_len), _p(vis_len), _p(ws), need, _stream()),
+          "mmx_selfattn_row_live")
+    return out
+
+
+def selfattn_raw_row(attn, text_len=None, vis_len=None, n_text=None):
+    """Raw attention of a padded single-stream batch: row ``c_b = text_len[b] - 2`` of ``mean_h attn[b, h]`` on sample b's live
+    positions ``[0, text_len[b]) u [T, T + vis_len[b])`` of a ``[B, H, N, N]`` fp32 slab, ``T = n_text`` (the padded text width),
+    exact zeros elsewhere and at ``c_b`` -> ``[B, N]``.  Lengths: device int tensors ``[B]`` or ``None`` (the full extent).  One
+    launch, nothing synchronises."""
+    return _selfattn_row("selfattn_raw_row", attn, None, text_len, vis_len, n_text)
+
+
+def selfattn_gradcam_row(attn, grad, text_len=None, vis_len=None, n_text=None):
+    """Attention GradCAM of a padded single-stream batch, min-max normalised over sample b's LIVE block only (the gradient of a padded
+    batch is not zero at padded keys), row ``c_b`` -> ``[B, N]``.  Arguments as ``selfattn_raw_row``; three launches."""
+    return _selfattn_row("selfattn_gradcam_row", attn, grad, text_len, vis_len, n_text)
+
+
+def selfattn_rollout_row(attn_layers, text_len=None, vis_len=None, n_text=None):
+    """Row ``c_b`` of the un-normalised rollout ``(I + A_{L-1}) ... (I + A_0)`` of a padded single-stream batch, ``A_l`` the head mean
+    of ``attn_layers[l]`` (fp32 ``[B, H, N, N]`` slabs, already sliced to ``start_layer:``) -> ``[B, N]``.  Two launches."""
+    what = "selfattn_rollout_row"
+    layers = [_slab(what, t) for t in attn_layers]
+    if not layers or any(t.shape != layers[0].shape for t in layers):
+        raise MMXError("%s: needs 1..%d slabs of one shape" % (what, _lib.BASELINES_MAX_TABLE))
+    B, H, T, V = _selfattn_shape(what, layers[0], n_text)
+    text_len, vis_len = _lengths(what, text_len, B), _lengths(what, vis_len, B)
+    need = lib().mmx_selfattn_rollout_row_workspace_bytes(len(layers), B, T, V)
+    if need == 0:
+        raise MMXError("%s: needs 1..%d slabs (got %d)" % (what, _lib.BASELINES_MAX_TABLE, len(layers)))
+    dev = layers[0].device
+    out = torch.empty(B, T + V, dtype=torch.float32, device=dev)
+    tbl, _k = _lib.ptr_table([t.data_ptr() for t in layers])
+    ws = _workspace(need, dev, tag="selfattn_rollout")               # grow-only scratch: pinned_state keeps it alive for graphs
+    check(lib().mmx_selfattn_rollout_row(tbl, len(layers), B, H, T, V, _p(text_len), _p(vis_len), _p(out), _p(ws), need, _stream()),
+          "mmx_selfattn_rollout_row")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- rollout
 def rollout_chain(layers, normalize):
     """``layers``: list of ``[B, N, N]`` (or ``[N, N]``) fp32 maps, already sliced to ``start_layer:``."""

@@ -48,6 +48,15 @@ def save_visual_results(*_args, **_kwargs):
                     "(transformer_mm_explainability_amd.postprocess)")
 
 
+def unpad_row(scores, b, n_text, padded_text):
+    """Row ``b`` of a ``*_batch`` result (``[B, T + V]``, padded layout) as the per-item methods return it and
+    ``VisualBertPerturbation`` takes it: ``[1, n_text + V]``, ``scores[b, :n_text]`` followed by ``scores[b, T:]``.  ``padded_text`` is
+    the padded text width ``T`` of the batch (``input_mask.shape[1]``); a ``[B, N]`` tensor alone does not say where its regions start."""
+    if not 0 < n_text <= padded_text < scores.shape[1]:
+        raise ValueError("unpad_row: n_text=%d, padded_text=%d do not fit %s" % (n_text, padded_text, tuple(scores.shape)))
+    return torch.cat((scores[b:b + 1, :n_text], scores[b:b + 1, padded_text:]), dim=1)
+
+
 class SelfAttentionGenerator:
     def __init__(self, model):
         self.model = model
@@ -150,6 +159,67 @@ class SelfAttentionGenerator:
             save_visual_results(input, cls_per_token_score, method_name='generate_attn_gradcam')
         return cls_per_token_score
 
+    # ---- the three attention-only baselines for a padded batch of ragged questions (per-item forms above: unchanged)
+    def _baseline_pass(self, input, backward=False, index=None):
+        """ONE forward of the padded batch [+ ONE backward with B one-hot seeds] -> ``(blocks, text_len, vis_len, T)``.
+
+        ``input``: the ``sample_list`` dict of B padded items (``input_ids`` / ``input_mask`` / ``segment_ids`` ``[B, T]``, masks
+        left-aligned, lengths may differ; ``image_feature_0`` ``[B, V, dim]``; optional ``image_dim``).  It does NOT go through
+        ``VisualBERT.forward``, whose trim by the total mask sum is the reference's batch-1 assumption (visual_bert.py:578-588): the
+        body takes the per-sample masks as they are.  ``text_len`` / ``vis_len`` stay on the device; nothing synchronises."""
+        mask, feats = input["input_mask"], input["image_feature_0"]
+        B, T = mask.shape
+        V = feats.shape[1]
+        if T + V > ops.SELFATTN_MAX_TOKENS:
+            raise NotImplementedError("the batched baselines carry one row of at most %d tokens (T + V = %d)"
+                                      % (ops.SELFATTN_MAX_TOKENS, T + V))
+        image_dim = input.get("image_dim")
+        if image_dim is None:
+            image_mask, vis_len = torch.ones(B, V, dtype=mask.dtype, device=mask.device), None
+        else:
+            image_mask = (torch.arange(V, device=mask.device).expand(B, V) < image_dim.reshape(B, 1)).to(mask.dtype)
+            vis_len = image_mask.sum(dim=1).to(torch.int32)
+        model = self.model.model                                     # VisualBERTForClassification
+        args = (input["input_ids"], mask, torch.cat((mask, image_mask), dim=-1), input["segment_ids"], feats,
+                torch.zeros_like(image_mask))
+
+        def seeds(output):
+            idx = output.argmax(dim=-1) if index is None else torch.as_tensor(index, device=output.device).reshape(-1)
+            return torch.zeros_like(output).scatter_(1, idx.reshape(-1, 1), 1.0)
+
+        if self.use_tape and hasattr(model, "forward_tape"):
+            output, state = model.forward_tape(*args)
+            if backward:
+                model.backward_tape(state, seeds(output))
+        elif backward:
+            output = rules.forward_for_backward(self.model, lambda: model(*args)["scores"])
+            self.model.zero_grad()
+            torch.sum(seeds(output) * output).backward(retain_graph=True)
+        else:
+            with torch.no_grad():
+                model(*args)
+        return self._blocks(), mask.sum(dim=1).to(torch.int32), vis_len, T
+
+    def generate_rollout_batch(self, input, start_layer=0):
+        """``generate_rollout`` (reference :168-180) for B padded items: one forward and two launches.  Returns ``[B, T + V]`` in the
+        padded layout (``unpad_row`` gives the per-item row): exact zero at padded positions and at ``cls_index``."""
+        blocks, text_len, vis_len, T = self._baseline_pass(input)
+        slabs = [blk.attention.self.get_attn().detach() for blk in blocks][start_layer:]
+        return ops.selfattn_rollout_row(slabs, text_len, vis_len, n_text=T)
+
+    def generate_raw_attn_batch(self, input):
+        """``generate_raw_attn`` (reference :155-166) for B padded items: one forward, one launch -> ``[B, T + V]``."""
+        blocks, text_len, vis_len, T = self._baseline_pass(input)
+        return ops.selfattn_raw_row(blocks[-1].attention.self.get_attn().detach(), text_len, vis_len, n_text=T)
+
+    def generate_attn_gradcam_batch(self, input, index=None):
+        """``generate_attn_gradcam`` (reference :186-215) for B padded items: one forward, one backward with B one-hot seeds
+        (``index``: ``None`` = the arg-max answer per sample, picked on the device, or ``[B]`` answer ids), three launches.  Head
+        weights, minimum and maximum are taken over each sample's LIVE block -> ``[B, T + V]``."""
+        blocks, text_len, vis_len, T = self._baseline_pass(input, backward=True, index=index)
+        sa = blocks[-1].attention.self
+        return ops.selfattn_gradcam_row(sa.get_attn().detach(), sa.get_attn_gradients().detach(), text_len, vis_len, n_text=T)
+
     def generate_transformer_att(self, input, index=None, start_layer=0, save_visualization=False,
                                  save_visualization_per_token=False):
         """Reference :24-66: rule 5 on the LRP cams, then the un-normalised batched rollout from ``start_layer``."""
@@ -218,6 +288,60 @@ class GraphedGenerateOursBatch:
             for k in self.KEYS:
                 if input[k].shape != self.static[k].shape:
                     raise ValueError("%s: %s, captured for %s" % (k, tuple(input[k].shape), tuple(self.static[k].shape)))
+                self.static[k].copy_(input[k])
+        if index is not None:
+            if self.static_index is None:
+                raise ValueError("the graph was captured with index=None (arg-max answers)")
+            self.static_index.copy_(torch.as_tensor(index))
+        self.graph.replay()
+        return self.output
+
+
+class GraphedBaselinesBatch:
+    """``SelfAttentionGenerator.generate_rollout_batch`` / ``generate_raw_attn_batch`` / ``generate_attn_gradcam_batch`` captured once
+    into a hipGraph and replayed, the way ``GraphedGenerateOursBatch`` replays ``generate_ours_batch``.  The kernels take the
+    per-sample lengths from the device (``input_mask.sum(1)`` is part of the graph), so ONE graph serves every ragged batch of the
+    captured shape: new ``input_ids`` / ``input_mask`` / ``segment_ids`` / ``image_feature_0`` (and ``image_dim``, when the example
+    had one) are copied into the captured buffers.
+
+        run = GraphedBaselinesBatch(model, example_sample_list, "rollout")    # "rollout" | "raw_attn" | "attn_gradcam"
+        scores = run(sample_list)                                              # [B, T + V], the graph's own output buffer
+    """
+
+    METHODS = ("rollout", "raw_attn", "attn_gradcam")
+    KEYS = ("input_ids", "input_mask", "segment_ids", "image_feature_0")
+
+    def __init__(self, model, example, method, index=None, start_layer=0, warmup=2):
+        if method not in self.METHODS:
+            raise ValueError("method must be one of %s, got %r" % (self.METHODS, method))
+        self.method = method
+        self.keys = self.KEYS + (("image_dim",) if example.get("image_dim") is not None else ())
+        self.static = {k: example[k].clone() for k in self.keys}
+        self.static_index = None if index is None else torch.as_tensor(index, device=example["input_ids"].device).clone()
+        self.gen = SelfAttentionGenerator(model)
+        if method == "rollout":
+            self._call = lambda: self.gen.generate_rollout_batch(self.static, start_layer=start_layer)
+        elif method == "raw_attn":
+            self._call = lambda: self.gen.generate_raw_attn_batch(self.static)
+        else:
+            self._call = lambda: self.gen.generate_attn_gradcam_batch(self.static, self.static_index)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._call()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(self.graph):
+            self.output = self._call()
+        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+
+    def __call__(self, input=None, index=None):
+        if input is not None:
+            for k in self.keys:
+                if input[k].shape != self.static[k].shape:
+                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
+                                     % (k, tuple(input[k].shape), tuple(self.static[k].shape)))
                 self.static[k].copy_(input[k])
         if index is not None:
             if self.static_index is None:
