@@ -9,6 +9,8 @@ forward, ONE all-gather of the per-sample step accuracies at the end.
 
 ``--explain-batch B`` (``raw_attn`` / ``attn_gradcam`` / ``rollout`` only; default 1, the per-item route): the relevancy rows of B items come from
 ONE padded batch (``SelfAttentionGenerator.generate_*_batch``, ``unpad_row``); every item is then perturbed as before.
+``--perturb-batch B`` (default 32; 0: the per-item route, one ``perturbation_image`` / ``perturbation_text`` call per item): the rows of B items -- explained as above, batched or per item -- are padded into one
+``[B, T + V]`` block (``pad_rows``) and all ``9 x B`` re-runs are ONE packed pass (``VisualBertPerturbation.perturbation_*_batch``).
 ``--reference-exact``: the reference loop stops only AFTER item ``num_samples + 1`` (its test is ``i > num_samples``) and
 still divides the accumulated accuracies by ``num_samples``; with the flag the printed numbers use
 exactly that accounting, without it ``num_samples`` items are evaluated and averaged.
@@ -75,6 +77,9 @@ def main():
     ap.add_argument("--explain-batch", type=int, default=1,
                     help="raw_attn / attn_gradcam / rollout only: explain this many items in ONE padded batch (one forward [+ one "
                          "backward] and two or three launches), then perturb each item as before.  1 (default): one item per call")
+    ap.add_argument("--perturb-batch", type=int, default=32,
+                    help="perturb this many items in ONE packed pass (perturbation_image_batch / perturbation_text_batch) after "
+                         "explaining them as above (default 32: profiles/visualbert_perturbation_batch_probe.txt).  0: one item per call")
     args = ap.parse_args()
     args.text, args.positive = args.is_text_pert, args.is_positive_pert
     rank, world, dev, gather_dev = sharding.init_evaluator_process()
@@ -99,6 +104,15 @@ def main():
     ahead = {}                                  # id -> (item on the device, its relevancy row), explained a batch at a time
     todo = []
 
+    def upcoming(k, n):
+        """The next ``n`` ids of this rank's shard from ``k`` on, in the order ``evaluate`` will ask for them: its shard minus what a
+        resumed run already holds (read once, as ``evaluate`` does)."""
+        if not todo:
+            done = store.done() if store is not None else ()
+            todo.extend(j for j in order if j not in done)
+        at = todo.index(k)
+        return todo[at:at + n]
+
     def explained(k):
         """Item ``k`` and its row.  The batched route explains the next ``--explain-batch`` ids of this rank's shard, in the order
         ``evaluate`` will ask for them, in one padded batch (``synthetic_item`` pads every question to the same width)."""
@@ -107,11 +121,7 @@ def main():
             return item, method_expl(dict(item)).detach()
         if k not in ahead:
             ahead.clear()
-            if not todo:                                # this rank's ids that ``evaluate`` will visit: its shard minus what a resumed
-                done = store.done() if store is not None else ()          # run already holds (read once, as ``evaluate`` does)
-                todo.extend(j for j in order if j not in done)
-            at = todo.index(k)
-            chunk = todo[at:at + args.explain_batch]
+            chunk = upcoming(k, args.explain_batch)
             items = [{name: t.to(dev) for name, t in synthetic_item(j).items()} for j in chunk]
             batch = {name: torch.cat([it[name] for it in items]) for name in ("input_ids", "input_mask", "segment_ids", "image_feature_0")}
             scores = explain_batch(batch).detach()
@@ -121,7 +131,21 @@ def main():
                 ahead[j] = (it, vb.unpad_row(scores, b, int(lens[b]), padded_text=width))
         return ahead.pop(k)
 
+    perturbed = {}                              # id -> its 9 step accuracies, perturbed --perturb-batch items at a time
+
     def step_accuracies_of(k):
+        if args.perturb_batch > 0:
+            if k not in perturbed:
+                perturbed.clear()
+                chunk = upcoming(k, args.perturb_batch)
+                items, rows = zip(*(explained(j) for j in chunk))
+                batch = {name: torch.cat([it[name] for it in items]) for name in ("input_ids", "input_mask", "segment_ids", "image_feature_0")}
+                regions = batch["image_feature_0"].shape[1]
+                cams = vb.pad_rows(rows, [row.shape[1] - regions for row in rows], batch["input_mask"].shape[1])
+                run = pert.perturbation_text_batch if args.text else pert.perturbation_image_batch
+                acc = pert.accuracy(run(batch, cams, args.positive), torch.cat([it["targets"] for it in items]))
+                perturbed.update(zip(chunk, acc))
+            return perturbed.pop(k)
         item, cam = explained(k)
         run = pert.perturbation_text if args.text else pert.perturbation_image
         return pert.accuracy(run(item, cam, args.positive), item["targets"][0])

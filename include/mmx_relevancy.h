@@ -657,6 +657,44 @@ int mmx_perturb_patches(const void* images_dev, const void* ranks_dev, const voi
 int mmx_perturb_tokens(const void* ids_dev, const void* scores_dev, const void* counts_dev, void* out_ids_dev, void* out_eot_dev,
                        void* ranks_dev, int B, int N, int S, void* stream);
 
+/* Perturbation test of the single-stream (VisualBERT-style) model for a PADDED batch of ragged questions (evaluator:
+ * visualbert_perturbation.py; VisualBERT/mmf/trainers/core/evaluation_loop.py:100-159).  Layout as for the mmx_selfattn_* baselines:
+ * the sequence is [T text positions | V regions], cam is the [B, T + V] fp32 relevancy row in the padded layout, text_len a DEVICE
+ * array of B int32, CLAMPED inside the kernels to 3 .. T before any use (so a length outside it never indexes out of bounds).  Both
+ * rank with the ONE stable descending order of mmx_patch_ranks (lower index first among equals, +0.0 == -0.0, NaN before +inf);
+ * positive != 0 ranks the negated scores.  Nothing is read back; no atomics, no workspace, workgroups independent of each other.
+ * Limits: T >= 3, V >= 1, T + V <= 256, at most 64 steps / groups, B >= 1, else MMX_EINVAL; null pointers and an output that overlaps
+ * an input or another output are refused the same way.  Every argument is checked before any HIP call.
+ *
+ * mmx_selfattn_perturb_regions: the image test (evaluation_loop.py:100-127; the physical gather of the kept regions, :113-120).
+ *   emb [B, T + V, E] fp32: the embedded and LayerNorm-ed rows of every item (row-wise, so computed once and shared by all steps;
+ *   a visual token has no index-dependent term, VisualBERT/mmf/modules/embeddings.py:399-417, so a gather in any order is the same
+ *   model); counts [G] int32 ON THE DEVICE, the DISTINCT keep counts c_0 > c_1 > ... (each clamped to 0 .. V), built once by the
+ *   host from int((1 - step) * V) (evaluation_loop.py:111).
+ *   -> x [R, E] fp32, R = B * sum_g (T + c_g): the sequence (g, b) starts at row off_g + b * (T + c_g), off_g = B * sum_{h < g} (T + c_h),
+ *      and holds the T text rows of item b as they are, then emb[b, T + order_b[j]] for j < c_g (order_b: the regions by rank);
+ *      mask [R] fp32: the additive key mask, -10000.0 at text positions >= text_len[b], 0 elsewhere;
+ *      pooled [G, B] int64: the packed row of token text_len[b] - 2 (the token the 'vqa' pooler reads);
+ *      ranks [B, V] int32 (or NULL): == mmx_patch_ranks of the (negated) region scores.
+ *   R is what the host sized x / mask for; a sequence that would end past it (counts that do not match R) is not written.
+ *   One workgroup per (b, g); each ranks its own V scores in LDS (V^2 compares) and streams its rows with 16-byte loads / stores when
+ *   E % 4 == 0 and emb / x are 16-byte aligned, one float at a time otherwise.  Besides the shared limits: 1 <= E <= 2^20 and
+ *   B * G <= 2^31 - 1 (the grid is one-dimensional), else MMX_EINVAL.  mmx_selfattn_perturb_text has no upper limit on B.
+ *
+ * mmx_selfattn_perturb_text: the text test (evaluation_loop.py:129-159).  ids / segments [B, T] int64, counts [S, T] int32 ON THE
+ *   DEVICE with counts[s][w] = int((1 - step_s) * w) in host arithmetic (:140).  Per question, n = the clamped length, c = n - 2: the
+ *   words are the positions 1 .. c - 1 (W = n - 3 of them, scores cam[b, 1 .. c - 1], :135), positions 0, c, c + 1 always stay
+ *   (:147); step s keeps word p iff rank[p] < counts[s][W].
+ *   -> out_ids / out_segments / out_mask [S, B, T] int64: the kept positions in their original order, left-aligned, zeros behind them
+ *      (mask 1 at the kept); new_len [S, B] int64 = 3 + kept.
+ *   One wave per question, the structure (and the key / counting / compaction code) of mmx_perturb_tokens. */
+int mmx_selfattn_perturb_regions(const void* emb_dev, const void* cam_dev, const void* text_len_dev, const void* counts_dev,
+                                 void* x_dev, void* mask_dev, void* pooled_dev, void* ranks_dev, int B, int T, int V, int E, int G,
+                                 int64_t R, int positive, void* stream);
+int mmx_selfattn_perturb_text(const void* ids_dev, const void* segments_dev, const void* cam_dev, const void* text_len_dev,
+                              const void* counts_dev, void* out_ids_dev, void* out_segments_dev, void* out_mask_dev, void* new_len_dev,
+                              int B, int T, int V, int S, int positive, void* stream);
+
 /* Row-relevancy mode of the backward (BASELINE config 5; CLIP `interpret`, CLIP/clip/... notebook cell 7:27-37, returns
  * only `R[:, 0, 1:]` of the image tower): row 0 of  R_final = (I + A_L) ... (I + A_start)  is  e_0^T (I + A_L) ... , i.e.
  * a ROW vector carried from the top layer down -- the order the backward visits the layers anyway:

@@ -82,6 +82,8 @@ _PROTOTYPES = {
     "mmx_patch_ranks": (_i, [_vp, _vp, _i, _i, _vp]),
     "mmx_perturb_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_perturb_patches": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mmx_selfattn_perturb_regions": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i, _i64, _i, _vp]),
+    "mmx_selfattn_perturb_text": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
     "mmx_attn_capture_bwd_ex": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64,
                                      _vp, _vp, _vp, _vp]
                                 + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),

@@ -206,6 +206,12 @@ __device__ __forceinline__ int xcd_contiguous_id(int w, int total) {
 }
 
 inline size_t dtype_size(int dt) { return dt == MMX_F32 ? 4 : 2; }
+// [a, a + na) and [b, b + nb) share a byte (a null pointer overlaps nothing): the alias checks of the entries
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
 
 void set_error(const char* fmt, ...);
 void attn_head_enable(int on);

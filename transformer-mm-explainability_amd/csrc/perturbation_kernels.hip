@@ -19,9 +19,17 @@
 //     wave finds e = the first maximum of the row (text.argmax: the EOT token), turns the scores of the words 1 <= p < e into the keys
 //     of mmx_patch_ranks (every other position: key 0, below every real key, so the counting loop needs no second predicate), ranks them
 //     by counting (W <= 254 words: at most 64 k comparisons), and for every step compacts [SOT, kept words, EOT] with one ballot and a
-//     popcount prefix per 64 positions.  The compacted row is assembled in LDS and leaves as contiguous 8-byte stores, zeros behind
+//     popcount prefix per 64 positions.  The kept positions are assembled in LDS and the row leaves as contiguous 8-byte stores, zeros behind
 //     it.  counts [S][N - 1] (device, host-built once: int((1 - step) * w) for every word count w) is indexed with the caption's own
 //     W: no float arithmetic on steps here, nothing read back.  No atomics, no workspace.
+//
+// Perturbation test of VisualBERT on a padded batch (visualbert_perturbation.py; VisualBERT/mmf/trainers/core/evaluation_loop.py:100-159),
+// sequence = [T text positions | V regions], lengths from a device array, clamped to 3 .. T:
+//   * mmx_selfattn_perturb_regions: one workgroup per (item, group of steps with one keep count c): it ranks the item's V <= 253 region
+//     scores in LDS the way mmx_patch_ranks does, then copies the item's T embedded text rows and its c best regions, in rank order,
+//     into the group's packed rows (16-byte loads / stores when E % 4 == 0), with the additive key mask and the pooled row index.
+//   * mmx_selfattn_perturb_text: mmx_perturb_tokens on the '?'-pooler convention (positions 0, n - 2, n - 1 stay, the words are
+//     1 .. n - 3) for ids and segments at once; the three wave-level steps are shared with perturb_tokens_kernel.
 #include "mmx_common.h"
 
 namespace mmx {
@@ -37,24 +45,36 @@ __device__ __forceinline__ unsigned order_key(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The whole workgroup stages the keys of one row of P scores (NEGATE: of their negations) in LDS, padded with 0 -- below every real
+// key -- to the next multiple of 4, and meets at a barrier: keys is complete on return.
+template <bool NEGATE>
+__device__ __forceinline__ void block_stage_keys(const float* __restrict__ row, int P, unsigned* keys) {
+    const int P4 = (P + 3) & ~3;
+    for (int j = threadIdx.x; j < P4; j += blockDim.x) keys[j] = j < P ? order_key(NEGATE ? -row[j] : row[j]) : 0u;
+    __syncthreads();
+}
+
+// Position of element i in ONE stable descending order of keys[0 .. n4) (n4 % 4 == 0, 16-byte aligned LDS): the keys above its own plus
+// the equal ones in front of it.  One LDS address per wave and read (broadcast, conflict-free), four keys per read.  The one counting
+// loop of this file: patch_ranks_kernel, selfattn_perturb_regions_kernel and wave_word_ranks call it.
+__device__ __forceinline__ int keys_before(const unsigned* keys, int n4, int i) {
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    const unsigned ki = keys[i];
+    int before = 0;
+    for (int j = 0; j < n4; j += 4) {
+        const u32x4_t kj = *reinterpret_cast<const u32x4_t*>(keys + j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) before += (kj[e] > ki || (kj[e] == ki && j + e < i)) ? 1 : 0;
+    }
+    return before;
+}
+
 __global__ __launch_bounds__(1024) void patch_ranks_kernel(const float* __restrict__ scores, int* __restrict__ ranks, int P) {
     __shared__ __attribute__((aligned(16))) unsigned keys[kMaxPatches];
-    const int b = blockIdx.x, tid = threadIdx.x, nthreads = blockDim.x;
+    const int b = blockIdx.x;
+    block_stage_keys<false>(scores + static_cast<int64_t>(b) * P, P, keys);
     const int P4 = (P + 3) & ~3;
-    const float* row = scores + static_cast<int64_t>(b) * P;
-    for (int j = tid; j < P4; j += nthreads) keys[j] = j < P ? order_key(row[j]) : 0u;    // padding: below every real key
-    __syncthreads();
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    for (int i = tid; i < P; i += nthreads) {
-        const unsigned ki = keys[i];
-        int before = 0;
-        for (int j = 0; j < P4; j += 4) {
-            const u32x4_t kj = *reinterpret_cast<const u32x4_t*>(keys + j);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) before += (kj[e] > ki || (kj[e] == ki && j + e < i)) ? 1 : 0;
-        }
-        ranks[static_cast<int64_t>(b) * P + i] = before;
-    }
+    for (int i = threadIdx.x; i < P; i += blockDim.x) ranks[static_cast<int64_t>(b) * P + i] = keys_before(keys, P4, i);
 }
 
 // VEC = 4: R % 4 == 0 and 16-byte aligned images / out; UNI: patch % 4 == 0, the four pixels share one patch
@@ -98,6 +118,46 @@ __global__ __launch_bounds__(256) void perturb_patches_kernel(const float* __res
 
 constexpr int kMaxPositions = 256, kMaxTokenSteps = 64;
 
+// ---- one wave, one row of N <= 256 positions: the three steps the token kernels share (perturb_tokens_kernel, selfattn_perturb_text_kernel)
+// keys[p] = order_key(score of word p) for the words lo <= p < hi (NEGATE: of its negation), 0 -- below every real key -- at every other
+// position up to the next multiple of 4: the counting loop needs no second predicate.  Scores outside the words are never read.
+template <bool NEGATE>
+__device__ __forceinline__ void wave_word_keys(const float* __restrict__ srow, int lo, int hi, int N, int lane, unsigned* keys) {
+    const int N4 = (N + 3) & ~3;
+    for (int c = 0; c < (N4 + 63) >> 6; ++c) {
+        const int p = c * 64 + lane;
+        if (p < N4) keys[p] = (p >= lo && p < hi) ? order_key(NEGATE ? -srow[p] : srow[p]) : 0u;
+    }
+}
+
+// rk[p] = position of word p in ONE stable descending order of the words (the counting of patch_ranks_kernel), -1 outside the words;
+// ranks_row (optional, global) receives the same.  keys must be complete (a barrier after wave_word_keys).
+__device__ __forceinline__ void wave_word_ranks(const unsigned* keys, int lo, int hi, int N, int lane, int* rk, int* ranks_row) {
+    const int E4 = (hi + 3) & ~3;                           // <= (N + 3) & ~3: keys at and past hi are 0
+    for (int c = 0; c < (N + 63) >> 6; ++c) {
+        const int p = c * 64 + lane;
+        if (p < N) {
+            const int before = (p >= lo && p < hi) ? keys_before(keys, E4, p) : -1;
+            rk[p] = before;
+            if (ranks_row) ranks_row[p] = before;
+        }
+    }
+}
+
+// src[j] = the j-th position p < N (ascending) with keep(p): one ballot and a popcount prefix per 64 positions.  Returns their number.
+template <class Keep>
+__device__ __forceinline__ int wave_compact(int N, int lane, Keep keep, int* src) {
+    int total = 0;
+    for (int c = 0; c < (N + 63) >> 6; ++c) {
+        const int p = c * 64 + lane;
+        const bool k = p < N && keep(p);
+        const unsigned long long m = __ballot(k);
+        if (k) src[total + __popcll(m & ((1ull << lane) - 1ull))] = p;
+        total += __popcll(m);
+    }
+    return total;
+}
+
 // grid B, one wave: caption b -> out_ids[s][b][.], out_eot[s][b] for every step s, ranks[b][.] (optional)
 __global__ __launch_bounds__(64) void perturb_tokens_kernel(const long long* __restrict__ ids, const float* __restrict__ scores,
                                                             const int* __restrict__ counts, long long* __restrict__ out_ids,
@@ -105,7 +165,7 @@ __global__ __launch_bounds__(64) void perturb_tokens_kernel(const long long* __r
                                                             int S) {
     __shared__ __attribute__((aligned(16))) unsigned keys[kMaxPositions];
     __shared__ long long idrow[kMaxPositions];
-    __shared__ long long outrow[kMaxPositions];
+    __shared__ int src[kMaxPositions];
     __shared__ int rk[kMaxPositions];
     const int b = blockIdx.x, lane = threadIdx.x;
     const long long* irow = ids + static_cast<int64_t>(b) * N;
@@ -131,51 +191,122 @@ __global__ __launch_bounds__(64) void perturb_tokens_kernel(const long long* __r
     }
     const int W = e > 1 ? e - 1 : 0;                        // the words are the positions 1 .. e - 1
 
-    const int N4 = (N + 3) & ~3;
-    for (int c = 0; c < (N4 + 63) >> 6; ++c) {
-        const int p = c * 64 + lane;
-        if (p < N4) keys[p] = (p >= 1 && p < e) ? order_key(srow[p]) : 0u;       // scores outside the words are never read
-    }
+    wave_word_keys<false>(srow, 1, e, N, lane, keys);
     __syncthreads();
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    const int E4 = (e + 3) & ~3;                            // <= N4: keys at and past e are 0
-    for (int c = 0; c < chunks; ++c) {
-        const int p = c * 64 + lane;
-        if (p < N) {
-            int before = -1;
-            if (p >= 1 && p < e) {
-                const unsigned kp = keys[p];
-                before = 0;
-                for (int j = 0; j < E4; j += 4) {
-                    const u32x4_t kj = *reinterpret_cast<const u32x4_t*>(keys + j);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) before += (kj[r] > kp || (kj[r] == kp && j + r < p)) ? 1 : 0;
-                }
-            }
-            rk[p] = before;
-            if (ranks) ranks[static_cast<int64_t>(b) * N + p] = before;
-        }
-    }
+    wave_word_ranks(keys, 1, e, N, lane, rk, ranks ? ranks + static_cast<int64_t>(b) * N : nullptr);
     __syncthreads();
 
     for (int s = 0; s < S; ++s) {
         const int keep_n = counts[static_cast<int64_t>(s) * (N - 1) + W];        // W <= N - 2
-        int total = 0;
-        for (int c = 0; c < chunks; ++c) {
-            const int p = c * 64 + lane;
-            const bool keep = p < N && (p == 0 || p == e || (p < e && rk[p] < keep_n));
-            const unsigned long long m = __ballot(keep);
-            if (keep) outrow[total + __popcll(m & ((1ull << lane) - 1ull))] = idrow[p];
-            total += __popcll(m);
-        }
+        const int total = wave_compact(N, lane, [&](int p) { return p == 0 || p == e || (p < e && rk[p] < keep_n); }, src);
         __syncthreads();
         long long* orow = out_ids + (static_cast<int64_t>(s) * B + b) * N;
         for (int c = 0; c < chunks; ++c) {
             const int p = c * 64 + lane;
-            if (p < N) orow[p] = p < total ? outrow[p] : 0ll;
+            if (p < N) orow[p] = p < total ? idrow[src[p]] : 0ll;
         }
         if (lane == 0) out_eot[static_cast<int64_t>(s) * B + b] = total - 1;
-        __syncthreads();                                    // the next step rewrites outrow
+        __syncthreads();                                    // the next step rewrites src
+    }
+}
+
+// ---- VisualBERT (single-stream) perturbation test on a PADDED batch: sequence = [T text positions | V regions], relevancy rows [B, T + V]
+__device__ __forceinline__ int clamp_text_len(const int* __restrict__ text_len, int b, int T) {
+    const int n = text_len[b];
+    return n < 3 ? 3 : (n > T ? T : n);
+}
+
+constexpr int kRegionThreads = 256;
+constexpr int kMaxRowFloats = 1 << 20;                      // E: the floats of a sequence, (T + c) * E <= 2^28, index as int
+
+// grid B * G (workgroup w: item w % B of group w / B), 256 threads.  VEC = 4: E % 4 == 0 and 16-byte aligned emb / x
+template <int VEC, bool NEGATE>
+__global__ __launch_bounds__(kRegionThreads) void selfattn_perturb_regions_kernel(
+    const float* __restrict__ emb, const float* __restrict__ cam, const int* __restrict__ text_len, const int* __restrict__ counts,
+    float* __restrict__ x, float* __restrict__ mask, long long* __restrict__ pooled, int* __restrict__ ranks, int B, int T, int V, int E,
+    int G, long long R) {
+    __shared__ __attribute__((aligned(16))) unsigned keys[kMaxPositions];
+    __shared__ int order[kMaxPositions];                    // order[r] = the region ranked r
+    const int b = blockIdx.x % B, g = blockIdx.x / B, tid = threadIdx.x;
+    const int N = T + V, V4 = (V + 3) & ~3;
+    block_stage_keys<NEGATE>(cam + static_cast<int64_t>(b) * N + T, V, keys);
+    if (tid < V) {                                          // V <= 253 < blockDim.x
+        const int before = keys_before(keys, V4, tid);
+        order[before] = tid;                                // a permutation of 0 .. V - 1: every slot written once
+        if (ranks && g == 0) ranks[static_cast<int64_t>(b) * V + tid] = before;
+    }
+    // where the sequence (g, b) starts: off_g + b * (T + c_g); counts clamped to 0 .. V, and nothing is written past R rows
+    long long row0 = 0;
+    for (int h = 0; h < g; ++h) {
+        const int ch = counts[h];
+        row0 += static_cast<long long>(B) * (T + (ch < 0 ? 0 : (ch > V ? V : ch)));
+    }
+    int c = counts[g];
+    c = c < 0 ? 0 : (c > V ? V : c);
+    const int L = T + c;
+    row0 += static_cast<long long>(b) * L;
+    if (row0 + L > R) return;                               // (uniform over the workgroup)
+    __syncthreads();
+    const int n = clamp_text_len(text_len, b, T);
+    for (int p = tid; p < L; p += kRegionThreads) mask[row0 + p] = (p < T && p >= n) ? -10000.0f : 0.0f;
+    if (tid == 0) pooled[static_cast<int64_t>(g) * B + b] = row0 + n - 2;
+    const float* ebase = emb + static_cast<int64_t>(b) * N * E;
+    float* xbase = x + row0 * E;
+    const int EV = E / VEC;
+    for (int i = tid; i < L * EV; i += kRegionThreads) {
+        const int p = i / EV, col = (i - p * EV) * VEC;
+        const int q = p < T ? p : T + order[p - T];
+        const float* sp = ebase + static_cast<int64_t>(q) * E + col;
+        float* dp = xbase + static_cast<int64_t>(p) * E + col;
+        if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(dp) = *reinterpret_cast<const f32x4*>(sp);
+        else *dp = *sp;
+    }
+}
+
+// grid B, one wave: question b -> out_ids / out_seg / out_mask [s][b][.] and new_len[s][b] for every step s (perturb_tokens_kernel's
+// structure; the length comes from text_len, the words are 1 .. c - 1 with c = n - 2, and 0, c, c + 1 always stay)
+template <bool NEGATE>
+__global__ __launch_bounds__(64) void selfattn_perturb_text_kernel(const long long* __restrict__ ids, const long long* __restrict__ seg,
+                                                                   const float* __restrict__ cam, const int* __restrict__ text_len,
+                                                                   const int* __restrict__ counts, long long* __restrict__ out_ids,
+                                                                   long long* __restrict__ out_seg, long long* __restrict__ out_mask,
+                                                                   long long* __restrict__ new_len, int B, int T, int V, int S) {
+    __shared__ __attribute__((aligned(16))) unsigned keys[kMaxPositions];
+    __shared__ long long idrow[kMaxPositions];
+    __shared__ long long segrow[kMaxPositions];
+    __shared__ int src[kMaxPositions];
+    __shared__ int rk[kMaxPositions];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int chunks = (T + 63) >> 6;
+    const int n = clamp_text_len(text_len, b, T), c = n - 2, W = n - 3;
+    for (int k = 0; k < chunks; ++k) {
+        const int p = k * 64 + lane;
+        if (p < T) {
+            idrow[p] = ids[static_cast<int64_t>(b) * T + p];
+            segrow[p] = seg[static_cast<int64_t>(b) * T + p];
+        }
+    }
+    wave_word_keys<NEGATE>(cam + static_cast<int64_t>(b) * (T + V), 1, c, T, lane, keys);
+    __syncthreads();
+    wave_word_ranks(keys, 1, c, T, lane, rk, nullptr);
+    __syncthreads();
+
+    for (int s = 0; s < S; ++s) {
+        const int keep_n = counts[static_cast<int64_t>(s) * T + W];              // W <= T - 3
+        const int total = wave_compact(T, lane, [&](int p) { return p == 0 || p == c || p == c + 1 || (p < c && rk[p] < keep_n); }, src);
+        __syncthreads();
+        const int64_t o = (static_cast<int64_t>(s) * B + b) * T;
+        for (int k = 0; k < chunks; ++k) {
+            const int p = k * 64 + lane;
+            if (p < T) {
+                const bool live = p < total;
+                out_ids[o + p] = live ? idrow[src[p]] : 0ll;
+                out_seg[o + p] = live ? segrow[src[p]] : 0ll;
+                out_mask[o + p] = live ? 1ll : 0ll;
+            }
+        }
+        if (lane == 0) new_len[static_cast<int64_t>(s) * B + b] = total;
+        __syncthreads();                                    // the next step rewrites src
     }
 }
 
@@ -228,5 +359,80 @@ extern "C" int mmx_perturb_tokens(const void* ids_dev, const void* scores_dev, c
         static_cast<const long long*>(ids_dev), static_cast<const float*>(scores_dev), static_cast<const int*>(counts_dev),
         static_cast<long long*>(out_ids_dev), static_cast<long long*>(out_eot_dev), static_cast<int*>(ranks_dev), B, N, S);
     MMX_LAUNCH_CHECK("perturb_tokens_kernel");
+    return MMX_OK;
+}
+
+extern "C" int mmx_selfattn_perturb_regions(const void* emb_dev, const void* cam_dev, const void* text_len_dev, const void* counts_dev,
+                                            void* x_dev, void* mask_dev, void* pooled_dev, void* ranks_dev, int B, int T, int V, int E,
+                                            int G, int64_t R, int positive, void* stream) {
+    const char* me = "mmx_selfattn_perturb_regions";
+    MMX_CHECK_ARG(emb_dev && cam_dev && text_len_dev && counts_dev && x_dev && mask_dev && pooled_dev, "%s: null pointer", me);
+    MMX_CHECK_ARG(B >= 1 && E >= 1 && E <= kMaxRowFloats, "%s: B=%d < 1 or E=%d outside 1 .. %d", me, B, E, kMaxRowFloats);
+    MMX_CHECK_ARG(T >= 3 && V >= 1 && T <= kMaxPositions && V <= kMaxPositions && T + V <= kMaxPositions,
+                  "%s: T=%d V=%d outside T >= 3, V >= 1, T + V <= %d", me, T, V, kMaxPositions);
+    MMX_CHECK_ARG(G >= 1 && G <= kMaxTokenSteps, "%s: %d groups outside 1 .. %d", me, G, kMaxTokenSteps);
+    const int64_t bg = static_cast<int64_t>(B) * G;
+    MMX_CHECK_ARG(bg <= 0x7FFFFFFF, "%s: B * G = %lld workgroups exceed the grid limit 2^31 - 1", me, static_cast<long long>(bg));
+    MMX_CHECK_ARG(R >= bg * T && R <= bg * (T + V), "%s: %lld packed rows outside B * G * T .. B * G * (T + V) = %lld .. %lld", me,
+                  static_cast<long long>(R), static_cast<long long>(bg * T), static_cast<long long>(bg * (T + V)));
+    const size_t f = sizeof(float), N = static_cast<size_t>(T + V), nb = static_cast<size_t>(B), rows = static_cast<size_t>(R);
+    const void* ins[4] = {emb_dev, cam_dev, text_len_dev, counts_dev};
+    const size_t in_sizes[4] = {f * nb * N * E, f * nb * N, sizeof(int) * nb, sizeof(int) * G};
+    const void* outs[4] = {x_dev, mask_dev, pooled_dev, ranks_dev};
+    const size_t out_sizes[4] = {f * rows * E, f * rows, sizeof(long long) * static_cast<size_t>(bg), sizeof(int) * nb * V};
+    bool alias = false;
+    for (int o = 0; o < 4; ++o) {
+        for (int i = 0; i < 4; ++i) alias |= ranges_overlap(outs[o], out_sizes[o], ins[i], in_sizes[i]);
+        for (int p = o + 1; p < 4; ++p) alias |= ranges_overlap(outs[o], out_sizes[o], outs[p], out_sizes[p]);
+    }
+    MMX_CHECK_ARG(!alias, "%s: an output may not alias an input or another output", me);
+    const bool vec = E % 4 == 0 && ((reinterpret_cast<uintptr_t>(emb_dev) | reinterpret_cast<uintptr_t>(x_dev)) & 15u) == 0;
+    const dim3 grid(static_cast<unsigned>(bg));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define MMX_REGIONS_LAUNCH(VEC, NEG)                                                                                                 \
+    selfattn_perturb_regions_kernel<VEC, NEG><<<grid, kRegionThreads, 0, s>>>(                                                       \
+        static_cast<const float*>(emb_dev), static_cast<const float*>(cam_dev), static_cast<const int*>(text_len_dev),               \
+        static_cast<const int*>(counts_dev), static_cast<float*>(x_dev), static_cast<float*>(mask_dev),                              \
+        static_cast<long long*>(pooled_dev), static_cast<int*>(ranks_dev), B, T, V, E, G, static_cast<long long>(R))
+    if (vec && positive) MMX_REGIONS_LAUNCH(4, true);
+    else if (vec) MMX_REGIONS_LAUNCH(4, false);
+    else if (positive) MMX_REGIONS_LAUNCH(1, true);
+    else MMX_REGIONS_LAUNCH(1, false);
+#undef MMX_REGIONS_LAUNCH
+    MMX_LAUNCH_CHECK("selfattn_perturb_regions_kernel");
+    return MMX_OK;
+}
+
+extern "C" int mmx_selfattn_perturb_text(const void* ids_dev, const void* segments_dev, const void* cam_dev, const void* text_len_dev,
+                                         const void* counts_dev, void* out_ids_dev, void* out_segments_dev, void* out_mask_dev,
+                                         void* new_len_dev, int B, int T, int V, int S, int positive, void* stream) {
+    const char* me = "mmx_selfattn_perturb_text";
+    MMX_CHECK_ARG(ids_dev && segments_dev && cam_dev && text_len_dev && counts_dev && out_ids_dev && out_segments_dev && out_mask_dev &&
+                      new_len_dev, "%s: null pointer", me);
+    MMX_CHECK_ARG(B >= 1, "%s: batch %d < 1", me, B);
+    MMX_CHECK_ARG(T >= 3 && V >= 1 && T <= kMaxPositions && V <= kMaxPositions && T + V <= kMaxPositions,
+                  "%s: T=%d V=%d outside T >= 3, V >= 1, T + V <= %d", me, T, V, kMaxPositions);
+    MMX_CHECK_ARG(S >= 1 && S <= kMaxTokenSteps, "%s: %d steps outside 1 .. %d", me, S, kMaxTokenSteps);
+    const size_t ll = sizeof(long long), nb = static_cast<size_t>(B), nt = static_cast<size_t>(T), ns = static_cast<size_t>(S);
+    const void* ins[5] = {ids_dev, segments_dev, cam_dev, text_len_dev, counts_dev};
+    const size_t in_sizes[5] = {ll * nb * nt, ll * nb * nt, sizeof(float) * nb * (T + V), sizeof(int) * nb, sizeof(int) * ns * nt};
+    const void* outs[4] = {out_ids_dev, out_segments_dev, out_mask_dev, new_len_dev};
+    const size_t out_sizes[4] = {ll * ns * nb * nt, ll * ns * nb * nt, ll * ns * nb * nt, ll * ns * nb};
+    bool alias = false;
+    for (int o = 0; o < 4; ++o) {
+        for (int i = 0; i < 5; ++i) alias |= ranges_overlap(outs[o], out_sizes[o], ins[i], in_sizes[i]);
+        for (int p = o + 1; p < 4; ++p) alias |= ranges_overlap(outs[o], out_sizes[o], outs[p], out_sizes[p]);
+    }
+    MMX_CHECK_ARG(!alias, "%s: an output may not alias an input or another output", me);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define MMX_TEXT_LAUNCH(NEG)                                                                                                         \
+    selfattn_perturb_text_kernel<NEG><<<dim3(B), 64, 0, s>>>(                                                                        \
+        static_cast<const long long*>(ids_dev), static_cast<const long long*>(segments_dev), static_cast<const float*>(cam_dev),     \
+        static_cast<const int*>(text_len_dev), static_cast<const int*>(counts_dev), static_cast<long long*>(out_ids_dev),            \
+        static_cast<long long*>(out_segments_dev), static_cast<long long*>(out_mask_dev), static_cast<long long*>(new_len_dev), B, T, V, S)
+    if (positive) MMX_TEXT_LAUNCH(true);
+    else MMX_TEXT_LAUNCH(false);
+#undef MMX_TEXT_LAUNCH
+    MMX_LAUNCH_CHECK("selfattn_perturb_text_kernel");
     return MMX_OK;
 }

@@ -281,12 +281,6 @@ using namespace mmx;
 static inline size_t sa_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 static inline bool sa_sizes_ok(int T, int V) { return T >= 2 && V >= 1 && T <= kSaMaxN && V <= kSaMaxN && T + V <= kSaMaxN; }
 static inline int sa_cam_strips(int N) { return (N + kSaStripRows - 1) / kSaStripRows; }
-// [a, a + na) and [b, b + nb) share a byte (a null pointer overlaps nothing)
-static inline bool sa_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
 
 // workspace of the GradCAM form: w [B, H] | (min, max) [B, strips, 2] | row c_b of cam [B, N], each part 256-byte aligned
 extern "C" size_t mmx_selfattn_row_live_workspace_bytes(int B, int H, int T, int V) {
@@ -315,10 +309,10 @@ extern "C" int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev,
     const size_t out_bytes = f * nb * N, in_bytes = f * nb * H * N * N, len_bytes = sizeof(int) * nb;
     const void* outs[2] = {out_dev, grad_dev ? workspace_dev : nullptr};
     const size_t out_sizes[2] = {out_bytes, need};
-    bool alias = sa_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
+    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
     for (int o = 0; o < 2; ++o)
-        alias |= sa_overlap(outs[o], out_sizes[o], attn_dev, in_bytes) || sa_overlap(outs[o], out_sizes[o], grad_dev, in_bytes) ||
-                 sa_overlap(outs[o], out_sizes[o], text_len_dev, len_bytes) || sa_overlap(outs[o], out_sizes[o], vis_len_dev, len_bytes);
+        alias |= ranges_overlap(outs[o], out_sizes[o], attn_dev, in_bytes) || ranges_overlap(outs[o], out_sizes[o], grad_dev, in_bytes) ||
+                 ranges_overlap(outs[o], out_sizes[o], text_len_dev, len_bytes) || ranges_overlap(outs[o], out_sizes[o], vis_len_dev, len_bytes);
     MMX_CHECK_ARG(!alias, "mmx_selfattn_row_live: the output or the workspace may not alias an input or each other");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float* P = static_cast<const float*>(attn_dev);
@@ -372,11 +366,11 @@ extern "C" int mmx_selfattn_rollout_row(const void* const* attn_table, int n_lay
     const size_t f = sizeof(float), nb = static_cast<size_t>(B);
     const void* outs[2] = {out_dev, workspace_dev};
     const size_t out_sizes[2] = {f * nb * N, need};
-    bool alias = sa_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
+    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
     for (int o = 0; o < 2; ++o) {
-        for (int l = 0; l < n_layers; ++l) alias |= sa_overlap(outs[o], out_sizes[o], attn_table[l], f * nb * H * N * N);
-        alias |= sa_overlap(outs[o], out_sizes[o], text_len_dev, sizeof(int) * nb);
-        alias |= sa_overlap(outs[o], out_sizes[o], vis_len_dev, sizeof(int) * nb);
+        for (int l = 0; l < n_layers; ++l) alias |= ranges_overlap(outs[o], out_sizes[o], attn_table[l], f * nb * H * N * N);
+        alias |= ranges_overlap(outs[o], out_sizes[o], text_len_dev, sizeof(int) * nb);
+        alias |= ranges_overlap(outs[o], out_sizes[o], vis_len_dev, sizeof(int) * nb);
     }
     MMX_CHECK_ARG(!alias, "mmx_selfattn_rollout_row: the output or the workspace may not alias an input or each other");
     a.n_layers = n_layers; a.B = B; a.H = H; a.T = T; a.V = V;

@@ -1401,6 +1401,87 @@ def perturb_tokens(ids, scores, counts, want_ranks=False, out=None):
     return (out_ids, out_eot, ranks) if want_ranks else (out_ids, out_eot)
 
 
+def _perturb_rows(what, cam, text_len, T):
+    """The operands the two single-stream builders share: ``cam [B, T + V]`` fp32 in the padded layout, ``text_len [B]`` int32 on the
+    device, the padded text width ``T`` -> ``(cam, text_len, B, T, V)``."""
+    if cam.dim() != 2 or cam.dtype != torch.float32:
+        raise MMXError("%s: cam must be [B, T + V] fp32 in the padded layout, got %s %s" % (what, tuple(cam.shape), cam.dtype))
+    B, N = cam.shape
+    T = int(T)
+    if T < 3 or N - T < 1 or N > _lib.SELFATTN_MAX_TOKENS:
+        raise MMXError("%s: needs T >= 3, V = N - T >= 1 and N <= %d (got N=%d, T=%d)" % (what, _lib.SELFATTN_MAX_TOKENS, N, T))
+    if text_len.dtype != torch.int32 or tuple(text_len.shape) != (B,):
+        raise MMXError("%s: text_len must be [%d] int32 on the device, got %s %s" % (what, B, tuple(text_len.shape), text_len.dtype))
+    return cam.contiguous(), text_len.contiguous(), B, T, N - T
+
+
+def selfattn_perturb_regions(emb, cam, text_len, counts, rows, n_text, positive=False, want_ranks=False, out=None):
+    """The packed input of the image perturbation test of a padded single-stream batch in one launch (``mmx_selfattn_perturb_regions``).
+    ``emb [B, T + V, E]`` fp32 (embedded + LayerNorm-ed rows), ``cam [B, T + V]`` fp32, ``text_len [B]`` int32, ``counts [G]`` int32 on
+    the device (the DISTINCT keep counts, descending), ``rows`` = ``B * sum_g (T + c_g)`` as the host computed it from the same counts,
+    ``n_text = T`` -> ``(x [rows, E] fp32, mask [rows] fp32, pooled [G, B] int64)``, with ``want_ranks`` also ``ranks [B, V]`` int32.
+    Sequence (g, b) starts at row ``off_g + b * (T + c_g)``: item b's T text rows, then its ``c_g`` best regions in rank order (the
+    stable order of ``patch_ranks``; ``positive`` ranks the negated scores); ``mask`` is ``-10000`` at padded text positions;
+    ``pooled`` is the packed row of token ``text_len[b] - 2``.  ``E <= 2**20`` and ``B * G < 2**31`` (the entry refuses more).  ``out``: contiguous ``(x, mask, pooled[, ranks])`` to write to."""
+    what = "selfattn_perturb_regions"
+    _dev(emb, cam, text_len, counts, *(out or ()))
+    cam, text_len, B, T, V = _perturb_rows(what, cam, text_len, n_text)
+    if emb.dim() != 3 or emb.dtype != torch.float32 or tuple(emb.shape[:2]) != (B, T + V) or emb.shape[2] < 1:
+        raise MMXError("%s: emb must be [%d, %d, E] fp32, got %s %s" % (what, B, T + V, tuple(emb.shape), emb.dtype))
+    if counts.dtype != torch.int32 or counts.dim() != 1 or not 1 <= counts.shape[0] <= 64:
+        raise MMXError("%s: counts must be [G] int32 with 1 <= G <= 64, got %s %s" % (what, tuple(counts.shape), counts.dtype))
+    E, G, rows = emb.shape[2], counts.shape[0], int(rows)
+    if not B * G * T <= rows <= B * G * (T + V):
+        raise MMXError("%s: %d packed rows outside B * G * T .. B * G * (T + V) = %d .. %d" % (what, rows, B * G * T, B * G * (T + V)))
+    emb, counts = emb.contiguous(), counts.contiguous()
+    shapes = (((rows, E), torch.float32), ((rows,), torch.float32), ((G, B), torch.int64), ((B, V), torch.int32))
+    if out is not None:
+        if len(out) != (4 if want_ranks else 3):
+            raise MMXError("%s: out must be (x, mask, pooled%s)" % (what, ", ranks" if want_ranks else ""))
+        for t, (shape, dt) in zip(out, shapes):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                raise MMXError("%s: out needs contiguous x [R, E] fp32, mask [R] fp32, pooled [G, B] int64, ranks [B, V] int32" % what)
+        x, mask, pooled, ranks = tuple(out) + (() if want_ranks else (None,))
+    else:
+        x, mask, pooled, ranks = (torch.empty(shape, dtype=dt, device=emb.device) for shape, dt in shapes)
+        if not want_ranks:
+            ranks = None
+    check(lib().mmx_selfattn_perturb_regions(_p(emb), _p(cam), _p(text_len), _p(counts), _p(x), _p(mask), _p(pooled), _p(ranks), B, T, V,
+                                             E, G, rows, int(bool(positive)), _stream()), "mmx_selfattn_perturb_regions")
+    return (x, mask, pooled, ranks) if want_ranks else (x, mask, pooled)
+
+
+def selfattn_perturb_text(ids, segments, cam, text_len, counts, positive=False, out=None):
+    """The S perturbed copies of B padded questions of a single-stream batch in one launch (``mmx_selfattn_perturb_text``).
+    ``ids`` / ``segments [B, T]`` int64, ``cam [B, T + V]`` fp32, ``text_len [B]`` int32, ``counts [S, T]`` int32 on the device
+    (``counts[s][w] = int((1 - step_s) * w)``) -> ``(ids, segments, mask [S, B, T] int64, new_len [S, B] int64)``.  With ``n`` the
+    length of question b (clamped to 3 .. T): positions 0, n - 2 and n - 1 always stay, step s keeps the ``counts[s][n - 3]`` best of
+    the words 1 .. n - 3 (the stable order of ``patch_ranks``; ``positive`` ranks the negated scores) in their original order,
+    left-aligned, zeros behind; ``new_len = 3 + kept``.  ``out``: the four contiguous tensors to write to."""
+    what = "selfattn_perturb_text"
+    _dev(ids, segments, cam, text_len, counts, *(out or ()))
+    if ids.dim() != 2 or ids.dtype != torch.int64 or segments.dtype != torch.int64 or segments.shape != ids.shape:
+        raise MMXError("%s: ids and segments must be [B, T] int64, got %s %s / %s %s"
+                       % (what, tuple(ids.shape), ids.dtype, tuple(segments.shape), segments.dtype))
+    cam, text_len, B, T, V = _perturb_rows(what, cam, text_len, ids.shape[1])
+    if ids.shape[0] != B:
+        raise MMXError("%s: %d questions but %d relevancy rows" % (what, ids.shape[0], B))
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != T or not 1 <= counts.shape[0] <= 64:
+        raise MMXError("%s: counts must be [S, %d] int32 with 1 <= S <= 64, got %s %s" % (what, T, tuple(counts.shape), counts.dtype))
+    S = counts.shape[0]
+    ids, segments, counts = ids.contiguous(), segments.contiguous(), counts.contiguous()
+    shapes = ((S, B, T), (S, B, T), (S, B, T), (S, B))
+    if out is not None:
+        if len(out) != 4 or any(tuple(t.shape) != s or t.dtype != torch.int64 or not t.is_contiguous() for t, s in zip(out, shapes)):
+            raise MMXError("%s: out needs contiguous int64 ids, segments, mask [S, B, T] and new_len [S, B]" % what)
+        o_ids, o_seg, o_mask, new_len = out
+    else:
+        o_ids, o_seg, o_mask, new_len = (torch.empty(s, dtype=torch.int64, device=ids.device) for s in shapes)
+    check(lib().mmx_selfattn_perturb_text(_p(ids), _p(segments), _p(cam), _p(text_len), _p(counts), _p(o_ids), _p(o_seg), _p(o_mask),
+                                          _p(new_len), B, T, V, S, int(bool(positive)), _stream()), "mmx_selfattn_perturb_text")
+    return o_ids, o_seg, o_mask, new_len
+
+
 def head_kernel_shape(n_q, n_k, head_dim, slab_dtype=torch.float32):
     """Does the register-resident whole-head backward (``attention_head.hip``) serve this shape?  (Its eligibility test, host side:
     what decides whether a bf16 gradient stream can pass through an exact-fp32 attention without conversion passes.)"""

@@ -57,6 +57,25 @@ def unpad_row(scores, b, n_text, padded_text):
     return torch.cat((scores[b:b + 1, :n_text], scores[b:b + 1, padded_text:]), dim=1)
 
 
+def pad_rows(rows, lens, padded_text):
+    """The inverse of ``unpad_row``: B per-item rows (``rows[b]``: ``[1, lens[b] + V]``, what the per-item methods return) -> ``[B, T + V]``
+    in the padded layout of the ``*_batch`` methods, ``T = padded_text``: item b's text scores at ``[b, :lens[b]]``, zeros up to ``T``,
+    its V region scores from ``T`` on.  ``lens``: host ints.  This is how the methods without a ragged batched form (``generate_ours``,
+    the LRP methods) feed ``VisualBertPerturbation.perturbation_*_batch``."""
+    if len(rows) == 0 or len(rows) != len(lens):
+        raise ValueError("pad_rows: %d rows for %d lengths" % (len(rows), len(lens)))
+    V = rows[0].shape[-1] - int(lens[0])
+    out = rows[0].new_zeros(len(rows), padded_text + max(V, 0))
+    for b, (row, n) in enumerate(zip(rows, lens)):
+        n = int(n)
+        if row.dim() != 2 or row.shape[0] != 1 or V < 1 or not 0 < n <= padded_text or row.shape[1] != n + V:
+            raise ValueError("pad_rows: row %d is %s, expected [1, %d + %d] with 0 < n_text <= padded_text=%d"
+                             % (b, tuple(row.shape), n, V, padded_text))
+        out[b, :n] = row[0, :n]
+        out[b, padded_text:] = row[0, n:]
+    return out
+
+
 class SelfAttentionGenerator:
     def __init__(self, model):
         self.model = model

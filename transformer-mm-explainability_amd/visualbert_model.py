@@ -12,13 +12,14 @@ TorchScript, ``relprop``.  Eval mode only.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import bert_lrp, bert_tape as bt, lrp
+from . import _lib, bert_lrp, bert_tape as bt, lrp, ops
 from .attention_modules import BertStyleAttention
 
 
@@ -94,6 +95,12 @@ class _DenseAddNorm(nn.Module):                                        # BertSel
         if torch.is_grad_enabled():                                    # Add / Linear inputs of the LRP pass (bert_lrp.py)
             self._lrp_tape = (hidden_states.detach(), d.detach(), input_tensor.detach())
         return self.LayerNorm(d + input_tensor)
+
+
+def _dense_add_norm_rows(mod, hidden, residual):
+    """``_DenseAddNorm`` on ``[rows, E]`` without a tape: a library GEMM (bias fused) + the fused add + LayerNorm kernel."""
+    ln = mod.LayerNorm
+    return ops.add_layernorm(residual, torch.addmm(mod.dense.bias, hidden, mod.dense.weight.t()), ln.weight, ln.bias, ln.eps)[1]
 
 
 class BertAttention(nn.Module):                                        # BERT_ours.py:189-232
@@ -216,6 +223,39 @@ class VisualBERTForClassification(nn.Module):                          # visual_
         if torch.is_grad_enabled():
             self._lrp_tape = (sequence_output.detach(), index if self.pooler_strategy == "vqa" else None, transformed.detach())
         return {"scores": self.classifier[1](transformed).reshape(-1, self.num_labels)}
+
+    @torch.no_grad()
+    def scores_packed(self, x, segments, mask, pooled):
+        """Inference forward of the BERT stack on PACKED rows -- the re-runs of the perturbation test (``visualbert_perturbation``).
+
+        ``x [R, E]`` fp32: the embedded and LayerNorm-ed rows of sequences of several lengths, one after the other; ``segments``: a
+        host list of ``(first row, number of sequences, sequence length)``, one entry per run of equally long sequences; ``mask [R]``
+        fp32: the additive key mask of every row (``-10000`` at padded text positions); ``pooled [P]`` int64: the packed rows the
+        classifier reads.  Returns ``scores [P, num_labels]``.
+
+        The QKV GEMM, dense + add + LayerNorm and the feed-forward are row-wise and run ONCE per layer on all R rows; only the
+        attention knows the sequences (one ``ops.attn_fwd`` launch per segment on views of the packed QKV / O buffers); the classifier
+        runs on the pooled rows.  Grad-free; writes no capture slab and no tape, and leaves those of an earlier pass alone."""
+        if self.pooler_strategy != "vqa":
+            raise NotImplementedError("scores_packed pools one token per sequence (pooler_strategy == 'vqa')")
+        R, E = x.shape
+        for blk in self.bert.encoder.layer:
+            att = blk.attention.self
+            H, D = att.num_attention_heads, att.attention_head_size
+            W, b = bt.packed_linear((att.query, att.key, att.value))
+            qkv = torch.addmm(b, x, W.t())
+            o = torch.empty(R, E, dtype=torch.float32, device=x.device)
+            for first, count, length in segments:
+                rows = slice(first, first + count * length)
+                q = qkv[rows].view(count, length, 3, H, D)
+                ops.attn_fwd(q[:, :, 0], q[:, :, 1], q[:, :, 2], math.sqrt(D), _lib.SCALE_SCORES, mask=mask[rows].view(count, 1, length),
+                             layout="bnhd", out=o[rows].view(count, length, H, D))
+            x = _dense_add_norm_rows(blk.attention.output, o, x)
+            inter = blk.intermediate
+            x = _dense_add_norm_rows(blk.output, inter.intermediate_act_fn(torch.addmm(inter.dense.bias, x, inter.dense.weight.t())), x)
+        head = self.classifier[0]                                      # (not through its forward: that resets the module's LRP tape)
+        picked = head.LayerNorm(head.transform_act_fn(head.dense(x[pooled.reshape(-1)])))
+        return self.classifier[1](picked).reshape(-1, self.num_labels)
 
     def relprop(self, cam, **kwargs):
         """``model.relprop(one_hot, alpha=1)`` (visual_bert.py:398-403, :150-153): the classifier's two Linear rules, the
