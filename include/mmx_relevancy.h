@@ -112,8 +112,10 @@ const char* mmx_last_error(void);
  *   "clip_head_fused"    1 (default) CLIP interpret / interpret_grouped take the similarity head's gradients from mmx_clip_head_f32 (one
  *                        launch) | 0: the autograd head over CLIP.logits (A / B runs; another rounding of the same formula)
  *   "gemm_rows_tm"       32 (default) | 64: rows per workgroup tile of mmx_gemm_rows_f32 (same products, another order of the k sum)
- *   "gemm_rows_tn"       0 (default: chosen from N and K) | 32 | 64: columns per workgroup tile of mmx_gemm_rows_f32 at 32 rows (same
+ *   "gemm_rows_tn"       0 (default: 32 for N <= 512, else 64) | 32 | 64: columns per workgroup tile of mmx_gemm_rows_f32 at 32 rows (same
  *                        products, another order of the k sum; 64-row tiles are always 64 wide)
+ *   "gemm_rows_pf"       0 (default: 4) | 3 | 4: slabs of K that mmx_gemm_rows_f32 / mmx_gemm_rows_bias_f32 request ahead
+ *                        into registers (A / B runs; the same bits at every depth: the order of the k sum does not depend on it)
  *   "debug_flags"        profiling only (phase skipping), 0 in production; one meaning per bit for every chain kernel the dispatcher
  *                        may pick: 1 return before the hand-off / combine | 4 matrix waves skip the MFMAs | 8 layer-group kernel:
  *                        ticket without combine | 16 column kernel: no block rotation

@@ -162,11 +162,22 @@ static std::vector<int> shuffled(int cap, int keep) {
     v.resize(keep);
     return v;
 }
-// fp32: the slab-count and row-list cases of tests/test_gpu_gemm_rows_pipeline.py
+// fp32 at another depth of the register ring (option "gemm_rows_pf"): slab counts around the ring -- one fewer, exactly the ring, one more
+// and ragged, two rounds and a ragged remainder -- and the shuffled row list (tests/test_gpu_gemm_rows_depth.py walks every count on the GPU)
+template <int TM, int TN, int BK, int PF>
+static int run_depth_f32() {
+    typedef F32<TM, TN, BK, PF> Kn;
+    int bad = 0;
+    std::vector<int> some = {0, 1, 2, 8, 9, 10, 11, 12, 13, 14, 15, 16};
+    for (int K : {(PF - 1) * BK, PF * BK, (PF + 1) * BK + 4, (2 * PF + 1) * BK + 4}) bad += run_case<Kn>(24, 100, K, some, -1);
+    bad += run_case<Kn>(70, 100, 200, shuffled(70, 45), -1);
+    return bad;
+}
+// fp32: the slab-count and row-list cases of tests/test_gpu_gemm_rows_pipeline.py at depth 3, then the other depth the library ships
 template <int TM, int TN, int BK>
 static int run_all_f32() {
     typedef F32<TM, TN, BK, 3> Kn;
-    int bad = 0;
+    int bad = run_depth_f32<TM, TN, BK, 4>();
     std::vector<int> some = {0, 1, 2, 8, 9, 10, 11, 12, 13, 14, 15, 16};
     for (int K : {4, 20, 32, 36, 64, 68, 96, 128, 192, 200, 256})
         for (int N : {36, 100}) bad += run_case<Kn>(24, N, K, some, -1);

@@ -17,11 +17,13 @@ static int g_text_live_rows = 1;   // option "text_live_rows": 1 (default) the r
 static int g_gemm_rows_tm = 32;    // option "gemm_rows_tm": rows per workgroup tile, 32 (default) or 64 (A / B runs)
 static int g_gemm_rows_tn = 0;     // option "gemm_rows_tn": columns per workgroup tile at 32 rows, 0 (default: from the shape) | 32 | 64 (A / B runs)
 static int g_text_live_rows_fwd = 1;   // option "text_live_rows_fwd": 1 (default) the forward of that tower takes the route too | 0: dense forward
+static int g_gemm_rows_pf = 0;     // option "gemm_rows_pf": slabs of K requested ahead (the register ring), 0 (default: rows_depth) | 3 | 4 (A / B runs)
 bool text_live_rows_option(const char* key, int value) {
     if (strcmp(key, "text_live_rows") == 0 && value >= 0 && value <= 1) { g_text_live_rows = value; return true; }
     if (strcmp(key, "text_live_rows_fwd") == 0 && value >= 0 && value <= 1) { g_text_live_rows_fwd = value; return true; }
     if (strcmp(key, "gemm_rows_tm") == 0 && (value == 32 || value == 64)) { g_gemm_rows_tm = value; return true; }
     if (strcmp(key, "gemm_rows_tn") == 0 && (value == 0 || value == 32 || value == 64)) { g_gemm_rows_tn = value; return true; }
+    if (strcmp(key, "gemm_rows_pf") == 0 && (value == 0 || value == 3 || value == 4)) { g_gemm_rows_pf = value; return true; }
     return false;
 }
 int gemm_rows_tn_option() { return g_gemm_rows_tn; }
@@ -144,26 +146,39 @@ __global__ __launch_bounds__(256, 2) void gemm_rows_f32_kernel(const float* __re
 }
 
 // The tile of a launch: rows x columns per workgroup, chosen from the options and the shape only (the live count stays on the device).
-struct RowsTile { int tm, tn; };
+// pf: the depth of the register ring, option "gemm_rows_pf" or rows_depth() of the tile.  What profiles/gemm_rows_depth_probe.txt measured
+// at the step's shapes (531 live rows): four slabs ahead beat three on every tile at every shape, six and eight were no better than four;
+// at four, 32 columns beat 64 at N = 512 for K = 512, 1536 and 2048 (twice the workgroups where 64 columns leave half the chip idle) and
+// lost or tied at N = 1536 and 2048 -- the rule of gemm_rows_f16.hip.
+struct RowsTile { int tm, tn, pf; };
+static int rows_depth(int tm, int tn) { return 4; }
 static RowsTile rows_tile(int N, int K) {
-    if (g_gemm_rows_tm == 64) return {64, 64};
-    const int tn = g_gemm_rows_tn ? g_gemm_rows_tn : 64;
-    return {32, tn};
+    const int tm = g_gemm_rows_tm == 64 ? 64 : 32;
+    const int tn = tm == 64 ? 64 : (g_gemm_rows_tn ? g_gemm_rows_tn : (N <= 512 ? 32 : 64));
+    return {tm, tn, g_gemm_rows_pf ? g_gemm_rows_pf : rows_depth(tm, tn)};
 }
 
 }  // namespace mmx
 
 #ifndef MMX_GEMM_ROWS_EMU   // (the host emulation takes the kernel, not the launches)
 namespace mmx {
+// One tile at the depth pf of its register ring (the depths option "gemm_rows_pf" accepts; rows_tile() hands out no other).
+template <int TM, int TN, int BK, int EPI, class... Args>
+static void launch_gemm_rows_depth(int pf, unsigned g, hipStream_t s, Args... args) {
+    if (pf == 3)
+        gemm_rows_f32_kernel<TM, TN, BK, 3, EPI><<<g, 256, 0, s>>>(args...);
+    else
+        gemm_rows_f32_kernel<TM, TN, BK, 4, EPI><<<g, 256, 0, s>>>(args...);
+}
 template <int EPI>
 static void launch_gemm_rows(RowsTile t, unsigned g, hipStream_t s, const float* A, const float* W, float* C, const int* rows,
                              const int* count, int cap_rows, int N, int K, const float* bias, float* C2) {
     if (t.tm == 64)
-        gemm_rows_f32_kernel<64, 64, 32, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+        launch_gemm_rows_depth<64, 64, 32, EPI>(t.pf, g, s, A, W, C, rows, count, cap_rows, N, K, bias, C2);
     else if (t.tn == 32)
-        gemm_rows_f32_kernel<32, 32, 64, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+        launch_gemm_rows_depth<32, 32, 64, EPI>(t.pf, g, s, A, W, C, rows, count, cap_rows, N, K, bias, C2);
     else
-        gemm_rows_f32_kernel<32, 64, 32, 3, EPI><<<g, 256, 0, s>>>(A, W, C, rows, count, cap_rows, N, K, bias, C2);
+        launch_gemm_rows_depth<32, 64, 32, EPI>(t.pf, g, s, A, W, C, rows, count, cap_rows, N, K, bias, C2);
 }
 
 }  // namespace mmx

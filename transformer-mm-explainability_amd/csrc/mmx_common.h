@@ -243,7 +243,7 @@ int chain_rows_layer_launch(const void* attn, const void* grad, const float* R_i
                             int64_t attn_bstride, hipStream_t s, int debug = 0);
 bool bmm_f32_tiles_try(const float* A, const float* B, const float* Cin, float* C, int batch, int M, int N, int K, int trans_a,
                        int64_t sa, int64_t sb, int64_t sc, int nan_to_zero, int cin_is_row, hipStream_t s);
-bool text_live_rows_option(const char* key, int value);   // gemm_rows_f32.hip: options "text_live_rows", "text_live_rows_fwd", "gemm_rows_tm", "gemm_rows_tn"
+bool text_live_rows_option(const char* key, int value);   // gemm_rows_f32.hip: options "text_live_rows", "text_live_rows_fwd", "gemm_rows_tm", "gemm_rows_tn", "gemm_rows_pf"
 int gemm_rows_tn_option();                                 // gemm_rows_f32.hip: option "gemm_rows_tn" as set (0: from the shape)
 bool gemm_rows_half_option(const char* key, int value);   // gemm_rows_f16.hip: option "text_live_rows_half"
 bool clip_head_option(const char* key, int value);        // clip_head.hip: option "clip_head_fused"
