@@ -61,6 +61,9 @@ def main():
                              "ours_no_normalization", "ours_no_lrp", "ours_no_lrp_no_norm", "ablation_no_aggregation",
                              "ablation_no_self_in_10"])
     ap.add_argument("--graph-slots", type=int, default=16, help="target slots of the captured explain pass (0: eager)")
+    ap.add_argument("--batch-baselines", type=int, default=1, choices=[0, 1],
+                    help="1: rollout / raw_attn / attn_gradcam explain all kept queries of an image in one pass "
+                         "(MaskGenerator(batch_baselines=True)); 0: the reference's per-query loop")
     ap.add_argument("--keep-top", type=int, default=8, help="random-init logits are flat: keep this many queries per image")
     ap.add_argument("--resume-dir", default=None)
     ap.add_argument("--warmup-images", type=int, default=2,
@@ -77,7 +80,7 @@ def main():
         tuned_gemms.enable("detr")     # pre-tuned library-GEMM selection for the 100-query decoder shapes (tuning stays off)
     torch.manual_seed(0)
     model = detr_model.detr_resnet50_head().to(dev).eval()
-    mg = MaskGenerator(model, threshold=0.5, graph_slots=args.graph_slots or None)
+    mg = MaskGenerator(model, threshold=0.5, graph_slots=args.graph_slots or None, batch_baselines=bool(args.batch_baselines))
     queries = [0]
 
     def masks_of(k):
@@ -116,7 +119,7 @@ def main():
     if rank == 0:
         print(json.dumps({"images": len(ids), "n_gpus": world, "eval_imgs_merge_matches": merge_ok, "seconds": round(elapsed, 3), "warmup_images": args.warmup_images,
                           "images_per_s": round(len(ids) / elapsed, 1),
-                          "queries_per_s_this_rank": round(queries[0] / elapsed, 1), "method": args.method,
+                          "queries_per_s_this_rank": round(queries[0] / elapsed, 1), "method": args.method, "batch_baselines": args.batch_baselines,
                           "mean_kept": round(float(table[:, 0].mean()), 2),
                           "mean_mask_area": round(float(table[:, 1].mean()), 4)}))
     if world > 1:

@@ -792,6 +792,45 @@ int mmx_detr_decoder_rows(const void* const* self_attn, const void* const* self_
                           void* s_out_dev, void* diag_min_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The attention-only baselines of DETR for ALL K kept queries of one image in one pass (csrc/detr_baselines.hip): raw attention
+ * (DETR/modules/ExplanationGenerator.py:226-238), rollout (:240-273 with compute_rollout_attention, :5-16) and attention GradCAM
+ * (:275-305).  Every method returns row t_k = targets[k] of a [Q, Ni] map, out [K, Ni] fp32, and works on row vectors only.
+ * Notation: P_x [H, Q, Ni] the LAST decoder layer's cross-attention slab, A_l [H, Ni, Ni] the encoder self-attention slabs,
+ * B_l [H, Q, Q] the decoder self-attention slabs, a bar = (sum_h .) / H, M^ = (Mbar + I) / rowsum(Mbar + I).
+ *
+ * mmx_detr_cross_rows:
+ *   cross_grad_dev == NULL: raw attention, out[k, :] = Pbar_x[t_k, :]; one launch, no workspace (workspace_dev may be NULL).
+ *   cross_grad_dev given:   GradCAM.  w[k, h] = (sum_{q, j} grad[k, h, q, j]) / float(Q Ni), the sum over the WHOLE [Q, Ni] block as
+ *                           grad.mean([1, 2]) states it (rows q != t_k are not assumed to be zero), the sum first, then one division;
+ *                           out[k, :] = max(0, (sum_h P_x[h, t_k, :] w[k, h]) / H) (a NaN stays a NaN).  grad_bstride (elements) is
+ *                           H Q Ni for per-sample gradient slabs [K, H, Q, Ni] or 0 when ONE slab [H, Q, Ni] serves every k.  Two
+ *                           launches: (k, h, strip of 8192 floats) sums into the workspace, then (k, 256 columns) adds the strips'
+ *                           sums in order.  workspace: mmx_detr_cross_rows_workspace_bytes(K, H, Q, Ni), 16-byte aligned.
+ * mmx_detr_rollout_rows: with R_qq = B^_Ld ... B^_1 and R_ii = A^_Le ... A^_1, row t_k of R_qq^T (Pbar_x R_ii) is
+ *   ((R_qq e_t)^T Pbar_x) R_ii:   1. u_k = B^_Ld( ... (B^_1 e_t)),  y <- (Bbar_l y + y) / r_l, r_l[i] = 1 + sum_j Bbar_l[i, j];
+ *   2. s_k = u_k^T Pbar_x;   3. x <- s_k, for l = Le ... 1: x <- w Abar_l + w, w[i] = x[i] / r_l[i], r_l[i] = 1 + sum_j Abar_l[i, j].
+ *   No Ni x Ni product exists.  enc_table / dec_self_table: HOST tables of n_enc / n_dec device slabs, entry 0 the FIRST layer.
+ *   Every slab is read once: Le x ceil(Ni / 4) workgroups take the head mean of strips of four rows (one contiguous, 16-byte aligned
+ *   run per head, 16-byte loads) into the workspace with r_l; the K vectors then go through each layer's head mean together, a strip of
+ *   eight rows and eight vectors per workgroup, partials per strip summed in strip order by the next launch.  Le H Ni^2 4 bytes of
+ *   slabs (173 MB at 950 tokens) plus Le Ni^2 4 of head means written and read back.
+ *   workspace: mmx_detr_rollout_rows_workspace_bytes(n_enc, n_dec, K, Q, Ni) bytes, 16-byte aligned, caller-owned, stream-ordered.
+ * targets_dev: int64 [K] on the device, clamped to 0 .. Q - 1 inside the kernels before they form an address.
+ * Limits: 1 <= Q <= 128, 1 <= Ni <= 2048, 1 <= H <= 32, 1 <= K <= 2^20, tables of 1 .. MMX_BASELINES_MAX_TABLE entries, fp32
+ * contiguous slabs.  Plain launches ordered by the stream, fixed summation orders, no atomics: two calls give the same bits, and row
+ * k's bits depend neither on K nor on k's position.  Every argument is checked before any HIP call: a null required pointer or table
+ * entry, a size outside the limits, a grad_bstride that is neither 0 nor H Q Ni, a workspace that is too small or not 16-byte
+ * aligned, an output or workspace that overlaps an input or the other one return MMX_EINVAL with a message in mmx_last_error().
+ * The workspace queries return 0 for arguments the entries refuse. */
+size_t mmx_detr_cross_rows_workspace_bytes(int K, int H, int Q, int Ni);
+int mmx_detr_cross_rows(const void* cross_attn_dev, const void* cross_grad_dev, int64_t grad_bstride, const void* targets_dev,
+                        void* out_dev, int K, int H, int Q, int Ni, void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t mmx_detr_rollout_rows_workspace_bytes(int n_enc, int n_dec, int K, int Q, int Ni);
+int mmx_detr_rollout_rows(const void* const* enc_table, int n_enc, const void* const* dec_self_table, int n_dec,
+                          const void* cross_attn_dev, const void* targets_dev, void* out_dev, int K, int H, int Q, int Ni,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * LRP relevance through the attention core: the two `einsum` relprops inside the reference's
  * MultiheadAttention.relprop (DETR/modules/layers.py:770-781; einsum = RelPropSimple, layers.py:54-66, each result halved;
  * softmax / dropout relprops are the identity, layers.py:170-186), which the reference evaluates by re-running the einsums

@@ -106,6 +106,10 @@ _PROTOTYPES = {
     "mmx_attn_relprop_phase": (_i, [_vp] * 5 + [_i64] * 15 + [_vp] * 5 + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp]),
     "mmx_detr_decoder_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mmx_detr_decoder_rows": (_i, [_vpp] * 4 + [_i] * 5 + [_i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmx_detr_cross_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mmx_detr_cross_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mmx_detr_rollout_rows_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mmx_detr_rollout_rows": (_i, [_vpp, _i, _vpp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mmx_linear_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_rows_to_dense": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_rows_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -199,6 +199,19 @@ class MultiheadAttention(_SlabOwner):
                 ops.backward_gemm(dv.reshape(K, -1, E), self.v_proj.weight, gemm_dtype))
 
     @torch.no_grad()
+    def backward_shared_slab(self, tape, d_out):
+        """The cross-attention form of ``backward_shared_into`` (``same_source=False``) up to and including the attention backward:
+        the SAME product and the same launch on the same inputs, so the gradient slab gets the same bits; the input-gradient GEMMs
+        that would follow are left out (a backward cut short at this block)."""
+        q, k, v, o_fwd = tape
+        K, T, H, D = d_out.shape[0], d_out.shape[1], self.num_heads, self.head_dim
+        d_o = torch.matmul(d_out, self.out_proj.weight).view(K, T, H, D)
+        dq = torch.empty(K, T, H, D, dtype=torch.float32, device=d_out.device)
+        dkv = torch.empty(K, k.shape[1], 2, H, D, dtype=torch.float32, device=d_out.device)
+        ops.attn_capture_bwd(q, k, v, self._probs, d_o, self._grads, float(D) ** -0.5, _lib.SCALE_Q_FIRST, need_dqkv=True,
+                             layout="bnhd", batch=K, o=o_fwd, out=(dq, dkv[:, :, 0], dkv[:, :, 1]))
+
+    @torch.no_grad()
     def backward_shared_into(self, tape, d_out, acc_q, acc_kv=None, same_source=True, kv_weights=None):
         """``backward_shared`` with the input-gradient GEMMs ACCUMULATING (beta = 1) into buffers the caller owns, fp32.
 

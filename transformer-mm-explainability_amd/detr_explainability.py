@@ -360,6 +360,91 @@ class Generator:
         self.R_q_i = self.gradcam(last.get_attn().detach(), last.get_attn_gradients().detach())
         return self.R_q_i.unsqueeze_(0)[:, target_index, :].unsqueeze_(0)
 
+    # ------------------------------------------------------------------ the three baselines, all kept queries in one pass
+    @staticmethod
+    def _multi_targets(img, target_indices, what):
+        if img.shape[0] != 1:
+            raise ValueError("%s explains the queries of ONE image (got batch %d)" % (what, img.shape[0]))
+        return torch.as_tensor(target_indices, device=img.device).reshape(-1)
+
+    def generate_raw_attn_multi(self, img, target_indices):
+        """``torch.cat([generate_raw_attn(img, t) for t in target_indices], dim=2)`` -- ``[1, 1, K, Ni]`` -- from ONE forward and one
+        launch (``ops.detr_raw_rows``): row ``t`` of the head mean of the last decoder cross-attention.  Nothing is read back."""
+        targets = self._multi_targets(img, target_indices, "generate_raw_attn_multi")
+        with torch.no_grad():
+            self.model(img)
+        cross = self.model.transformer.decoder.layers[-1].multihead_attn.get_attn().detach()
+        cross = cross.reshape(-1, cross.shape[-2], cross.shape[-1])
+        self.R_q_i = None
+        return ops.detr_raw_rows(cross, targets).reshape(1, 1, targets.numel(), -1)
+
+    def generate_rollout_multi(self, img, target_indices):
+        """``torch.cat([generate_rollout(img, t) for t in target_indices], dim=2)`` -- ``[1, 1, K, Ni]`` -- from ONE forward.
+
+        Row ``t`` of ``R_qq^T . (C . R_ii)`` is ``((R_qq e_t)^T C) R_ii``: a chain of ``Q``-vector mat-vecs with the normalised decoder
+        maps, one vector-matrix product with the head-mean cross-attention ``C`` and a chain of vector-matrix products with the
+        normalised encoder maps, all K vectors together (``ops.detr_rollout_rows``).  ``R_ii``, ``R_qq`` and the 950^3 products of the
+        per-query route never exist: ``self.R_i_i`` / ``R_q_q`` / ``R_q_i`` are ``None`` afterwards."""
+        targets = self._multi_targets(img, target_indices, "generate_rollout_multi")
+        with torch.no_grad():
+            self.model(img)
+        tr = self.model.transformer
+
+        def slab(mod):
+            a = mod.get_attn().detach()
+            return a.reshape(-1, a.shape[-2], a.shape[-1])
+
+        self.R_i_i = self.R_q_q = self.R_q_i = None
+        out = ops.detr_rollout_rows([slab(b.self_attn) for b in tr.encoder.layers], [slab(b.self_attn) for b in tr.decoder.layers],
+                                    slab(tr.decoder.layers[-1].multihead_attn), targets)
+        return out.reshape(1, 1, targets.numel(), -1)
+
+    def generate_attn_gradcam_multi(self, img, target_indices, index=None):
+        """``torch.cat([generate_attn_gradcam(img, t, index) for t in target_indices], dim=2)`` -- ``[1, 1, K, Ni]``.
+
+        A body with ``forward_shared`` (``detr_model``): ONE forward, K one-hot seeds by scatter, and a backward that STOPS once the
+        top decoder layer's cross-attention gradient slab is complete -- the only slab GradCAM reads; the eleven layers below it are
+        never differentiated.  ``index``: ``None`` = each target's arg-max class; a tensor whose entries ``< 0`` mean arg-max, as in
+        ``generate_ours_multi``.  Another body: the replicated-batch autograd route of ``generate_ours_multi``.  Then one
+        ``ops.detr_gradcam_rows`` call for the K rows."""
+        targets = self._multi_targets(img, target_indices, "generate_attn_gradcam_multi")
+        K = targets.numel()
+        last = self.model.transformer.decoder.layers[-1].multihead_attn
+        if hasattr(self.model, "forward_shared"):
+            with torch.no_grad():
+                logits, state = self.model.forward_shared(img, K)
+                own = logits[0].index_select(0, targets)[:, :-1].argmax(dim=-1)
+                if index is None:
+                    index = own
+                else:
+                    index = torch.as_tensor(index, device=img.device).reshape(-1)
+                    index = torch.where(index < 0, own, index)
+                n_cls = logits.shape[-1]
+                one_hot = torch.zeros(K, logits.shape[1] * n_cls, dtype=logits.dtype, device=img.device)
+                one_hot.scatter_(1, (targets * n_cls + index).reshape(K, 1), 1.0)
+                self.model.backward_shared(state, one_hot.view(K, logits.shape[1], n_cls), stop_after_top_cross=True)
+            cross = last.get_attn().detach()                                   # [H, Q, Ni]: one forward
+        else:
+            rows = torch.arange(K, device=img.device)
+            batch = img.expand(K, *img.shape[1:])
+            outputs = rules.forward_for_backward(self.model, lambda: self.model(batch)["pred_logits"])
+            own = outputs[rows, targets, :-1].argmax(dim=-1)
+            if index is None:
+                index = own
+            else:
+                index = torch.as_tensor(index, device=img.device).reshape(-1)
+                index = torch.where(index < 0, own, index)
+            one_hot = torch.zeros_like(outputs)
+            one_hot[rows, targets, index] = 1
+            self.model.zero_grad()
+            torch.sum(one_hot * outputs).backward(retain_graph=True)
+            cross = last.get_attn().detach()                                   # [K * H, Q, Ni]: K identical forwards
+            cross = cross.reshape(K, -1, cross.shape[-2], cross.shape[-1])[0]
+        grad = last.get_attn_gradients().detach()
+        grad = grad.reshape(-1, grad.shape[-2], grad.shape[-1])                # [K * H, Q, Ni]
+        self.R_q_i = None
+        return ops.detr_gradcam_rows(cross.reshape(-1, cross.shape[-2], cross.shape[-1]), grad, targets).reshape(1, 1, K, -1)
+
     def generate_transformer_att(self, img, target_index, index=None):
         """Reference :64-108: rule 5 on the LRP cam of the LAST decoder cross-attention (needs the body's ``relprop``)."""
         _require_relprop(self.model)
@@ -440,6 +525,10 @@ class MaskGenerator:
     like the reference's buffer.  For the three rule-based methods every kept query goes through
     ``Generator.generate_ours_multi`` in one pass and all Otsu thresholds are one launch
     (``postprocess.otsu_masks``); the remaining methods run the reference's per-query loop.
+
+    ``batch_baselines=True`` (default off): ``rollout``, ``raw_attn`` and ``attn_gradcam`` explain all kept queries in one pass too
+    (``Generator.generate_*_multi``; with ``graph_slots`` the captured ``GraphedBaselinesMulti``).  The LRP baselines and
+    ``ablation_no_aggregation`` stay per query.
     """
 
     _BATCHED = {"ours_no_lrp": {}, "ablation_no_self_in_10": {"apply_self_in_rule_10": False},
@@ -447,7 +536,9 @@ class MaskGenerator:
 
     _PER_QUERY = ("ablation_no_aggregation", "ours_with_lrp", "raw_attn", "rollout", "attn_gradcam", "transformer_att", "partial_lrp")
 
-    def __init__(self, model, threshold=0.5, graph_slots=None, max_graphs=4):
+    _BASELINES_MULTI = ("rollout", "raw_attn", "attn_gradcam")
+
+    def __init__(self, model, threshold=0.5, graph_slots=None, max_graphs=4, batch_baselines=False):
         """``graph_slots`` (e.g. 16): run the batched methods through ``GraphedGenerateOursMulti`` with that many target
         slots (captured on the first image of a given feature-map size; the evaluator's images are resized to a common
         size per batch, ``DETR/datasets/coco.py:138-140``).  Each captured pass owns a private memory pool and its pinned
@@ -460,6 +551,7 @@ class MaskGenerator:
             raise ValueError("graph_slots must be >= 2 (the K-slot pass shares ONE forward between its slots)")
         self.graph_slots = graph_slots
         self.max_graphs = max_graphs
+        self.batch_baselines = bool(batch_baselines)
         self._graphs = collections.OrderedDict()     # (method, feature shape) -> captured pass, least recently used first
         self._diag_running = None                    # smallest handle_residual word of the batched passes not checked yet
         self.last_kept = 0
@@ -475,6 +567,16 @@ class MaskGenerator:
         if self._diag_running is not None:
             word, self._diag_running = float(self._diag_running), None
             assert word >= 0, "handle_residual: diag(R - I) < 0 (or NaN) in a relevancy pass"
+
+    def _graph_for(self, key, make):
+        """The captured pass of ``key`` = (method, feature shape), made on first use; at most ``max_graphs`` are kept, the least
+        recently used one evicted."""
+        if key not in self._graphs:
+            while len(self._graphs) >= self.max_graphs:
+                self._graphs.popitem(last=False)
+            self._graphs[key] = make()
+        self._graphs.move_to_end(key)
+        return self._graphs[key]
 
     def _per_query(self, img, idx, method):
         """The reference's per-query dispatch (DETR/mask_generator.py:91-113) for the methods that are not batched here; the
@@ -513,17 +615,22 @@ class MaskGenerator:
         # the generator re-derives it from a second, identical forward)
         classes = outputs["pred_logits"][0, kept, :-1].argmax(dim=-1)
         if method in self._BATCHED and self.graph_slots and hasattr(self.model, "forward_shared"):
-            key = (method, tuple(img.shape))
-            if key not in self._graphs:
-                while len(self._graphs) >= self.max_graphs:
-                    self._graphs.popitem(last=False)
-                self._graphs[key] = GraphedGenerateOursMulti(self.model, img, self.graph_slots, **self._BATCHED[method])
-            self._graphs.move_to_end(key)
-            cams = self._graphs[key](img, kept, index=classes, check=self._fold_diag)[0, 0]
+            run = self._graph_for((method, tuple(img.shape)),
+                                  lambda: GraphedGenerateOursMulti(self.model, img, self.graph_slots, **self._BATCHED[method]))
+            cams = run(img, kept, index=classes, check=self._fold_diag)[0, 0]
         elif method in self._BATCHED:
             cams = self.gen.generate_ours_multi(img, kept, index=classes, check_diag="defer",
                                                 **self._BATCHED[method])[0, 0]                             # [K, Ni]
             self._fold_diag(self.gen.diag_min)
+        elif self.batch_baselines and method in self._BASELINES_MULTI and self.graph_slots \
+                and hasattr(self.model, "forward_shared"):
+            run = self._graph_for((method, tuple(img.shape)), lambda: GraphedBaselinesMulti(self.model, img, method, self.graph_slots))
+            cams = run(img, kept, index=classes)[0, 0]
+        elif self.batch_baselines and method in self._BASELINES_MULTI:
+            if method == "attn_gradcam":
+                cams = self.gen.generate_attn_gradcam_multi(img, kept, index=classes)[0, 0]
+            else:
+                cams = getattr(self.gen, "generate_%s_multi" % method)(img, kept)[0, 0]
         else:
             if method not in self._PER_QUERY:
                 # the reference's error convention (DETR/mask_generator.py:111-113): a message and ``None``, reached -- as there,
@@ -601,5 +708,70 @@ class GraphedGenerateOursMulti:
                 check(self.diag_min)
             elif check and self.diag_min is not None:
                 assert self.diag_min.item() >= 0
+            chunks.append(self.out[:, :, :part.numel()].clone())
+        return torch.cat(chunks, dim=2) if len(chunks) != 1 else chunks[0]
+
+
+class GraphedBaselinesMulti:
+    """``Generator.generate_rollout_multi`` / ``generate_raw_attn_multi`` / ``generate_attn_gradcam_multi`` captured into a hipGraph
+    for a FIXED number of target slots ``K`` and replayed, with the slot handling of ``GraphedGenerateOursMulti``: an image with fewer
+    kept queries fills the spare slots with repeats of its last target (their rows are dropped), one with more is processed in chunks
+    of ``K``.  Raw attention and rollout take any ``K >= 1``; GradCAM keeps ``K >= 2`` and needs a body with ``forward_shared``, so that
+    the capture never takes the autograd route.
+
+        run = GraphedBaselinesMulti(model, example_features, "rollout", K=16)
+        maps = run(features, kept_query_indices)        # [1, 1, len(kept), Ni], == Generator(model).generate_rollout_multi(...)
+    """
+
+    METHODS = ("rollout", "raw_attn", "attn_gradcam")
+
+    def __init__(self, model, example_img, method, K=16, warmup=2):
+        if method not in self.METHODS:
+            raise ValueError("GraphedBaselinesMulti: method must be one of %s, got %r" % (self.METHODS, method))
+        if K < 1:
+            raise ValueError("GraphedBaselinesMulti: K >= 1 target slots")
+        if method == "attn_gradcam":
+            if not hasattr(model, "forward_shared"):
+                raise ValueError("GraphedBaselinesMulti: attn_gradcam needs a body with forward_shared / backward_shared (detr_model)")
+            if K < 2:
+                raise ValueError("GraphedBaselinesMulti: attn_gradcam needs K >= 2 target slots (as GraphedGenerateOursMulti: a "
+                                 "capture must never take the autograd route)")
+        self.K, self.method = K, method
+        self.img = example_img.clone()
+        self.targets = torch.zeros(K, dtype=torch.long, device=example_img.device)
+        self.index = torch.full((K,), -1, dtype=torch.long, device=example_img.device)      # -1: this pass's own arg-max
+        self.gen = Generator(model)
+        if method == "attn_gradcam":
+            self._call = lambda: self.gen.generate_attn_gradcam_multi(self.img, self.targets, index=self.index)
+        else:
+            fn = getattr(self.gen, "generate_%s_multi" % method)
+            self._call = lambda: fn(self.img, self.targets)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._call()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(self.graph):
+            self.out = self._call()
+        self._pinned = ops.pinned_state(model)        # slabs and scratch whose addresses the graph holds
+
+    def __call__(self, img, target_indices, index=None):
+        targets = torch.as_tensor(target_indices, device=self.img.device).reshape(-1)
+        n = targets.numel()
+        classes = None if index is None else torch.as_tensor(index, device=self.img.device).reshape(-1)
+        self.img.copy_(img)
+        chunks = []
+        for i in range(0, n, self.K):
+            part = targets[i:i + self.K]
+            self.targets[:part.numel()] = part
+            self.index.fill_(-1)
+            if classes is not None:
+                self.index[:part.numel()] = classes[i:i + self.K]
+            if part.numel() < self.K:
+                self.targets[part.numel():] = part[-1]
+                self.index[part.numel():] = self.index[part.numel() - 1]
+            self.graph.replay()
             chunks.append(self.out[:, :, :part.numel()].clone())
         return torch.cat(chunks, dim=2) if len(chunks) != 1 else chunks[0]

@@ -229,19 +229,27 @@ class TransformerDecoderLayer(nn.Module, _FeedForward):
         out, ln3 = _add_ln_fwd(self.norm3, tgt2, ff)
         return out, (t_self, ln1, t_cross, ln2, h, ln3, (h > 0).to(h.dtype))
 
-    def backward_shared(self, tape, d_out, need_tgt_grad=True, gemm_dtype=torch.float32, d_memory=None):
+    def backward_shared(self, tape, d_out, need_tgt_grad=True, gemm_dtype=torch.float32, d_memory=None, stop_after_cross=False):
         """``d_out [K, Q, E]`` -> ``(d_tgt [K, Q, E] | None, d_memory [K, N, E])``.  fp32: the memory gradient ACCUMULATES into
-        ``d_memory`` (in place) when one is handed in; the opt-in bf16 route returns this layer's share."""
+        ``d_memory`` (in place) when one is handed in; the opt-in bf16 route returns this layer's share.
+        ``stop_after_cross``: return ``(None, None)`` as soon as the cross-attention's gradient slab is written -- by the same launches
+        on the same inputs as in the full pass, so the slab holds the same bits (attention GradCAM reads nothing below it)."""
         t_self, ln1, t_cross, ln2, h, ln3, live = tape
         d_z3 = _ln_bwd(self.norm3, ln3, d_out)                             # w.r.t. tgt2 + ff
         if gemm_dtype != torch.float32:
             d_z2 = _ln_bwd(self.norm2, ln2, d_z3 + self._ffn_bwd_shared(h, d_z3, gemm_dtype))
+            if stop_after_cross:
+                self.multihead_attn.backward_shared(t_cross, d_z2, True, gemm_dtype)
+                return None, None
             dq, dk, dv = self.multihead_attn.backward_shared(t_cross, d_z2, True, gemm_dtype)
             d_z1 = _ln_bwd(self.norm1, ln1, d_z2 + dq)
             sq, sk, sv = self.self_attn.backward_shared(t_self, d_z1, need_tgt_grad, gemm_dtype)
             share = dk + dv
             return (d_z1 + sq + sk + sv if need_tgt_grad else None), share if d_memory is None else d_memory + share
         d_z2 = _ln_bwd(self.norm2, ln2, self._ffn_bwd_shared_into(live, d_z3))          # w.r.t. tgt1 + cross-attn output
+        if stop_after_cross:
+            self.multihead_attn.backward_shared_slab(t_cross, d_z2)
+            return None, None
         # d_z2 <- d_z2 + dq . Wq (in place: it is dead afterwards); d_memory (+)= [dk | dv] . [Wk; Wv]
         d_sum, d_memory = self.multihead_attn.backward_shared_into(t_cross, d_z2, d_z2, d_memory, same_source=False)
         d_z1 = _ln_bwd(self.norm1, ln1, d_sum)                             # w.r.t. tgt + self-attention output
@@ -384,15 +392,20 @@ class Transformer(nn.Module):
         return hs, (enc_tapes, dec_tapes, ln)
 
     @torch.no_grad()
-    def backward_shared(self, tape, d_hs, hooks=None):
+    def backward_shared(self, tape, d_hs, hooks=None, stop_after_top_cross=False):
         """``d_hs [K, Q, C]``: per-sample upstream gradients of ``hs_last``; fills every block's gradient slab.
         ``hooks``: ``{"decoder_done": f(), "encoder_layer_done": f(i)}`` called right after the named gradient slabs are
-        complete on the current stream (the rule kernels that only need those can start beside the rest of the backward)."""
+        complete on the current stream (the rule kernels that only need those can start beside the rest of the backward).
+        ``stop_after_top_cross``: stop once the TOP decoder layer's cross-attention gradient slab is complete (all attention GradCAM
+        reads); every other gradient slab keeps what it held, and no hook is called."""
         enc_tapes, dec_tapes, ln = tape
         hooks = hooks or {}
         gd = getattr(self, "backward_gemm_dtype", torch.float32)      # torch.bfloat16: opt-in bf16 MFMA for the dX GEMMs
         d_out = _ln_bwd(self.decoder.norm, ln, d_hs)
         d_memory = None
+        if stop_after_top_cross:
+            self.decoder.layers[-1].backward_shared(dec_tapes[-1], d_out, gemm_dtype=gd, stop_after_cross=True)
+            return
         for i in range(len(self.decoder.layers) - 1, -1, -1):
             d_out, d_memory = self.decoder.layers[i].backward_shared(dec_tapes[i], d_out, need_tgt_grad=i > 0, gemm_dtype=gd,
                                                                      d_memory=d_memory)
@@ -529,10 +542,11 @@ class DETRFromFeatures(nn.Module):
         return self.class_embed(hs), tape
 
     @torch.no_grad()
-    def backward_shared(self, state, d_logits, hooks=None):
-        """``d_logits [K, Q, classes+1]``: one upstream gradient of ``pred_logits`` per explained target.  ``hooks``: see
-        ``Transformer.backward_shared``."""
-        self.transformer.backward_shared(state, torch.matmul(d_logits, self.class_embed.weight), hooks)
+    def backward_shared(self, state, d_logits, hooks=None, stop_after_top_cross=False):
+        """``d_logits [K, Q, classes+1]``: one upstream gradient of ``pred_logits`` per explained target.  ``hooks`` and
+        ``stop_after_top_cross``: see ``Transformer.backward_shared``."""
+        self.transformer.backward_shared(state, torch.matmul(d_logits, self.class_embed.weight), hooks,
+                                         stop_after_top_cross=stop_after_top_cross)
 
 
 def detr_resnet50_head(num_classes=91, num_queries=100):

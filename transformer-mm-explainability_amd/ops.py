@@ -1748,3 +1748,84 @@ def detr_decoder_rows(self_pairs, cross_pairs, targets, shared_attn=False):
                                       0 if shared_attn else H * Q * Ni, _p(targets), _p(s_out), _p(dmin), _p(ws), need,
                                       _stream()), "mmx_detr_decoder_rows")
     return s_out, dmin
+
+
+# ------------------------------------------------------------------------------------------- DETR baselines, all kept queries at once
+DETR_BASELINES_MAX_TOKENS = 2048       # Ni of mmx_detr_cross_rows / mmx_detr_rollout_rows (Q <= 128, H <= 32)
+
+
+def _detr_slab(what, t, tail=None):
+    """An fp32 ``[H, rows, cols]`` capture slab of ONE image (``get_attn()`` of a DETR attention module)."""
+    _dev(t)
+    if t.dtype != torch.float32 or t.dim() != 3 or (tail is not None and tuple(t.shape[1:]) != tuple(tail)):
+        raise MMXError("%s: fp32 [H, rows, cols] capture slabs of one image only, got %s %s%s"
+                       % (what, t.dtype, tuple(t.shape), "" if tail is None else " (expected [*, %d, %d])" % tuple(tail)))
+    return t.contiguous()
+
+
+def _detr_targets(what, targets):
+    _dev(targets)
+    targets = targets.reshape(-1).to(torch.long).contiguous()
+    if targets.numel() < 1:
+        raise MMXError("%s: needs at least one target" % what)
+    return targets
+
+
+def _detr_cross_rows(what, cross_attn, cross_grad, targets):
+    P = _detr_slab(what, cross_attn)
+    targets = _detr_targets(what, targets)
+    K, (H, Q, Ni) = targets.numel(), P.shape
+    bstride, ws, need = 0, None, 0
+    if cross_grad is not None:
+        cross_grad = _detr_slab(what, cross_grad, (Q, Ni))
+        if cross_grad.shape[0] == K * H:
+            bstride = H * Q * Ni
+        elif cross_grad.shape[0] != H:
+            raise MMXError("%s: the gradient slab is [K * H, Q, Ni] or, shared by every target, [H, Q, Ni]; got %s for K = %d, H = %d"
+                           % (what, tuple(cross_grad.shape), K, H))
+        need = lib().mmx_detr_cross_rows_workspace_bytes(K, H, Q, Ni)
+        ws = _workspace(need, P.device, tag="detr_cross_rows")      # grow-only scratch: pinned_state keeps it alive for graphs
+    out = torch.empty(K, Ni, dtype=torch.float32, device=P.device)
+    check(lib().mmx_detr_cross_rows(_p(P), _p(cross_grad), bstride, _p(targets), _p(out), K, H, Q, Ni, _p(ws), need, _stream()),
+          "mmx_detr_cross_rows")
+    return out
+
+
+def detr_raw_rows(cross_attn, targets):
+    """Raw attention for all kept queries of one image: row ``targets[k]`` of the head mean of the last decoder layer's
+    cross-attention slab ``[H, Q, Ni]`` (fp32) -> ``[K, Ni]``.  ``targets``: device ``[K]`` integers, clamped to ``0 .. Q - 1`` by the
+    kernel.  One launch, nothing synchronises."""
+    return _detr_cross_rows("detr_raw_rows", cross_attn, None, targets)
+
+
+def detr_gradcam_rows(cross_attn, cross_grad, targets):
+    """Attention GradCAM for all kept queries of one image: ``max(0, mean_h(P[h, t_k] * w[k, h]))`` with ``w[k, h]`` the mean of
+    target k's gradient block ``[Q, Ni]`` of head h -> ``[K, Ni]``.  ``cross_grad``: ``[K * H, Q, Ni]``, or ``[H, Q, Ni]`` when one
+    gradient slab serves every target.  Two launches."""
+    return _detr_cross_rows("detr_gradcam_rows", cross_attn, cross_grad, targets)
+
+
+def detr_rollout_rows(enc_attn_list, dec_self_attn_list, cross_attn, targets):
+    """Rollout for all kept queries of one image: row ``targets[k]`` of ``R_qq^T . (mean_h cross_attn . R_ii)`` with ``R_ii`` / ``R_qq``
+    the normalised rollouts of the encoder / decoder self-attention slabs (``[H, Ni, Ni]`` / ``[H, Q, Q]`` fp32, first layer first),
+    carried as row vectors: no ``Ni x Ni`` product is formed -> ``[K, Ni]``.  See include/mmx_relevancy.h."""
+    what = "detr_rollout_rows"
+    P = _detr_slab(what, cross_attn)
+    H, Q, Ni = P.shape
+    enc = [_detr_slab(what, t, (Ni, Ni)) for t in enc_attn_list]
+    dec = [_detr_slab(what, t, (Q, Q)) for t in dec_self_attn_list]
+    if any(t.shape[0] != H for t in enc + dec):
+        raise MMXError("%s: every slab needs the %d heads of the cross-attention slab" % (what, H))
+    targets = _detr_targets(what, targets)
+    K = targets.numel()
+    need = lib().mmx_detr_rollout_rows_workspace_bytes(len(enc), len(dec), K, Q, Ni)
+    if need == 0:
+        raise MMXError("%s: needs 1..%d encoder and decoder slabs, Q <= 128 and Ni <= %d (got %d, %d, Q=%d, Ni=%d)"
+                       % (what, _lib.BASELINES_MAX_TABLE, DETR_BASELINES_MAX_TOKENS, len(enc), len(dec), Q, Ni))
+    out = torch.empty(K, Ni, dtype=torch.float32, device=P.device)
+    et, _k0 = _lib.ptr_table([t.data_ptr() for t in enc])
+    dt, _k1 = _lib.ptr_table([t.data_ptr() for t in dec])
+    ws = _workspace(need, P.device, tag="detr_rollout_rows")        # grow-only scratch: pinned_state keeps it alive for graphs
+    check(lib().mmx_detr_rollout_rows(et, len(enc), dt, len(dec), _p(P), _p(targets), _p(out), K, H, Q, Ni, _p(ws), need, _stream()),
+          "mmx_detr_rollout_rows")
+    return out
