@@ -7,8 +7,9 @@ forward, ONE all-gather of the per-sample step accuracies at the end.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29513 \\
         examples/visualbert_pert_eval.py --num-samples 10000 --text                   # one rank per GPU, RCCL
 
-``--explain-batch B`` (``raw_attn`` / ``attn_gradcam`` / ``rollout`` only; default 1, the per-item route): the relevancy rows of B items come from
-ONE padded batch (``SelfAttentionGenerator.generate_*_batch``, ``unpad_row``); every item is then perturbed as before.
+``--explain-batch B`` (``ours_no_lrp`` / ``raw_attn`` / ``attn_gradcam`` / ``rollout``; default 1, the per-item route; the LRP methods stay
+per item): the relevancy rows of B items come from ONE padded batch (``SelfAttentionGenerator.generate_ours_padded_batch`` /
+``generate_*_batch``, ``unpad_row``); every item is then perturbed as before.
 ``--perturb-batch B`` (default 32; 0: the per-item route, one ``perturbation_image`` / ``perturbation_text`` call per item): the rows of B items -- explained as above, batched or per item -- are padded into one
 ``[B, T + V]`` block (``pad_rows``) and all ``9 x B`` re-runs are ONE packed pass (``VisualBertPerturbation.perturbation_*_batch``).
 ``--reference-exact``: the reference loop stops only AFTER item ``num_samples + 1`` (its test is ``i > num_samples``) and
@@ -75,8 +76,9 @@ def main():
     ap.add_argument("--reference-exact", action="store_true")
     ap.add_argument("--resume-dir", default=None)
     ap.add_argument("--explain-batch", type=int, default=1,
-                    help="raw_attn / attn_gradcam / rollout only: explain this many items in ONE padded batch (one forward [+ one "
-                         "backward] and two or three launches), then perturb each item as before.  1 (default): one item per call")
+                    help="ours_no_lrp / raw_attn / attn_gradcam / rollout: explain this many items in ONE padded batch (one forward "
+                         "[+ one backward] and two or three launches), then perturb each item as before.  The LRP methods ignore it.  "
+                         "1 (default): one item per call")
     ap.add_argument("--perturb-batch", type=int, default=32,
                     help="perturb this many items in ONE packed pass (perturbation_image_batch / perturbation_text_batch) after "
                          "explaining them as above (default 32: profiles/visualbert_perturbation_batch_probe.txt).  0: one item per call")
@@ -99,7 +101,7 @@ def main():
                    "partial_lrp": gen.generate_partial_lrp, "raw_attn": gen.generate_raw_attn,
                    "attn_gradcam": gen.generate_attn_gradcam, "rollout": gen.generate_rollout}[args.method]
 
-    explain_batch = {"raw_attn": gen.generate_raw_attn_batch, "attn_gradcam": gen.generate_attn_gradcam_batch,
+    explain_batch = {"ours_no_lrp": gen.generate_ours_padded_batch, "raw_attn": gen.generate_raw_attn_batch, "attn_gradcam": gen.generate_attn_gradcam_batch,
                      "rollout": gen.generate_rollout_batch}.get(args.method) if args.explain_batch > 1 else None
     ahead = {}                                  # id -> (item on the device, its relevancy row), explained a batch at a time
     todo = []

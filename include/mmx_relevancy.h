@@ -471,6 +471,27 @@ size_t mmx_selfattn_rollout_row_workspace_bytes(int n_layers, int B, int T, int 
 int mmx_selfattn_rollout_row(const void* const* attn_table, int n_layers, int B, int H, int T, int V, const void* text_len_dev,
                              const void* vis_len_dev, void* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* mmx_selfattn_ours_row: generate_ours (VisualBERT/mmf/models/transformers/backends/ExplanationGenerator.py:68-107) for a PADDED
+ *   batch of ragged questions, in the layout and under the rules of the baselines above.  Per layer l (:86-93)
+ *   A_l = (sum_h max(0, grad_l[b, h] * attn_l[b, h])) / H -- the clamp per head, BEFORE the sum; a NaN stays a NaN -- and
+ *   R <- R + A_l R from layer 0 up, so R = (I + A_{L-1}) ... (I + A_0).  Only row c_b = t_b - 2 is returned (:94-97): x = e_{c_b};
+ *   x <- x + x . A_l for l = n_layers - 1 ... 0 on sample b's live set, exact zero outside it and at column c_b.
+ *   attn_table / grad_table: HOST tables of n_layers device slabs [B, H, N, N] fp32, entry l of both belonging to one layer.  Any cam
+ *   slab may stand in for attn: generate_transformer_att's rows (:42-56) are the same arithmetic on LRP cams.
+ *   The gradient of a padded batch is not zero at padded key columns and padded query rows hold garbage; neither reaches the output.
+ *   Two plain launches ordered by the stream: B x n_layers x ceil(N^2 / 2048) workgroups form A_l on the live rows (16-byte loads
+ *   inside a head's own block, heads in ascending order, chunks of padded query rows neither read nor written) into the workspace
+ *   in mmx_selfattn_rollout_row's layout; that entry's row kernel then carries x.  Fixed summation orders, no atomics: two calls give
+ *   the same bits, and sample b's output depends neither on B nor on its position in the batch.
+ *   Refused with MMX_EINVAL before any HIP call: what mmx_selfattn_rollout_row refuses, for both tables, and
+ *   B x n_layers x ceil(N^2 / 2048) > 2^31 - 1 (a one-dimensional grid).
+ *   workspace: mmx_selfattn_ours_row_workspace_bytes(n_layers, B, T, V) bytes (0 for arguments the entry refuses), 16-byte aligned,
+ *   caller-owned, stream-ordered. */
+size_t mmx_selfattn_ours_row_workspace_bytes(int n_layers, int B, int T, int V);
+int mmx_selfattn_ours_row(const void* const* attn_table, const void* const* grad_table, int n_layers, int B, int H, int T, int V,
+                          const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev,
+                          size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * On-device post-processing of relevancy maps (one workgroup per map, no host round trip):
  *  mmx_heatmap_bilinear_minmax: [B, g, g] patch maps -> bilinear upsample to [B, S, S] (torch interpolate semantics,

@@ -21,8 +21,8 @@ MMX_ATTN_IO_BF16 = 0x200        # backward: bf16 dO in, bf16 dq / dk / dv out (w
 MMX_ATTN_MMA_BF16 = 0x100       # OR-ed into slab_dtype of the attention *_ex entry points (bf16 matrix cores)
 MM_NORMALIZE, MM_SELF_IN_RULE10, MM_NAN_TO_ZERO = 1, 2, 4
 HEAD_MEAN_ZERO_CLS = 1          # mmx_head_mean_live: out[b, 0, 0] = 0
-BASELINES_MAX_TABLE = 32        # mmx_lxmert_rollout, mmx_selfattn_rollout_row: slabs per table
-SELFATTN_MAX_TOKENS = 256       # mmx_selfattn_row_live, mmx_selfattn_rollout_row: T + V
+BASELINES_MAX_TABLE = 32        # mmx_lxmert_rollout, mmx_selfattn_rollout_row, mmx_selfattn_ours_row: slabs per table
+SELFATTN_MAX_TOKENS = 256       # mmx_selfattn_row_live, mmx_selfattn_rollout_row, mmx_selfattn_ours_row: T + V
 CHAIN_CAUSAL = 1                # mmx_relevancy_self_chain_flags: probabilities of a causally masked tower (zeros above the diagonal)
 SCALE_Q_FIRST, SCALE_SCORES = 0, 1
 LRP_VALUES, LRP_SCORES = 1, 2        # phases of mmx_attn_relprop_phase
@@ -56,6 +56,8 @@ _PROTOTYPES = {
     "mmx_selfattn_row_live": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mmx_selfattn_rollout_row_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mmx_selfattn_rollout_row": (_i, [_vpp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmx_selfattn_ours_row_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mmx_selfattn_ours_row": (_i, [_vpp, _vpp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mmx_lrp_workspace_bytes": (_sz, []),
     "mmx_lrp_split_signs": (_i, [_vp, _vp, _i64, _i, _vp]),
     "mmx_lrp_safe_divide": (_i, [_vp, _vp, _vp, _i64, _vp]),

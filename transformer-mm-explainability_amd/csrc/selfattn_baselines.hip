@@ -21,6 +21,8 @@
 //                          UNCONDITIONALLY from a clamped address (lanes past the row's end repeat its last chunk, items past the
 //                          live rows repeat the last live row times zero), so eight loads and eight FMAs form one basic block and
 //                          the waits are counted: a ring of eight rows per lane stays in flight, across the layer boundary too.
+//   sa_ours_means_kernel   generate_ours (:68-107) on the same layout: workgroups as sa_rollout_means_kernel, but the matrix of a layer is
+//                          rule 5, (sum_h max(0, grad_h * attn_h)) / H with the clamp per head; sa_rollout_row_kernel then runs on it.
 // Plain launches ordered by the stream (no tickets, no spinning), fixed summation orders, no atomics: two runs give the same bits,
 // and sample b's result depends neither on B nor on b.
 #include "mmx_common.h"
@@ -220,6 +222,71 @@ __global__ __launch_bounds__(kSaThreads) void sa_rollout_means_kernel(const SaRo
     }
 }
 
+struct SaOursArgs {
+    const float* attn[kSaMaxTable];    // [B, H, N, N] probabilities (or any cam slab), one entry per layer
+    const float* grad[kSaMaxTable];    // [B, H, N, N] their gradients: NOT zero at padded key columns
+    int n_layers, B, H, T, V, strips;
+    const int *text_len, *vis_len;
+    float* ws;                         // [B][n_layers][N][NP] as SaRolloutArgs::ws: sa_rollout_row_kernel reads it
+};
+
+// rule 5 on the live rows: (sum_h clamp0(grad_h * attn_h)) / H, the clamp per head BEFORE the sum, heads in ascending order.  The
+// workgroup layout, the skipped chunks and the workspace are those of sa_rollout_means_kernel; padded key columns of a live row are
+// computed and written (the gradient there is arbitrary) and never read: the row kernel multiplies by x, which is zero there.
+__global__ __launch_bounds__(kSaThreads) void sa_ours_means_kernel(const SaOursArgs a) {
+    constexpr int kHeads = 4;                                        // heads per batch: 2 * kHeads 16-byte loads in flight
+    const int tid = threadIdx.x, N = a.T + a.V, hs = N * N, H = a.H;
+    int w = blockIdx.x;
+    const int s = w % a.strips; w /= a.strips;
+    const int l = w % a.n_layers, b = w / a.n_layers;
+    const int t = sa_text_len(a.text_len, b, a.T), v = sa_vis_len(a.vis_len, b, a.V);
+    const float* __restrict__ P = a.attn[l] + static_cast<int64_t>(b) * H * hs;
+    const float* __restrict__ G = a.grad[l] + static_cast<int64_t>(b) * H * hs;
+    const int NP = sa_row_stride(N);
+    float* dst = a.ws + (static_cast<int64_t>(b) * a.n_layers + l) * N * NP;
+    const float fH = static_cast<float>(H);
+#pragma unroll
+    for (int u = 0; u < kSaMeanChunks; ++u) {
+        const int p = s * kSaMeanStrip + (u * kSaThreads + tid) * 4;
+        if (p >= hs) continue;
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) any |= p + e < hs && sa_live((p + e) / N, t, a.T, v);
+        if (!any) continue;                                          // a chunk of padded query rows: neither read nor written
+        f32x4 m = {0.f, 0.f, 0.f, 0.f};
+        if (p + 3 < hs) {                                            // the 16-byte loads stay inside the head's own N x N block
+            int h = 0;
+            for (; h + kHeads <= H; h += kHeads) {
+                f32x4 x[kHeads], g[kHeads];
+#pragma unroll
+                for (int q = 0; q < kHeads; ++q) {
+                    x[q] = ldg4_u(P + static_cast<int64_t>(h + q) * hs + p);
+                    g[q] = ldg4_u(G + static_cast<int64_t>(h + q) * hs + p);
+                }
+#pragma unroll
+                for (int q = 0; q < kHeads; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) m[e] += relu_nan(g[q][e] * x[q][e]);
+            }
+            for (; h < H; ++h) {
+                const f32x4 x = ldg4_u(P + static_cast<int64_t>(h) * hs + p), g = ldg4_u(G + static_cast<int64_t>(h) * hs + p);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) m[e] += relu_nan(g[e] * x[e]);
+            }
+        } else {
+            for (int e = 0; p + e < hs; ++e)
+                for (int h = 0; h < H; ++h)
+                    m[e] += relu_nan(G[static_cast<int64_t>(h) * hs + p + e] * P[static_cast<int64_t>(h) * hs + p + e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (p + e < hs) {
+                const int row = (p + e) / N;
+                dst[row * NP + (p + e - row * N)] = m[e] / fH;       // rows of the workspace start on 16-byte boundaries
+            }
+    }
+}
+
 __global__ __launch_bounds__(kSaThreads) void sa_rollout_row_kernel(const SaRolloutArgs a) {
     __shared__ float x[kSaMaxN];
     __shared__ float part[kSaWaves][kSaMaxN];
@@ -382,6 +449,64 @@ extern "C" int mmx_selfattn_rollout_row(const void* const* attn_table, int n_lay
     hipStream_t s = static_cast<hipStream_t>(stream);
     sa_rollout_means_kernel<<<static_cast<unsigned>(B) * n_layers * a.strips, kSaThreads, 0, s>>>(a);
     MMX_LAUNCH_CHECK("sa_rollout_means_kernel");
+    sa_rollout_row_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(a);
+    MMX_LAUNCH_CHECK("sa_rollout_row_kernel");
+    return MMX_OK;
+}
+
+// the workspace is the rollout's: one head-mean matrix per (sample, layer)
+extern "C" size_t mmx_selfattn_ours_row_workspace_bytes(int n_layers, int B, int T, int V) {
+    return mmx_selfattn_rollout_row_workspace_bytes(n_layers, B, T, V);
+}
+
+extern "C" int mmx_selfattn_ours_row(const void* const* attn_table, const void* const* grad_table, int n_layers, int B, int H, int T,
+                                     int V, const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev,
+                                     size_t workspace_bytes, void* stream) {
+    MMX_CHECK_ARG(attn_table && grad_table && out_dev && workspace_dev, "mmx_selfattn_ours_row: null pointer");
+    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_selfattn_ours_row: B=%d H=%d (both >= 1)", B, H);
+    MMX_CHECK_ARG(sa_sizes_ok(T, V), "mmx_selfattn_ours_row: T=%d V=%d outside T >= 2, V >= 1, T + V <= %d", T, V, kSaMaxN);
+    MMX_CHECK_ARG(n_layers >= 1 && n_layers <= kSaMaxTable, "mmx_selfattn_ours_row: n_layers=%d outside 1..%d", n_layers, kSaMaxTable);
+    const int N = T + V;
+    const int strips = (N * N + kSaMeanStrip - 1) / kSaMeanStrip;
+    const int64_t groups = static_cast<int64_t>(B) * n_layers * strips;
+    MMX_CHECK_ARG(groups <= 2147483647LL, "mmx_selfattn_ours_row: B=%d x n_layers=%d x %d strips is beyond a one-dimensional grid", B,
+                  n_layers, strips);
+    const size_t need = mmx_selfattn_ours_row_workspace_bytes(n_layers, B, T, V);
+    MMX_CHECK_ARG(workspace_bytes >= need,
+                  "mmx_selfattn_ours_row: workspace of %zu bytes needed (mmx_selfattn_ours_row_workspace_bytes), got %zu", need,
+                  workspace_bytes);
+    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_selfattn_ours_row: the workspace must be 16-byte aligned");
+    SaOursArgs m;
+    memset(&m, 0, sizeof(m));
+    for (int l = 0; l < n_layers; ++l) {
+        MMX_CHECK_ARG(attn_table[l] && grad_table[l], "mmx_selfattn_ours_row: null pointer in a table (entry %d)", l);
+        m.attn[l] = static_cast<const float*>(attn_table[l]);
+        m.grad[l] = static_cast<const float*>(grad_table[l]);
+    }
+    const size_t f = sizeof(float), nb = static_cast<size_t>(B);
+    const void* outs[2] = {out_dev, workspace_dev};
+    const size_t out_sizes[2] = {f * nb * N, need};
+    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
+    for (int o = 0; o < 2; ++o) {
+        for (int l = 0; l < n_layers; ++l)
+            alias |= ranges_overlap(outs[o], out_sizes[o], attn_table[l], f * nb * H * N * N) ||
+                     ranges_overlap(outs[o], out_sizes[o], grad_table[l], f * nb * H * N * N);
+        alias |= ranges_overlap(outs[o], out_sizes[o], text_len_dev, sizeof(int) * nb);
+        alias |= ranges_overlap(outs[o], out_sizes[o], vis_len_dev, sizeof(int) * nb);
+    }
+    MMX_CHECK_ARG(!alias, "mmx_selfattn_ours_row: the output or the workspace may not alias an input or each other");
+    m.n_layers = n_layers; m.B = B; m.H = H; m.T = T; m.V = V; m.strips = strips;
+    m.text_len = static_cast<const int*>(text_len_dev);
+    m.vis_len = static_cast<const int*>(vis_len_dev);
+    m.ws = static_cast<float*>(workspace_dev);
+    SaRolloutArgs a;                   // the row kernel reads the sizes, the lengths, the workspace and the output: no slab
+    memset(&a, 0, sizeof(a));
+    a.n_layers = n_layers; a.B = B; a.H = H; a.T = T; a.V = V; a.strips = strips;
+    a.text_len = m.text_len; a.vis_len = m.vis_len; a.ws = m.ws;
+    a.out = static_cast<float*>(out_dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    sa_ours_means_kernel<<<static_cast<unsigned>(groups), kSaThreads, 0, s>>>(m);
+    MMX_LAUNCH_CHECK("sa_ours_means_kernel");
     sa_rollout_row_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(a);
     MMX_LAUNCH_CHECK("sa_rollout_row_kernel");
     return MMX_OK;

@@ -1206,6 +1206,36 @@ def selfattn_rollout_row(attn_layers, text_len=None, vis_len=None, n_text=None):
     return out
 
 
+def selfattn_ours_row(attn_layers, grad_layers, text_len=None, vis_len=None, n_text=None):
+    """``generate_ours`` (reference :68-107) of a padded single-stream batch: row ``c_b`` of ``(I + A_{L-1}) ... (I + A_0)`` with
+    ``A_l = mean_h clamp(grad_layers[l] * attn_layers[l], min=0)`` (the clamp per head, before the mean) on sample b's live set, exact
+    zeros elsewhere and at ``c_b`` -> ``[B, T + V]``.  Both tables: fp32 ``[B, H, N, N]`` slabs of one shape, entry ``l`` of both from
+    one layer; the gradient's padding may hold anything.  Any cam slab may stand in for ``attn``: the rows of
+    ``generate_transformer_att`` (reference :42-56) are the same arithmetic on the LRP cams.  Lengths and ``n_text`` as
+    ``selfattn_raw_row``.  Two launches, nothing synchronises."""
+    what = "selfattn_ours_row"
+    layers = [_slab(what, t) for t in attn_layers]
+    grads = [_slab(what, t) for t in grad_layers]
+    if not layers or len(layers) != len(grads):
+        raise MMXError("%s: needs 1..%d probability slabs and as many gradient slabs (got %d and %d)"
+                       % (what, _lib.BASELINES_MAX_TABLE, len(layers), len(grads)))
+    if any(t.shape != layers[0].shape for t in layers + grads):
+        raise MMXError("%s: every slab of both tables must have the shape %s" % (what, tuple(layers[0].shape)))
+    B, H, T, V = _selfattn_shape(what, layers[0], n_text)
+    text_len, vis_len = _lengths(what, text_len, B), _lengths(what, vis_len, B)
+    need = lib().mmx_selfattn_ours_row_workspace_bytes(len(layers), B, T, V)
+    if need == 0:
+        raise MMXError("%s: needs 1..%d slabs per table (got %d)" % (what, _lib.BASELINES_MAX_TABLE, len(layers)))
+    dev = layers[0].device
+    out = torch.empty(B, T + V, dtype=torch.float32, device=dev)
+    at, _k0 = _lib.ptr_table([t.data_ptr() for t in layers])
+    gt, _k1 = _lib.ptr_table([t.data_ptr() for t in grads])
+    ws = _workspace(need, dev, tag="selfattn_ours")                  # grow-only scratch: pinned_state keeps it alive for graphs
+    check(lib().mmx_selfattn_ours_row(at, gt, len(layers), B, H, T, V, _p(text_len), _p(vis_len), _p(out), _p(ws), need, _stream()),
+          "mmx_selfattn_ours_row")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- rollout
 def rollout_chain(layers, normalize):
     """``layers``: list of ``[B, N, N]`` (or ``[N, N]``) fp32 maps, already sliced to ``start_layer:``."""

@@ -60,8 +60,8 @@ def unpad_row(scores, b, n_text, padded_text):
 def pad_rows(rows, lens, padded_text):
     """The inverse of ``unpad_row``: B per-item rows (``rows[b]``: ``[1, lens[b] + V]``, what the per-item methods return) -> ``[B, T + V]``
     in the padded layout of the ``*_batch`` methods, ``T = padded_text``: item b's text scores at ``[b, :lens[b]]``, zeros up to ``T``,
-    its V region scores from ``T`` on.  ``lens``: host ints.  This is how the methods without a ragged batched form (``generate_ours``,
-    the LRP methods) feed ``VisualBertPerturbation.perturbation_*_batch``."""
+    its V region scores from ``T`` on.  ``lens``: host ints.  This is how rows explained one item at a time (the LRP methods, which have
+    no batched form, and every method on its per-item route) feed ``VisualBertPerturbation.perturbation_*_batch``."""
     if len(rows) == 0 or len(rows) != len(lens):
         raise ValueError("pad_rows: %d rows for %d lengths" % (len(rows), len(lens)))
     V = rows[0].shape[-1] - int(lens[0])
@@ -239,6 +239,16 @@ class SelfAttentionGenerator:
         sa = blocks[-1].attention.self
         return ops.selfattn_gradcam_row(sa.get_attn().detach(), sa.get_attn_gradients().detach(), text_len, vis_len, n_text=T)
 
+    def generate_ours_padded_batch(self, input, index=None):
+        """``generate_ours`` (reference :68-107) for B padded items whose questions may differ in length: one forward, one backward
+        with B one-hot seeds (``index`` as ``generate_attn_gradcam_batch``) and two launches over every layer's probability and
+        gradient slabs.  Rule 5 and the row update run on each sample's LIVE block (the gradient slabs of a padded batch are not zero
+        at padded keys) -> ``[B, T + V]`` in the padded layout (``unpad_row`` gives the per-item row).  ``generate_ours_batch`` (items
+        of equal length, the text padding trimmed away) is unchanged."""
+        blocks, text_len, vis_len, T = self._baseline_pass(input, backward=True, index=index)
+        return ops.selfattn_ours_row([blk.attention.self.get_attn().detach() for blk in blocks],
+                                     [blk.attention.self.get_attn_gradients().detach() for blk in blocks], text_len, vis_len, n_text=T)
+
     def generate_transformer_att(self, input, index=None, start_layer=0, save_visualization=False,
                                  save_visualization_per_token=False):
         """Reference :24-66: rule 5 on the LRP cams, then the un-normalised batched rollout from ``start_layer``."""
@@ -344,6 +354,50 @@ class GraphedBaselinesBatch:
             self._call = lambda: self.gen.generate_raw_attn_batch(self.static)
         else:
             self._call = lambda: self.gen.generate_attn_gradcam_batch(self.static, self.static_index)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._call()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with ops.graph_capture(self.graph):
+            self.output = self._call()
+        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+
+    def __call__(self, input=None, index=None):
+        if input is not None:
+            for k in self.keys:
+                if input[k].shape != self.static[k].shape:
+                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
+                                     % (k, tuple(input[k].shape), tuple(self.static[k].shape)))
+                self.static[k].copy_(input[k])
+        if index is not None:
+            if self.static_index is None:
+                raise ValueError("the graph was captured with index=None (arg-max answers)")
+            self.static_index.copy_(torch.as_tensor(index))
+        self.graph.replay()
+        return self.output
+
+
+class GraphedGenerateOursPadded:
+    """``SelfAttentionGenerator.generate_ours_padded_batch`` captured once into a hipGraph and replayed, under the contract of
+    ``GraphedBaselinesBatch``: the kernels take the per-sample lengths from the device, so ONE graph serves every ragged batch of the
+    captured shape (``GraphedGenerateOursBatch`` is tied to one text length).  New ``input_ids`` / ``input_mask`` / ``segment_ids`` /
+    ``image_feature_0`` (and ``image_dim``, when the example had one) and ``index`` are copied into the captured buffers.
+
+        run = GraphedGenerateOursPadded(model, example_sample_list)
+        scores = run(sample_list)                                              # [B, T + V], the graph's own output buffer
+    """
+
+    KEYS = GraphedBaselinesBatch.KEYS
+
+    def __init__(self, model, example, index=None, warmup=2):
+        self.keys = self.KEYS + (("image_dim",) if example.get("image_dim") is not None else ())
+        self.static = {k: example[k].clone() for k in self.keys}
+        self.static_index = None if index is None else torch.as_tensor(index, device=example["input_ids"].device).clone()
+        self.gen = SelfAttentionGenerator(model)
+        self._call = lambda: self.gen.generate_ours_padded_batch(self.static, self.static_index)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
