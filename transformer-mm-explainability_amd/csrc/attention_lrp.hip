@@ -14,7 +14,8 @@
 // Same tiling as the capture op's first-generation kernels (attention_kernels.hip): the query side owns 16 query rows and
 // walks the keys in 64-key tiles (cam_P, cam_Q); the key side owns 16 keys and walks the queries in 64-row tiles (cam_K,
 // cam_V; it re-reads cam_P from the slab the query side wrote, so it must be launched after it on the same stream).  All
-// products are exact-fp32 MFMAs (v_mfma_f32_16x16x4_f32); Z is recomputed from q and k, never stored.
+// products are exact-fp32 MFMAs (v_mfma_f32_16x16x4_f32); Z is recomputed from q and k, never stored.  safe_divide is the one of
+// mmx_common.h (a NaN in O or in a score stays NaN, as in the reference).
 //
 // Phases (mmx_attn_relprop_phase): BertSelfAttention.relprop (VisualBERT/.../BERT_ours.py:345-395) puts one more rule
 // between the two matmul relprops -- Add.relprop of [scores / sqrt(d), attention_mask], whose rescale needs sums over the
@@ -29,13 +30,6 @@ namespace {
 
 constexpr int kT16 = 16;   // rows a workgroup owns
 constexpr int kT64 = 64;   // rows of the streamed operand staged per step
-
-// DETR/modules/layers.py:11-14 in fp32
-__device__ __forceinline__ float safe_divide(float a, float b) {
-    float den = fmaxf(b, 1e-9f) + fminf(b, 1e-9f);
-    if (den == 0.f) den += 1e-9f;
-    return (b != 0.f) ? a / den : a / den * 0.f;
-}
 
 struct LrpArgs {
     const float *q, *k, *v, *o, *cam_o;

@@ -15,20 +15,14 @@
 //            ra *= safe_divide(|sa| / (|sa| + |sb|) * sum R, sa), likewise rb   lrp_add_scale_kernel
 //   Clone    out = X * sum_i safe_divide(R_i, X)                                lrp_clone_kernel
 // Sums are two-stage and deterministic (fixed grid, partials added in index order).  safe_divide is the reference's
-// (DETR/modules/layers.py:11-14): a / (b + 1e-9), 0 where b == 0 (a denominator that cancels to exactly 0 becomes 1e-9).
+// (DETR/modules/layers.py:11-14): a / (b + 1e-9), 0 where b == 0 (a denominator that cancels to exactly 0 becomes 1e-9) -- the
+// one device function of mmx_common.h, shared with the attention core.
 #include "mmx_common.h"
 
 namespace mmx {
 
 constexpr int kLrpThreads = 256;
 constexpr int kLrpMaxBlocks = 1024;
-
-__device__ __forceinline__ float lrp_safe_divide(float a, float b) {
-    // den = clamp(b, min=1e-9) + clamp(b, max=1e-9) = b + 1e-9 (one of the two clamps is the constant); den == 0 -> 1e-9
-    float den = (b < 1e-9f ? 1e-9f : b) + (b > 1e-9f ? 1e-9f : b);
-    den = den + (den == 0.f ? 1e-9f : 0.f);
-    return a / den * (b != 0.f ? 1.f : 0.f);
-}
 
 // block-wide sum of up to 3 values, result valid on thread 0 (fixed order: lanes by xor-shuffle tree, waves in index order)
 template <int NV>
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(kLrpThreads) void lrp_safe_divide_kernel(const floa
                                                                       float* __restrict__ out, int64_t n) {
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * kLrpThreads + threadIdx.x; e < n;
          e += static_cast<int64_t>(gridDim.x) * kLrpThreads)
-        out[e] = lrp_safe_divide(a[e], b[e]);
+        out[e] = safe_divide(a[e], b[e]);
 }
 
 // out[r, j] = XX[r, j] * Y[r, j] + XX[r, n + j] * Y[r, n + j]; partial[0][block] = sum out, partial[1][block] = sum R (if asked)
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(kLrpThreads) void lrp_scale_ratio_kernel(float* __r
     __shared__ float lds[2 * kLrpThreads / 64], bc[2];
     float v[2];
     partials_sum<2>(partial, nparts, nparts, 1, v, lds, bc);      // v[0] = sum out, v[1] = sum R
-    const float k = lrp_safe_divide(v[1], v[0]);
+    const float k = safe_divide(v[1], v[0]);
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * kLrpThreads + threadIdx.x; e < total;
          e += static_cast<int64_t>(gridDim.x) * kLrpThreads)
         out[e] *= k;
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(kLrpThreads) void lrp_add_split_kernel(const float*
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * kLrpThreads + threadIdx.x; e < per;
          e += static_cast<int64_t>(gridDim.x) * kLrpThreads) {
         const float r = R[off + e], av = a[off + e], bv = b[off + e];
-        const float s = lrp_safe_divide(r, av + bv);
+        const float s = safe_divide(r, av + bv);
         const float x = av * s, y = bv * s;
         ra[off + e] = x;
         rb[off + e] = y;
@@ -163,8 +157,8 @@ __global__ __launch_bounds__(kLrpThreads) void lrp_add_scale_kernel(float* __res
     float v[3];
     partials_sum<3>(partial + static_cast<int64_t>(blockIdx.y) * nparts * 3, nparts, 1, 3, v, lds, bc);   // sa, sb, total
     const float den = fabsf(v[0]) + fabsf(v[1]);
-    const float fa = lrp_safe_divide(fabsf(v[0]), den) * v[2], fb = lrp_safe_divide(fabsf(v[1]), den) * v[2];
-    const float xa = lrp_safe_divide(fa, v[0]), xb = lrp_safe_divide(fb, v[1]);
+    const float fa = safe_divide(fabsf(v[0]), den) * v[2], fb = safe_divide(fabsf(v[1]), den) * v[2];
+    const float xa = safe_divide(fa, v[0]), xb = safe_divide(fb, v[1]);
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * kLrpThreads + threadIdx.x; e < per;
          e += static_cast<int64_t>(gridDim.x) * kLrpThreads) {
         ra[off + e] *= xa;
@@ -203,8 +197,8 @@ __global__ __launch_bounds__(kLrpThreads) void lrp_mha_apply_kernel(const MhaRes
     partials_sum<5>(a.partial, nparts, nparts, 1, v, lds, bc);
     if (!(v[1] == 0.f && v[0] != 0.f)) return;                      // rescale = all_zero(v_post) & ~all_zero(v_pre)
     const float den = fabsf(v[2]) + fabsf(v[3]);
-    const float kf = lrp_safe_divide(fabsf(v[2]), den) * v[4], qf = lrp_safe_divide(fabsf(v[3]), den) * v[4];
-    const float xk = lrp_safe_divide(kf, v[2]), xq = lrp_safe_divide(qf, v[3]);
+    const float kf = safe_divide(fabsf(v[2]), den) * v[4], qf = safe_divide(fabsf(v[3]), den) * v[4];
+    const float xk = safe_divide(kf, v[2]), xq = safe_divide(qf, v[3]);
     const int64_t t0 = static_cast<int64_t>(blockIdx.x) * kLrpThreads + threadIdx.x, st = static_cast<int64_t>(gridDim.x) * kLrpThreads;
     for (int64_t e = t0; e < a.n_k; e += st) a.cam_k[e] *= xk;
     for (int64_t e = t0; e < a.n_q; e += st) a.cam_q[e] *= xq;
@@ -218,10 +212,10 @@ __global__ __launch_bounds__(kLrpThreads) void lrp_clone_kernel(const CloneArgs 
     for (int64_t e = static_cast<int64_t>(blockIdx.x) * kLrpThreads + threadIdx.x; e < n;
          e += static_cast<int64_t>(gridDim.x) * kLrpThreads) {
         const float x = X[e];
-        float c = lrp_safe_divide(a.R[0][e], x);
+        float c = safe_divide(a.R[0][e], x);
 #pragma unroll
         for (int i = 1; i < kLrpMaxClones; ++i)
-            if (i < a.nr) c += lrp_safe_divide(a.R[i][e], x);
+            if (i < a.nr) c += safe_divide(a.R[i][e], x);
         out[e] = x * c;
     }
 }

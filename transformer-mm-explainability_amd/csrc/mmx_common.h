@@ -148,6 +148,16 @@ __device__ __forceinline__ void slab_store(typename slab_elem<DT>::type* p, floa
 // clamp(x, min=0) with torch semantics: NaN propagates (fmaxf would drop it)
 __device__ __forceinline__ float relu_nan(float x) { return (x < 0.0f) ? 0.0f : x; }
 
+// safe_divide of the reference's LRP layer library (DETR/modules/layers.py:11-14) in fp32: a / (b + 1e-9), 0 where b == 0.  ONE device
+// function for the attention core (attention_lrp.hip) and the layer rules (lrp_kernels.hip).  den = clamp(b, min=1e-9) +
+// clamp(b, max=1e-9) = b + 1e-9 (one of the two clamps is the constant); den == 0 -> 1e-9.  Comparisons, like torch.clamp: a NaN
+// denominator stays NaN (fmaxf / fminf would drop it and give a / 2e-9).
+__device__ __forceinline__ float safe_divide(float a, float b) {
+    float den = (b < 1e-9f ? 1e-9f : b) + (b > 1e-9f ? 1e-9f : b);
+    den = den + (den == 0.f ? 1e-9f : 0.f);
+    return a / den * (b != 0.f ? 1.f : 0.f);
+}
+
 // QuickGELU, x * sigmoid(1.702 x) (CLIP/clip/model.py:162-164): ONE device function for every kernel that evaluates it (the fused
 // elementwise passes, the c_fc epilogue of the row-list GEMM), so that they agree bit for bit.
 __device__ __forceinline__ float sigmoid_f(float z) { return 1.f / (1.f + expf(-z)); }
