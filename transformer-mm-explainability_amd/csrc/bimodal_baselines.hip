@@ -33,12 +33,6 @@ constexpr int kRcWaves = kRcThreads / 64;
 // the clamped length of sample b: NEVER used unclamped
 __device__ __forceinline__ int live_len(const int* len, int b, int N) { return len ? min(max(len[b], 1), N) : N; }
 
-__device__ __forceinline__ float wave_sum_bl(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ __launch_bounds__(kHmThreads) void head_mean_live_kernel(const float* __restrict__ attn, const float* __restrict__ grad,
                                                                     float* __restrict__ out, int H, int Nq, int Nk,
                                                                     const int* q_len, const int* k_len, unsigned flags) {
@@ -78,7 +72,7 @@ __global__ __launch_bounds__(kHmThreads) void head_mean_live_kernel(const float*
                     j += 64;
                     while (j >= k) { j -= k; ++i; }
                 }
-                s = wave_sum_bl(s);
+                s = wave_sum(s);
                 if (lane == 0) w_lds[hh] = s / cnt;
             }
             __syncthreads();
@@ -275,16 +269,9 @@ __global__ __launch_bounds__(kRcThreads) void rollout_chain_kernel(const Rollout
 
 using namespace mmx;
 
-static inline size_t bl_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 static inline int bl_block_floats(int T, int I) {
     const int m = T > I ? T : I;
     return ((m * m + 3) / 4) * 4;
-}
-// [a, a + na) and [b, b + nb) share a byte (a null pointer overlaps nothing)
-static inline bool bl_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 extern "C" int mmx_head_mean_live(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int Nq, int Nk,
@@ -295,9 +282,9 @@ extern "C" int mmx_head_mean_live(const void* attn_dev, const void* grad_dev, vo
     MMX_CHECK_ARG((flags & ~static_cast<unsigned>(MMX_HEAD_MEAN_ZERO_CLS)) == 0, "mmx_head_mean_live: unknown flags 0x%x", flags);
     const size_t out_bytes = sizeof(float) * static_cast<size_t>(B) * Nq * Nk, in_bytes = out_bytes * static_cast<size_t>(H);
     const size_t len_bytes = sizeof(int) * static_cast<size_t>(B);
-    MMX_CHECK_ARG(!bl_overlap(out_dev, out_bytes, attn_dev, in_bytes) && !bl_overlap(out_dev, out_bytes, grad_dev, in_bytes) &&
-                      !bl_overlap(out_dev, out_bytes, q_len_dev, len_bytes) && !bl_overlap(out_dev, out_bytes, k_len_dev, len_bytes),
-                  "mmx_head_mean_live: the output may not alias an input");
+    const Span out = {out_dev, out_bytes};
+    const Span ins[4] = {{attn_dev, in_bytes}, {grad_dev, in_bytes}, {q_len_dev, len_bytes}, {k_len_dev, len_bytes}};
+    MMX_CHECK_ARG(!spans_alias(&out, 1, ins, 4), "mmx_head_mean_live: the output may not alias an input");
     head_mean_live_kernel<<<static_cast<unsigned>(B), kHmThreads, 0, static_cast<hipStream_t>(stream)>>>(
         static_cast<const float*>(attn_dev), static_cast<const float*>(grad_dev), static_cast<float*>(out_dev), H, Nq, Nk,
         static_cast<const int*>(q_len_dev), static_cast<const int*>(k_len_dev), flags);
@@ -308,7 +295,7 @@ extern "C" int mmx_head_mean_live(const void* attn_dev, const void* grad_dev, vo
 extern "C" size_t mmx_lxmert_rollout_workspace_bytes(int n_text, int n_img, int B, int T, int I) {
     if (n_text < 2 || n_img < 1 || n_text > kBlMaxTable || n_img > kBlMaxTable || B < 1 || T < 1 || I < 1 || T > kBlMax || I > kBlMax)
         return 0;
-    return bl_align256(sizeof(float) * static_cast<size_t>(B) * (n_text + n_img + 1) * bl_block_floats(T, I));
+    return align256(sizeof(float) * static_cast<size_t>(B) * (n_text + n_img + 1) * bl_block_floats(T, I));
 }
 
 extern "C" int mmx_lxmert_rollout(const void* const* text_attn, int n_text, const void* const* img_attn, int n_img,
@@ -321,32 +308,24 @@ extern "C" int mmx_lxmert_rollout(const void* const* text_attn, int n_text, cons
                   n_text, n_img);
     MMX_CHECK_ARG(n_text <= kBlMaxTable && n_img <= kBlMaxTable, "mmx_lxmert_rollout: at most %d slabs per table (n_text=%d n_img=%d)",
                   kBlMaxTable, n_text, n_img);
+    const char* me = "mmx_lxmert_rollout";
+    const int nblk = n_text + n_img + 1;
+    if (int rc = check_grid(me, static_cast<int64_t>(B) * nblk, "B=%d x %d blocks", B, nblk)) return rc;
     const size_t need = mmx_lxmert_rollout_workspace_bytes(n_text, n_img, B, T, I);
-    MMX_CHECK_ARG(workspace_bytes >= need, "mmx_lxmert_rollout: workspace of %zu bytes needed (mmx_lxmert_rollout_workspace_bytes), got %zu",
-                  need, workspace_bytes);
-    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_lxmert_rollout: the workspace must be 16-byte aligned");
+    if (int rc = check_workspace(me, "mmx_lxmert_rollout_workspace_bytes", workspace_dev, workspace_bytes, need)) return rc;
     RolloutArgs a;
     memset(&a, 0, sizeof(a));
-    for (int l = 0; l < n_text; ++l) {
-        MMX_CHECK_ARG(text_attn[l], "mmx_lxmert_rollout: null pointer in the text table (entry %d)", l);
-        a.text[l] = static_cast<const float*>(text_attn[l]);
-    }
-    for (int l = 0; l < n_img; ++l) {
-        MMX_CHECK_ARG(img_attn[l], "mmx_lxmert_rollout: null pointer in the image table (entry %d)", l);
-        a.img[l] = static_cast<const float*>(img_attn[l]);
-    }
+    if (int rc = copy_table(me, "the text table", text_attn, n_text, a.text)) return rc;
+    if (int rc = copy_table(me, "the image table", img_attn, n_img, a.img)) return rc;
     const size_t f = sizeof(float), nb = static_cast<size_t>(B);
-    const void* outs[4] = {R_tt_dev, R_ti_dev, R_ii_dev, workspace_dev};
-    const size_t out_bytes[4] = {f * nb * T * T, f * nb * T * I, f * nb * I * I, need};
-    bool alias = false;
-    for (int o = 0; o < 4; ++o) {
-        for (int l = 0; l < n_text; ++l) alias |= bl_overlap(outs[o], out_bytes[o], text_attn[l], f * nb * H * T * T);
-        for (int l = 0; l < n_img; ++l) alias |= bl_overlap(outs[o], out_bytes[o], img_attn[l], f * nb * H * I * I);
-        alias |= bl_overlap(outs[o], out_bytes[o], cross_attn_dev, f * nb * H * T * I);
-        alias |= bl_overlap(outs[o], out_bytes[o], text_len_dev, sizeof(int) * nb);
-        for (int p = o + 1; p < 4; ++p) alias |= bl_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p]);
-    }
-    MMX_CHECK_ARG(!alias, "mmx_lxmert_rollout: an output or the workspace may not alias an input or another output");
+    const Span outs[4] = {{R_tt_dev, f * nb * T * T}, {R_ti_dev, f * nb * T * I}, {R_ii_dev, f * nb * I * I}, {workspace_dev, need}};
+    Span ins[2 * kBlMaxTable + 2];
+    int n_in = 0;
+    for (int l = 0; l < n_text; ++l) ins[n_in++] = {text_attn[l], f * nb * H * T * T};
+    for (int l = 0; l < n_img; ++l) ins[n_in++] = {img_attn[l], f * nb * H * I * I};
+    ins[n_in++] = {cross_attn_dev, f * nb * H * T * I};
+    ins[n_in++] = {text_len_dev, sizeof(int) * nb};
+    MMX_CHECK_ARG(!spans_alias(outs, 4, ins, n_in), "mmx_lxmert_rollout: an output or the workspace may not alias an input or another output");
     a.cross = static_cast<const float*>(cross_attn_dev);
     a.n_text = n_text; a.n_img = n_img; a.B = B; a.H = H; a.T = T; a.I = I;
     a.text_len = static_cast<const int*>(text_len_dev);
@@ -354,7 +333,6 @@ extern "C" int mmx_lxmert_rollout(const void* const* text_attn, int n_text, cons
     a.bs = bl_block_floats(T, I);
     a.R_tt = static_cast<float*>(R_tt_dev); a.R_ti = static_cast<float*>(R_ti_dev); a.R_ii = static_cast<float*>(R_ii_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nblk = n_text + n_img + 1;
     rollout_means_kernel<<<static_cast<unsigned>(B) * nblk, kHmThreads, 0, s>>>(a);
     MMX_LAUNCH_CHECK("rollout_means_kernel");
     const int m = T > I ? T : I, D16 = ((m + 15) / 16) * 16;

@@ -379,7 +379,6 @@ __global__ void bm_v2_reset_kernel(float* diag, unsigned* counters, int B) {
 
 using namespace mmx;
 
-static inline size_t bm_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 static inline int bm_nblk(int n_lang, int n_vis, int n_x) { return n_lang + n_vis + 4 * n_x - 2; }
 static inline int bm_block_floats(int T, int I) {
     const int m = T > I ? T : I;
@@ -389,8 +388,8 @@ static int g_bm_split = 0;   // MMX_BM_SPLIT=1 (read per call, profiling knob): 
 
 extern "C" size_t mmx_lxmert_schedule_workspace_bytes(int n_lang, int n_vis, int n_x, int B, int T, int I) {
     if (n_lang < 0 || n_vis < 0 || n_x < 1 || B < 1 || T < 1 || I < 1) return 0;
-    return bm_align256(sizeof(unsigned) * static_cast<size_t>(B)) +
-           bm_align256(sizeof(float) * static_cast<size_t>(B) * bm_nblk(n_lang, n_vis, n_x) * bm_block_floats(T, I));
+    return align256(sizeof(unsigned) * static_cast<size_t>(B)) +
+           align256(sizeof(float) * static_cast<size_t>(B) * bm_nblk(n_lang, n_vis, n_x) * bm_block_floats(T, I));
 }
 
 extern "C" int mmx_lxmert_schedule(const void* const* lang_attn, const void* const* lang_grad, int n_lang,
@@ -444,7 +443,7 @@ extern "C" int mmx_lxmert_schedule(const void* const* lang_attn, const void* con
     v.nblk = bm_nblk(n_lang, n_vis, n_x);
     v.bs = bm_block_floats(T, I);
     v.counters = static_cast<unsigned*>(workspace_dev);
-    v.abar = reinterpret_cast<float*>(static_cast<char*>(workspace_dev) + bm_align256(sizeof(unsigned) * static_cast<size_t>(B)));
+    v.abar = reinterpret_cast<float*>(static_cast<char*>(workspace_dev) + align256(sizeof(unsigned) * static_cast<size_t>(B)));
     const int m = T > I ? T : I;
     v.D16 = ((m + 15) / 16) * 16;
     {

@@ -24,12 +24,6 @@ bool clip_head_option(const char* key, int value) {
     return false;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ __launch_bounds__(64) void clip_head_kernel(const float* img, const float* txt, const float* logit_scale, float* d_img,
                                                        float* d_txt, float* logit_diag, int B, int D, int Bi, int img_group) {
     const int b = blockIdx.x;

@@ -49,15 +49,9 @@ constexpr int kDbStepVecs = 8;                  // vectors carried through a str
 constexpr int kDcStripChunks = 8;               // 16-byte chunks per thread of a gradient strip
 constexpr int kDcStrip = kDbThreads * kDcStripChunks * 4;     // floats per gradient strip
 
-__host__ __device__ __forceinline__ int db_row_stride(int Ni) { return (Ni + 3) & ~3; }
 __device__ __forceinline__ int db_target(const int64_t* targets, int k, int Q) {
     const int64_t t = targets[k];
     return t < 0 ? 0 : (t > Q - 1 ? Q - 1 : static_cast<int>(t));
-}
-__device__ __forceinline__ float wave_sum_db(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 __device__ __forceinline__ f32x4 fma4(float w, f32x4 a, f32x4 acc) {
     f32x4 r;
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(kDbThreads) void dc_w_part_kernel(const float* __re
         }
         acc += v;
     }
-    float t = wave_sum_db((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    float t = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
     if (lane == 0) part[wave] = t;
     __syncthreads();
     if (tid == 0) wpart[static_cast<int64_t>(kh) * strips + s] = (part[0] + part[1]) + (part[2] + part[3]);
@@ -190,7 +184,7 @@ __global__ __launch_bounds__(kDbThreads) void db_enc_means_kernel(const DbTable 
     if (wave < rows) {                                               // r_l of row i0 + wave: lane partials, then the xor tree
         float t = 0.f;
         for (int j = lane; j < Ni; j += 64) t += m[wave * Ni + j];
-        t = wave_sum_db(t);
+        t = wave_sum(t);
         if (lane == 0) a.renc[static_cast<int64_t>(l) * Ni + i0 + wave] = 1.0f + t;
     }
     float* dst = a.abar + (static_cast<int64_t>(l) * Ni + i0) * NP;
@@ -222,8 +216,8 @@ __global__ __launch_bounds__(kDbThreads) void db_dec_chain_kernel(const DbRollou
         const float y0 = y[lane], y1 = y[lane + 64];
         for (int i = wave; i < Q; i += kDbWaves) {
             const float b0 = has0 ? B[i * Q + lane] : 0.f, b1 = has1 ? B[i * Q + lane + 64] : 0.f;
-            const float d = wave_sum_db(__builtin_fmaf(b1, y1, b0 * y0));
-            const float rs = wave_sum_db(b0 + b1);
+            const float d = wave_sum(__builtin_fmaf(b1, y1, b0 * y0));
+            const float rs = wave_sum(b0 + b1);
             if (lane == 0) yn[i] = (d + y[i]) / (1.0f + rs);
         }
         __syncthreads();
@@ -305,7 +299,6 @@ __global__ __launch_bounds__(kDbThreads) void db_enc_reduce_kernel(const DbRollo
 
 using namespace mmx;
 
-static inline size_t db_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 static inline bool db_sizes_ok(int K, int H, int Q, int Ni) {
     return K >= 1 && K <= kDbMaxK && H >= 1 && H <= kDbMaxH && Q >= 1 && Q <= kDbMaxQ && Ni >= 1 && Ni <= kDbMaxNi;
 }
@@ -314,7 +307,7 @@ static inline int dc_strips(int Q, int Ni) { return (Q * Ni + kDcStrip - 1) / kD
 // workspace of the GradCAM form: the strips' sums [K, H, strips]
 extern "C" size_t mmx_detr_cross_rows_workspace_bytes(int K, int H, int Q, int Ni) {
     if (!db_sizes_ok(K, H, Q, Ni)) return 0;
-    return db_align256(sizeof(float) * static_cast<size_t>(K) * H * dc_strips(Q, Ni));
+    return align256(sizeof(float) * static_cast<size_t>(K) * H * dc_strips(Q, Ni));
 }
 
 extern "C" int mmx_detr_cross_rows(const void* cross_attn_dev, const void* cross_grad_dev, int64_t grad_bstride, const void* targets_dev,
@@ -330,19 +323,13 @@ extern "C" int mmx_detr_cross_rows(const void* cross_attn_dev, const void* cross
                       "mmx_detr_cross_rows: grad_bstride=%lld is neither 0 (one shared slab) nor H Q Ni = %lld",
                       static_cast<long long>(grad_bstride), static_cast<long long>(H) * Q * Ni);
         MMX_CHECK_ARG(workspace_dev, "mmx_detr_cross_rows: null pointer (the GradCAM form needs a workspace)");
-        MMX_CHECK_ARG(workspace_bytes >= need,
-                      "mmx_detr_cross_rows: workspace of %zu bytes needed (mmx_detr_cross_rows_workspace_bytes), got %zu", need,
-                      workspace_bytes);
-        MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_detr_cross_rows: the workspace must be 16-byte aligned");
+        if (int rc = check_workspace("mmx_detr_cross_rows", "mmx_detr_cross_rows_workspace_bytes", workspace_dev, workspace_bytes, need))
+            return rc;
     }
     const size_t grad_bytes = slab * (grad_bstride ? static_cast<size_t>(K) : 1);
-    const void* outs[2] = {out_dev, cross_grad_dev ? workspace_dev : nullptr};
-    const size_t out_sizes[2] = {f * static_cast<size_t>(K) * Ni, need};
-    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
-    for (int o = 0; o < 2; ++o)
-        alias |= ranges_overlap(outs[o], out_sizes[o], cross_attn_dev, slab) || ranges_overlap(outs[o], out_sizes[o], cross_grad_dev, grad_bytes) ||
-                 ranges_overlap(outs[o], out_sizes[o], targets_dev, sizeof(int64_t) * static_cast<size_t>(K));
-    MMX_CHECK_ARG(!alias, "mmx_detr_cross_rows: the output or the workspace may not alias an input or each other");
+    const Span outs[2] = {{out_dev, f * static_cast<size_t>(K) * Ni}, {cross_grad_dev ? workspace_dev : nullptr, need}};
+    const Span ins[3] = {{cross_attn_dev, slab}, {cross_grad_dev, grad_bytes}, {targets_dev, sizeof(int64_t) * static_cast<size_t>(K)}};
+    MMX_CHECK_ARG(!spans_alias(outs, 2, ins, 3), "mmx_detr_cross_rows: the output or the workspace may not alias an input or each other");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float* P = static_cast<const float*>(cross_attn_dev);
     const int64_t* tg = static_cast<const int64_t*>(targets_dev);
@@ -368,16 +355,16 @@ struct DbLayout {
     size_t abar, renc, bbar, pbar, u, x, part, total;
 };
 DbLayout db_layout(int n_enc, int n_dec, int K, int Q, int Ni) {
-    const size_t f = sizeof(float), NP = db_row_stride(Ni), strips = (Ni + kDbStepRows - 1) / kDbStepRows, nk = static_cast<size_t>(K);
+    const size_t f = sizeof(float), NP = row_stride4(Ni), strips = (Ni + kDbStepRows - 1) / kDbStepRows, nk = static_cast<size_t>(K);
     DbLayout L;
     size_t at = 0;
-    L.abar = at; at += db_align256(f * n_enc * Ni * NP);
-    L.renc = at; at += db_align256(f * n_enc * Ni);
-    L.bbar = at; at += db_align256(f * n_dec * Q * Q);
-    L.pbar = at; at += db_align256(f * Q * Ni);
-    L.u = at;    at += db_align256(f * nk * Q);
-    L.x = at;    at += db_align256(f * nk * Ni);
-    L.part = at; at += db_align256(f * strips * nk * NP);
+    L.abar = at; at += align256(f * n_enc * Ni * NP);
+    L.renc = at; at += align256(f * n_enc * Ni);
+    L.bbar = at; at += align256(f * n_dec * Q * Q);
+    L.pbar = at; at += align256(f * Q * Ni);
+    L.u = at;    at += align256(f * nk * Q);
+    L.x = at;    at += align256(f * nk * Ni);
+    L.part = at; at += align256(f * strips * nk * NP);
     L.total = at;
     return L;
 }
@@ -400,39 +387,29 @@ extern "C" int mmx_detr_rollout_rows(const void* const* enc_table, int n_enc, co
                   "1 <= Ni <= %d", K, H, Q, Ni, kDbMaxK, kDbMaxH, kDbMaxQ, kDbMaxNi);
     MMX_CHECK_ARG(db_tables_ok(n_enc, n_dec), "mmx_detr_rollout_rows: tables of %d and %d entries outside 1..%d", n_enc, n_dec, kDbMaxTable);
     const DbLayout L = db_layout(n_enc, n_dec, K, Q, Ni);
-    MMX_CHECK_ARG(workspace_bytes >= L.total,
-                  "mmx_detr_rollout_rows: workspace of %zu bytes needed (mmx_detr_rollout_rows_workspace_bytes), got %zu", L.total,
-                  workspace_bytes);
-    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_detr_rollout_rows: the workspace must be 16-byte aligned");
+    const char* me = "mmx_detr_rollout_rows";
+    if (int rc = check_workspace(me, "mmx_detr_rollout_rows_workspace_bytes", workspace_dev, workspace_bytes, L.total)) return rc;
     DbTable enc, dec, cross;
     memset(&enc, 0, sizeof(enc));
     memset(&dec, 0, sizeof(dec));
     memset(&cross, 0, sizeof(cross));
-    for (int l = 0; l < n_enc; ++l) {
-        MMX_CHECK_ARG(enc_table[l], "mmx_detr_rollout_rows: null pointer in the encoder table (entry %d)", l);
-        enc.p[l] = static_cast<const float*>(enc_table[l]);
-    }
-    for (int l = 0; l < n_dec; ++l) {
-        MMX_CHECK_ARG(dec_self_table[l], "mmx_detr_rollout_rows: null pointer in the decoder table (entry %d)", l);
-        dec.p[l] = static_cast<const float*>(dec_self_table[l]);
-    }
+    if (int rc = copy_table(me, "the encoder table", enc_table, n_enc, enc.p)) return rc;
+    if (int rc = copy_table(me, "the decoder table", dec_self_table, n_dec, dec.p)) return rc;
     cross.p[0] = static_cast<const float*>(cross_attn_dev);
     const size_t f = sizeof(float), nk = static_cast<size_t>(K);
-    const void* outs[2] = {out_dev, workspace_dev};
-    const size_t out_sizes[2] = {f * nk * Ni, L.total};
-    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
-    for (int o = 0; o < 2; ++o) {
-        for (int l = 0; l < n_enc; ++l) alias |= ranges_overlap(outs[o], out_sizes[o], enc_table[l], f * H * Ni * Ni);
-        for (int l = 0; l < n_dec; ++l) alias |= ranges_overlap(outs[o], out_sizes[o], dec_self_table[l], f * H * Q * Q);
-        alias |= ranges_overlap(outs[o], out_sizes[o], cross_attn_dev, f * H * Q * Ni);
-        alias |= ranges_overlap(outs[o], out_sizes[o], targets_dev, sizeof(int64_t) * nk);
-    }
-    MMX_CHECK_ARG(!alias, "mmx_detr_rollout_rows: the output or the workspace may not alias an input or each other");
+    const Span outs[2] = {{out_dev, f * nk * Ni}, {workspace_dev, L.total}};
+    Span ins[2 * kDbMaxTable + 2];
+    int n_in = 0;
+    for (int l = 0; l < n_enc; ++l) ins[n_in++] = {enc_table[l], f * H * Ni * Ni};
+    for (int l = 0; l < n_dec; ++l) ins[n_in++] = {dec_self_table[l], f * H * Q * Q};
+    ins[n_in++] = {cross_attn_dev, f * H * Q * Ni};
+    ins[n_in++] = {targets_dev, sizeof(int64_t) * nk};
+    MMX_CHECK_ARG(!spans_alias(outs, 2, ins, n_in), "mmx_detr_rollout_rows: the output or the workspace may not alias an input or each other");
     char* ws = static_cast<char*>(workspace_dev);
     DbRolloutArgs a;
     memset(&a, 0, sizeof(a));
     a.n_enc = n_enc; a.n_dec = n_dec; a.K = K; a.H = H; a.Q = Q; a.Ni = Ni;
-    a.NP = db_row_stride(Ni);
+    a.NP = row_stride4(Ni);
     a.strips = (Ni + kDbStepRows - 1) / kDbStepRows;
     a.targets = static_cast<const int64_t*>(targets_dev);
     a.abar = reinterpret_cast<float*>(ws + L.abar);

@@ -264,8 +264,6 @@ __global__ __launch_bounds__(256) void detr_rows_finish_kernel(const DetrRowsArg
     }
 }
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 }  // namespace
 }  // namespace mmx
 

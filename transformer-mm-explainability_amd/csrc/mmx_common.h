@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
 #include "../../include/mmx_relevancy.h"
+#include "entry_checks.h"
 
 namespace mmx {
 
@@ -147,6 +149,18 @@ __device__ __forceinline__ void slab_store(typename slab_elem<DT>::type* p, floa
 
 // clamp(x, min=0) with torch semantics: NaN propagates (fmaxf would drop it)
 __device__ __forceinline__ float relu_nan(float x) { return (x < 0.0f) ? 0.0f : x; }
+// torch's min / max: a NaN wins
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
+
+// 64-lane all-reduce: the xor butterfly, every lane ends with the same sum
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// floats between two rows of N floats in a workspace whose rows start on 16-byte boundaries: N rounded up to whole chunks
+__host__ __device__ __forceinline__ int row_stride4(int N) { return (N + 3) & ~3; }
 
 // safe_divide of the reference's LRP layer library (DETR/modules/layers.py:11-14) in fp32: a / (b + 1e-9), 0 where b == 0.  ONE device
 // function for the attention core (attention_lrp.hip) and the layer rules (lrp_kernels.hip).  den = clamp(b, min=1e-9) +
@@ -216,14 +230,51 @@ __device__ __forceinline__ int xcd_contiguous_id(int w, int total) {
 }
 
 inline size_t dtype_size(int dt) { return dt == MMX_F32 ? 4 : 2; }
-// [a, a + na) and [b, b + nb) share a byte (a null pointer overlaps nothing): the alias checks of the entries
-inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!a || !b) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
 
 void set_error(const char* fmt, ...);
+
+// The preamble of an entry that takes a workspace or a pointer table (entry_checks.h has the sizes and the alias test).  Each
+// returns MMX_OK, or MMX_EINVAL after set_error: `if (int rc = check_...(...)) return rc;`.  `entry` is the C name of the caller.
+//
+// the workspace against what `query` (the name of the entry's _workspace_bytes function) returns, then its alignment
+inline int check_workspace(const char* entry, const char* query, const void* ws, size_t given, size_t need) {
+    if (given < need) {
+        set_error("%s: workspace of %zu bytes needed (%s), got %zu", entry, need, query, given);
+        return MMX_EINVAL;
+    }
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) {
+        set_error("%s: the workspace must be 16-byte aligned", entry);
+        return MMX_EINVAL;
+    }
+    return MMX_OK;
+}
+// no null entry in a host table of n <= MMX_BASELINES_MAX_TABLE device pointers, copied into a kernel's argument struct; `table`
+// names it in the message ("the text table").  src2 / dst2: a second table of the same length that goes entry by entry with the
+// first (a slab and its gradient), or null
+inline int copy_table(const char* entry, const char* table, const void* const* src, int n, const float** dst,
+                      const void* const* src2 = nullptr, const float** dst2 = nullptr) {
+    for (int l = 0; l < n; ++l) {
+        if (!src[l] || (src2 && !src2[l])) {
+            set_error("%s: null pointer in %s (entry %d)", entry, table, l);
+            return MMX_EINVAL;
+        }
+        dst[l] = static_cast<const float*>(src[l]);
+        if (src2) dst2[l] = static_cast<const float*>(src2[l]);
+    }
+    return MMX_OK;
+}
+// a one-dimensional grid carries at most 2^31 - 1 workgroups; the format spells the product for the message ("B=%d x %d blocks")
+__attribute__((format(printf, 3, 4))) inline int check_grid(const char* entry, int64_t groups, const char* product_fmt, ...) {
+    if (groups <= 2147483647LL) return MMX_OK;
+    char product[128];
+    va_list ap;
+    va_start(ap, product_fmt);
+    vsnprintf(product, sizeof(product), product_fmt, ap);
+    va_end(ap);
+    set_error("%s: %s is beyond a one-dimensional grid", entry, product);
+    return MMX_EINVAL;
+}
+
 void attn_head_enable(int on);
 void attn_head_tile_skip(int on);
 bool attn_head_live_option(const char* key, int value);   // attention_head.hip: option "text_live_attn"

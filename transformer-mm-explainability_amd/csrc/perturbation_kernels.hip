@@ -376,16 +376,10 @@ extern "C" int mmx_selfattn_perturb_regions(const void* emb_dev, const void* cam
     MMX_CHECK_ARG(R >= bg * T && R <= bg * (T + V), "%s: %lld packed rows outside B * G * T .. B * G * (T + V) = %lld .. %lld", me,
                   static_cast<long long>(R), static_cast<long long>(bg * T), static_cast<long long>(bg * (T + V)));
     const size_t f = sizeof(float), N = static_cast<size_t>(T + V), nb = static_cast<size_t>(B), rows = static_cast<size_t>(R);
-    const void* ins[4] = {emb_dev, cam_dev, text_len_dev, counts_dev};
-    const size_t in_sizes[4] = {f * nb * N * E, f * nb * N, sizeof(int) * nb, sizeof(int) * G};
-    const void* outs[4] = {x_dev, mask_dev, pooled_dev, ranks_dev};
-    const size_t out_sizes[4] = {f * rows * E, f * rows, sizeof(long long) * static_cast<size_t>(bg), sizeof(int) * nb * V};
-    bool alias = false;
-    for (int o = 0; o < 4; ++o) {
-        for (int i = 0; i < 4; ++i) alias |= ranges_overlap(outs[o], out_sizes[o], ins[i], in_sizes[i]);
-        for (int p = o + 1; p < 4; ++p) alias |= ranges_overlap(outs[o], out_sizes[o], outs[p], out_sizes[p]);
-    }
-    MMX_CHECK_ARG(!alias, "%s: an output may not alias an input or another output", me);
+    const Span ins[4] = {{emb_dev, f * nb * N * E}, {cam_dev, f * nb * N}, {text_len_dev, sizeof(int) * nb}, {counts_dev, sizeof(int) * G}};
+    const Span outs[4] = {{x_dev, f * rows * E}, {mask_dev, f * rows}, {pooled_dev, sizeof(long long) * static_cast<size_t>(bg)},
+                          {ranks_dev, sizeof(int) * nb * V}};
+    MMX_CHECK_ARG(!spans_alias(outs, 4, ins, 4), "%s: an output may not alias an input or another output", me);
     const bool vec = E % 4 == 0 && ((reinterpret_cast<uintptr_t>(emb_dev) | reinterpret_cast<uintptr_t>(x_dev)) & 15u) == 0;
     const dim3 grid(static_cast<unsigned>(bg));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -414,16 +408,11 @@ extern "C" int mmx_selfattn_perturb_text(const void* ids_dev, const void* segmen
                   "%s: T=%d V=%d outside T >= 3, V >= 1, T + V <= %d", me, T, V, kMaxPositions);
     MMX_CHECK_ARG(S >= 1 && S <= kMaxTokenSteps, "%s: %d steps outside 1 .. %d", me, S, kMaxTokenSteps);
     const size_t ll = sizeof(long long), nb = static_cast<size_t>(B), nt = static_cast<size_t>(T), ns = static_cast<size_t>(S);
-    const void* ins[5] = {ids_dev, segments_dev, cam_dev, text_len_dev, counts_dev};
-    const size_t in_sizes[5] = {ll * nb * nt, ll * nb * nt, sizeof(float) * nb * (T + V), sizeof(int) * nb, sizeof(int) * ns * nt};
-    const void* outs[4] = {out_ids_dev, out_segments_dev, out_mask_dev, new_len_dev};
-    const size_t out_sizes[4] = {ll * ns * nb * nt, ll * ns * nb * nt, ll * ns * nb * nt, ll * ns * nb};
-    bool alias = false;
-    for (int o = 0; o < 4; ++o) {
-        for (int i = 0; i < 5; ++i) alias |= ranges_overlap(outs[o], out_sizes[o], ins[i], in_sizes[i]);
-        for (int p = o + 1; p < 4; ++p) alias |= ranges_overlap(outs[o], out_sizes[o], outs[p], out_sizes[p]);
-    }
-    MMX_CHECK_ARG(!alias, "%s: an output may not alias an input or another output", me);
+    const Span ins[5] = {{ids_dev, ll * nb * nt}, {segments_dev, ll * nb * nt}, {cam_dev, sizeof(float) * nb * (T + V)},
+                         {text_len_dev, sizeof(int) * nb}, {counts_dev, sizeof(int) * ns * nt}};
+    const Span outs[4] = {{out_ids_dev, ll * ns * nb * nt}, {out_segments_dev, ll * ns * nb * nt}, {out_mask_dev, ll * ns * nb * nt},
+                          {new_len_dev, ll * ns * nb}};
+    MMX_CHECK_ARG(!spans_alias(outs, 4, ins, 5), "%s: an output may not alias an input or another output", me);
     hipStream_t s = static_cast<hipStream_t>(stream);
 #define MMX_TEXT_LAUNCH(NEG)                                                                                                         \
     selfattn_perturb_text_kernel<NEG><<<dim3(B), 64, 0, s>>>(                                                                        \

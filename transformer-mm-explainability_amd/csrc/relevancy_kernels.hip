@@ -878,7 +878,6 @@ __global__ void copy_scrub_kernel(const float* __restrict__ in, float* __restric
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 extern "C" size_t mmx_mm_rules_workspace_bytes(int Ns, int Nq) {
     // Rn_ss [Ns,Ns] + Rn_qq [Nq,Nq] + tmp [Ns,Nq]

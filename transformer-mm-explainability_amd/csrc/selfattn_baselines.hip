@@ -42,19 +42,8 @@ constexpr int kSaRing = 8;                      // row loads in flight per lane 
 __device__ __forceinline__ int sa_text_len(const int* len, int b, int T) { return len ? min(max(len[b], 2), T) : T; }
 __device__ __forceinline__ int sa_vis_len(const int* len, int b, int V) { return len ? min(max(len[b], 1), V) : V; }
 __device__ __forceinline__ bool sa_live(int j, int t, int T, int v) { return j < t || (j >= T && j < T + v); }
-// floats between two rows of a head-mean matrix in the rollout workspace: N rounded up to whole 16-byte chunks
-__host__ __device__ __forceinline__ int sa_row_stride(int N) { return (N + 3) & ~3; }
 // the k-th live index, k < t + v
 __device__ __forceinline__ int sa_live_at(int k, int t, int T) { return k < t ? k : T + (k - t); }
-
-__device__ __forceinline__ float wave_sum_sa(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-// torch's min / max: a NaN wins
-__device__ __forceinline__ float min_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }
-__device__ __forceinline__ float max_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
 
 // columns 4 lane .. 4 lane + 3 of one row of N floats (zeros beyond N); p points at the row
 __device__ __forceinline__ f32x4 sa_row4(const float* __restrict__ p, int lane, int N) {
@@ -100,7 +89,7 @@ __global__ __launch_bounds__(kSaThreads) void sa_gradcam_w_kernel(const float* _
 #pragma unroll
         for (int e = 0; e < 4; ++e) s += lv[e] ? g[e] : 0.f;
     }
-    s = wave_sum_sa(s);
+    s = wave_sum(s);
     if (lane == 0) part[wave] = s;
     __syncthreads();
     if (tid == 0) {
@@ -172,77 +161,36 @@ __global__ __launch_bounds__(kSaThreads) void sa_gradcam_out_kernel(const float*
 }
 
 struct SaRolloutArgs {
-    const float* attn[kSaMaxTable];    // [B, H, N, N], already sliced to start_layer:
+    const float* attn[kSaMaxTable];    // [B, H, N, N], one entry per layer (the rollout's already sliced to start_layer:)
     int n_layers, B, H, T, V, strips;
     const int *text_len, *vis_len;
-    float* ws;                         // [B][n_layers][N][NP] head means, NP = sa_row_stride(N); rows of padded queries and the
+    float* ws;                         // [B][n_layers][N][NP] head means, NP = row_stride4(N); rows of padded queries and the
                                        // NP - N floats behind a row are never written, and never used
     float* out;
+    const float* grad[kSaMaxTable];    // generate_ours only: [B, H, N, N] the gradients of attn, NOT zero at padded key columns
+                                       // (behind everything sa_rollout_row_kernel reads)
 };
 
-__global__ __launch_bounds__(kSaThreads) void sa_rollout_means_kernel(const SaRolloutArgs a) {
-    const int tid = threadIdx.x, N = a.T + a.V, hs = N * N, H = a.H;
-    int w = blockIdx.x;
-    const int s = w % a.strips; w /= a.strips;
-    const int l = w % a.n_layers, b = w / a.n_layers;
-    const int t = sa_text_len(a.text_len, b, a.T), v = sa_vis_len(a.vis_len, b, a.V);
-    const float* __restrict__ src = a.attn[l] + static_cast<int64_t>(b) * H * hs;
-    const int NP = sa_row_stride(N);
-    float* dst = a.ws + (static_cast<int64_t>(b) * a.n_layers + l) * N * NP;
-    const float fH = static_cast<float>(H);
-#pragma unroll
-    for (int u = 0; u < kSaMeanChunks; ++u) {
-        const int p = s * kSaMeanStrip + (u * kSaThreads + tid) * 4;
-        if (p >= hs) continue;
-        bool any = false;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) any |= p + e < hs && sa_live((p + e) / N, t, a.T, v);
-        if (!any) continue;                                          // a chunk of padded query rows: neither read nor written
-        f32x4 m = {0.f, 0.f, 0.f, 0.f};
-        if (p + 3 < hs) {                                            // the 16-byte loads stay inside the head's own N x N block
-            int h = 0;
-            for (; h + 6 <= H; h += 6) {
-                f32x4 x[6];
-#pragma unroll
-                for (int q = 0; q < 6; ++q) x[q] = ldg4_u(src + static_cast<int64_t>(h + q) * hs + p);
-#pragma unroll
-                for (int q = 0; q < 6; ++q) m += x[q];
-            }
-            for (; h < H; ++h) m += ldg4_u(src + static_cast<int64_t>(h) * hs + p);
-        } else {
-            for (int e = 0; p + e < hs; ++e)
-                for (int h = 0; h < H; ++h) m[e] += src[static_cast<int64_t>(h) * hs + p + e];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (p + e < hs) {
-                const int row = (p + e) / N;
-                dst[row * NP + (p + e - row * N)] = m[e] / fH;       // rows of the workspace start on 16-byte boundaries
-            }
-    }
+// what head h adds to the matrix of a layer: its probability (rollout), or rule 5, clamp0(grad_h * attn_h) (generate_ours)
+template <bool kOurs>
+__device__ __forceinline__ float sa_head_term(float x, float g) {
+    if constexpr (kOurs) return relu_nan(g * x);
+    else return x;
 }
 
-struct SaOursArgs {
-    const float* attn[kSaMaxTable];    // [B, H, N, N] probabilities (or any cam slab), one entry per layer
-    const float* grad[kSaMaxTable];    // [B, H, N, N] their gradients: NOT zero at padded key columns
-    int n_layers, B, H, T, V, strips;
-    const int *text_len, *vis_len;
-    float* ws;                         // [B][n_layers][N][NP] as SaRolloutArgs::ws: sa_rollout_row_kernel reads it
-};
-
-// rule 5 on the live rows: (sum_h clamp0(grad_h * attn_h)) / H, the clamp per head BEFORE the sum, heads in ascending order.  The
-// workgroup layout, the skipped chunks and the workspace are those of sa_rollout_means_kernel; padded key columns of a live row are
-// computed and written (the gradient there is arbitrary) and never read: the row kernel multiplies by x, which is zero there.
-__global__ __launch_bounds__(kSaThreads) void sa_ours_means_kernel(const SaOursArgs a) {
-    constexpr int kHeads = 4;                                        // heads per batch: 2 * kHeads 16-byte loads in flight
+// The matrix of a layer on the live rows: (sum_h term_h) / H, the clamp of rule 5 per head BEFORE the sum, heads in ascending order,
+// kHeads of them (kHeads 16-byte loads per slab) in flight.  Padded key columns of a live row are computed and written (the
+// gradient there is arbitrary) and never read: the row kernel multiplies by x, which is zero there.
+template <bool kOurs, int kHeads>
+__device__ __forceinline__ void sa_means_body(const SaRolloutArgs& a) {
     const int tid = threadIdx.x, N = a.T + a.V, hs = N * N, H = a.H;
     int w = blockIdx.x;
     const int s = w % a.strips; w /= a.strips;
     const int l = w % a.n_layers, b = w / a.n_layers;
     const int t = sa_text_len(a.text_len, b, a.T), v = sa_vis_len(a.vis_len, b, a.V);
     const float* __restrict__ P = a.attn[l] + static_cast<int64_t>(b) * H * hs;
-    const float* __restrict__ G = a.grad[l] + static_cast<int64_t>(b) * H * hs;
-    const int NP = sa_row_stride(N);
+    const float* __restrict__ G = kOurs ? a.grad[l] + static_cast<int64_t>(b) * H * hs : P;
+    const int NP = row_stride4(N);
     float* dst = a.ws + (static_cast<int64_t>(b) * a.n_layers + l) * N * NP;
     const float fH = static_cast<float>(H);
 #pragma unroll
@@ -261,22 +209,25 @@ __global__ __launch_bounds__(kSaThreads) void sa_ours_means_kernel(const SaOursA
 #pragma unroll
                 for (int q = 0; q < kHeads; ++q) {
                     x[q] = ldg4_u(P + static_cast<int64_t>(h + q) * hs + p);
-                    g[q] = ldg4_u(G + static_cast<int64_t>(h + q) * hs + p);
+                    g[q] = kOurs ? ldg4_u(G + static_cast<int64_t>(h + q) * hs + p) : x[q];
                 }
 #pragma unroll
                 for (int q = 0; q < kHeads; ++q)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) m[e] += relu_nan(g[q][e] * x[q][e]);
+                    for (int e = 0; e < 4; ++e) m[e] += sa_head_term<kOurs>(x[q][e], g[q][e]);
             }
             for (; h < H; ++h) {
-                const f32x4 x = ldg4_u(P + static_cast<int64_t>(h) * hs + p), g = ldg4_u(G + static_cast<int64_t>(h) * hs + p);
+                const f32x4 x = ldg4_u(P + static_cast<int64_t>(h) * hs + p);
+                const f32x4 g = kOurs ? ldg4_u(G + static_cast<int64_t>(h) * hs + p) : x;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) m[e] += relu_nan(g[e] * x[e]);
+                for (int e = 0; e < 4; ++e) m[e] += sa_head_term<kOurs>(x[e], g[e]);
             }
         } else {
             for (int e = 0; p + e < hs; ++e)
-                for (int h = 0; h < H; ++h)
-                    m[e] += relu_nan(G[static_cast<int64_t>(h) * hs + p + e] * P[static_cast<int64_t>(h) * hs + p + e]);
+                for (int h = 0; h < H; ++h) {
+                    const float x = P[static_cast<int64_t>(h) * hs + p + e];
+                    m[e] += sa_head_term<kOurs>(x, kOurs ? G[static_cast<int64_t>(h) * hs + p + e] : x);
+                }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -287,12 +238,16 @@ __global__ __launch_bounds__(kSaThreads) void sa_ours_means_kernel(const SaOursA
     }
 }
 
+// thin wrappers: the kernel names are what the profiles and tools/prof_summary.py select by
+__global__ __launch_bounds__(kSaThreads) void sa_rollout_means_kernel(const SaRolloutArgs a) { sa_means_body<false, 6>(a); }
+__global__ __launch_bounds__(kSaThreads) void sa_ours_means_kernel(const SaRolloutArgs a) { sa_means_body<true, 4>(a); }
+
 __global__ __launch_bounds__(kSaThreads) void sa_rollout_row_kernel(const SaRolloutArgs a) {
     __shared__ float x[kSaMaxN];
     __shared__ float part[kSaWaves][kSaMaxN];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x, N = a.T + a.V, NP = sa_row_stride(N), L = a.n_layers;
+    const int b = blockIdx.x, N = a.T + a.V, NP = row_stride4(N), L = a.n_layers;
     const int64_t ls = static_cast<int64_t>(N) * NP;
     const int t = sa_text_len(a.text_len, b, a.T), v = sa_vis_len(a.vis_len, b, a.V), n = t + v, c = t - 2;
     // items of a layer and wave: live rows wave, wave + 4, ..., padded to a multiple of the ring so that a layer ends where an
@@ -345,7 +300,6 @@ __global__ __launch_bounds__(kSaThreads) void sa_rollout_row_kernel(const SaRoll
 
 using namespace mmx;
 
-static inline size_t sa_align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 static inline bool sa_sizes_ok(int T, int V) { return T >= 2 && V >= 1 && T <= kSaMaxN && V <= kSaMaxN && T + V <= kSaMaxN; }
 static inline int sa_cam_strips(int N) { return (N + kSaStripRows - 1) / kSaStripRows; }
 
@@ -353,7 +307,7 @@ static inline int sa_cam_strips(int N) { return (N + kSaStripRows - 1) / kSaStri
 extern "C" size_t mmx_selfattn_row_live_workspace_bytes(int B, int H, int T, int V) {
     if (B < 1 || H < 1 || !sa_sizes_ok(T, V)) return 0;
     const size_t f = sizeof(float), nb = static_cast<size_t>(B), N = static_cast<size_t>(T + V);
-    return sa_align256(f * nb * H) + sa_align256(f * nb * sa_cam_strips(T + V) * 2) + sa_align256(f * nb * N);
+    return align256(f * nb * H) + align256(f * nb * sa_cam_strips(T + V) * 2) + align256(f * nb * N);
 }
 
 extern "C" int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int T, int V,
@@ -365,22 +319,15 @@ extern "C" int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev,
     const size_t need = grad_dev ? mmx_selfattn_row_live_workspace_bytes(B, H, T, V) : 0;
     if (grad_dev) {
         MMX_CHECK_ARG(workspace_dev, "mmx_selfattn_row_live: null pointer (the GradCAM form needs a workspace)");
-        MMX_CHECK_ARG(workspace_bytes >= need,
-                      "mmx_selfattn_row_live: workspace of %zu bytes needed (mmx_selfattn_row_live_workspace_bytes), got %zu", need,
-                      workspace_bytes);
-        MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0,
-                      "mmx_selfattn_row_live: the workspace must be 16-byte aligned");
+        if (int rc = check_workspace("mmx_selfattn_row_live", "mmx_selfattn_row_live_workspace_bytes", workspace_dev, workspace_bytes, need))
+            return rc;
     }
     const int N = T + V;
     const size_t f = sizeof(float), nb = static_cast<size_t>(B);
-    const size_t out_bytes = f * nb * N, in_bytes = f * nb * H * N * N, len_bytes = sizeof(int) * nb;
-    const void* outs[2] = {out_dev, grad_dev ? workspace_dev : nullptr};
-    const size_t out_sizes[2] = {out_bytes, need};
-    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
-    for (int o = 0; o < 2; ++o)
-        alias |= ranges_overlap(outs[o], out_sizes[o], attn_dev, in_bytes) || ranges_overlap(outs[o], out_sizes[o], grad_dev, in_bytes) ||
-                 ranges_overlap(outs[o], out_sizes[o], text_len_dev, len_bytes) || ranges_overlap(outs[o], out_sizes[o], vis_len_dev, len_bytes);
-    MMX_CHECK_ARG(!alias, "mmx_selfattn_row_live: the output or the workspace may not alias an input or each other");
+    const size_t in_bytes = f * nb * H * N * N, len_bytes = sizeof(int) * nb;
+    const Span outs[2] = {{out_dev, f * nb * N}, {grad_dev ? workspace_dev : nullptr, need}};
+    const Span ins[4] = {{attn_dev, in_bytes}, {grad_dev, in_bytes}, {text_len_dev, len_bytes}, {vis_len_dev, len_bytes}};
+    MMX_CHECK_ARG(!spans_alias(outs, 2, ins, 4), "mmx_selfattn_row_live: the output or the workspace may not alias an input or each other");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float* P = static_cast<const float*>(attn_dev);
     const int* tl = static_cast<const int*>(text_len_dev);
@@ -394,8 +341,8 @@ extern "C" int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev,
     const int strips = sa_cam_strips(N);
     char* ws = static_cast<char*>(workspace_dev);
     float* w = reinterpret_cast<float*>(ws);
-    float* mm = reinterpret_cast<float*>(ws + sa_align256(f * nb * H));
-    float* row = reinterpret_cast<float*>(ws + sa_align256(f * nb * H) + sa_align256(f * nb * strips * 2));
+    float* mm = reinterpret_cast<float*>(ws + align256(f * nb * H));
+    float* row = reinterpret_cast<float*>(ws + align256(f * nb * H) + align256(f * nb * strips * 2));
     sa_gradcam_w_kernel<<<static_cast<unsigned>(B) * H, kSaThreads, 0, s>>>(static_cast<const float*>(grad_dev), w, T, V, tl, vl, H);
     MMX_LAUNCH_CHECK("sa_gradcam_w_kernel");
     sa_gradcam_cam_kernel<<<static_cast<unsigned>(B) * strips, kSaThreads, 0, s>>>(P, w, mm, row, H, T, V, strips, tl, vl);
@@ -408,50 +355,63 @@ extern "C" int mmx_selfattn_row_live(const void* attn_dev, const void* grad_dev,
 extern "C" size_t mmx_selfattn_rollout_row_workspace_bytes(int n_layers, int B, int T, int V) {
     if (n_layers < 1 || n_layers > kSaMaxTable || B < 1 || !sa_sizes_ok(T, V)) return 0;
     const size_t N = static_cast<size_t>(T + V);
-    return sa_align256(sizeof(float) * static_cast<size_t>(B) * n_layers * N * sa_row_stride(T + V));
+    return align256(sizeof(float) * static_cast<size_t>(B) * n_layers * N * row_stride4(T + V));
 }
 
-extern "C" int mmx_selfattn_rollout_row(const void* const* attn_table, int n_layers, int B, int H, int T, int V,
-                                        const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev,
-                                        size_t workspace_bytes, void* stream) {
-    MMX_CHECK_ARG(attn_table && out_dev && workspace_dev, "mmx_selfattn_rollout_row: null pointer");
-    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_selfattn_rollout_row: B=%d H=%d (both >= 1)", B, H);
-    MMX_CHECK_ARG(sa_sizes_ok(T, V), "mmx_selfattn_rollout_row: T=%d V=%d outside T >= 2, V >= 1, T + V <= %d", T, V, kSaMaxN);
-    MMX_CHECK_ARG(n_layers >= 1 && n_layers <= kSaMaxTable, "mmx_selfattn_rollout_row: n_layers=%d outside 1..%d", n_layers, kSaMaxTable);
+// the rollout (grad_table null) and generate_ours: the matrices of the layers into the workspace, then the row chain on them
+static int sa_chain_row(const void* const* attn_table, const void* const* grad_table, int n_layers, int B, int H, int T, int V,
+                        const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev, size_t workspace_bytes,
+                        void* stream) {
+    const bool ours = grad_table != nullptr;
+    const char* me = ours ? "mmx_selfattn_ours_row" : "mmx_selfattn_rollout_row";
+    MMX_CHECK_ARG(attn_table && out_dev && workspace_dev, "%s: null pointer", me);
+    MMX_CHECK_ARG(B > 0 && H > 0, "%s: B=%d H=%d (both >= 1)", me, B, H);
+    MMX_CHECK_ARG(sa_sizes_ok(T, V), "%s: T=%d V=%d outside T >= 2, V >= 1, T + V <= %d", me, T, V, kSaMaxN);
+    MMX_CHECK_ARG(n_layers >= 1 && n_layers <= kSaMaxTable, "%s: n_layers=%d outside 1..%d", me, n_layers, kSaMaxTable);
+    const int N = T + V;
+    const int strips = (N * N + kSaMeanStrip - 1) / kSaMeanStrip;
+    const int64_t groups = static_cast<int64_t>(B) * n_layers * strips;
+    if (int rc = check_grid(me, groups, "B=%d x n_layers=%d x %d strips", B, n_layers, strips)) return rc;
     const size_t need = mmx_selfattn_rollout_row_workspace_bytes(n_layers, B, T, V);
-    MMX_CHECK_ARG(workspace_bytes >= need,
-                  "mmx_selfattn_rollout_row: workspace of %zu bytes needed (mmx_selfattn_rollout_row_workspace_bytes), got %zu", need,
-                  workspace_bytes);
-    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_selfattn_rollout_row: the workspace must be 16-byte aligned");
+    const char* query = ours ? "mmx_selfattn_ours_row_workspace_bytes" : "mmx_selfattn_rollout_row_workspace_bytes";
+    if (int rc = check_workspace(me, query, workspace_dev, workspace_bytes, need)) return rc;
     SaRolloutArgs a;
     memset(&a, 0, sizeof(a));
-    for (int l = 0; l < n_layers; ++l) {
-        MMX_CHECK_ARG(attn_table[l], "mmx_selfattn_rollout_row: null pointer in the table (entry %d)", l);
-        a.attn[l] = static_cast<const float*>(attn_table[l]);
-    }
-    const int N = T + V;
+    if (int rc = copy_table(me, ours ? "a table" : "the table", attn_table, n_layers, a.attn, grad_table, a.grad)) return rc;
     const size_t f = sizeof(float), nb = static_cast<size_t>(B);
-    const void* outs[2] = {out_dev, workspace_dev};
-    const size_t out_sizes[2] = {f * nb * N, need};
-    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
-    for (int o = 0; o < 2; ++o) {
-        for (int l = 0; l < n_layers; ++l) alias |= ranges_overlap(outs[o], out_sizes[o], attn_table[l], f * nb * H * N * N);
-        alias |= ranges_overlap(outs[o], out_sizes[o], text_len_dev, sizeof(int) * nb);
-        alias |= ranges_overlap(outs[o], out_sizes[o], vis_len_dev, sizeof(int) * nb);
+    const Span outs[2] = {{out_dev, f * nb * N}, {workspace_dev, need}};
+    Span ins[2 * kSaMaxTable + 2];
+    int n_in = 0;
+    for (int l = 0; l < n_layers; ++l) {
+        ins[n_in++] = {attn_table[l], f * nb * H * N * N};
+        if (ours) ins[n_in++] = {grad_table[l], f * nb * H * N * N};
     }
-    MMX_CHECK_ARG(!alias, "mmx_selfattn_rollout_row: the output or the workspace may not alias an input or each other");
-    a.n_layers = n_layers; a.B = B; a.H = H; a.T = T; a.V = V;
-    a.strips = (N * N + kSaMeanStrip - 1) / kSaMeanStrip;
+    ins[n_in++] = {text_len_dev, sizeof(int) * nb};
+    ins[n_in++] = {vis_len_dev, sizeof(int) * nb};
+    MMX_CHECK_ARG(!spans_alias(outs, 2, ins, n_in), "%s: the output or the workspace may not alias an input or each other", me);
+    a.n_layers = n_layers; a.B = B; a.H = H; a.T = T; a.V = V; a.strips = strips;
     a.text_len = static_cast<const int*>(text_len_dev);
     a.vis_len = static_cast<const int*>(vis_len_dev);
     a.ws = static_cast<float*>(workspace_dev);
     a.out = static_cast<float*>(out_dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    sa_rollout_means_kernel<<<static_cast<unsigned>(B) * n_layers * a.strips, kSaThreads, 0, s>>>(a);
-    MMX_LAUNCH_CHECK("sa_rollout_means_kernel");
+    if (ours) {
+        sa_ours_means_kernel<<<static_cast<unsigned>(groups), kSaThreads, 0, s>>>(a);
+        MMX_LAUNCH_CHECK("sa_ours_means_kernel");
+    } else {
+        sa_rollout_means_kernel<<<static_cast<unsigned>(groups), kSaThreads, 0, s>>>(a);
+        MMX_LAUNCH_CHECK("sa_rollout_means_kernel");
+    }
     sa_rollout_row_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(a);
     MMX_LAUNCH_CHECK("sa_rollout_row_kernel");
     return MMX_OK;
+}
+
+extern "C" int mmx_selfattn_rollout_row(const void* const* attn_table, int n_layers, int B, int H, int T, int V,
+                                        const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev,
+                                        size_t workspace_bytes, void* stream) {
+    return sa_chain_row(attn_table, nullptr, n_layers, B, H, T, V, text_len_dev, vis_len_dev, out_dev, workspace_dev, workspace_bytes,
+                        stream);
 }
 
 // the workspace is the rollout's: one head-mean matrix per (sample, layer)
@@ -462,52 +422,7 @@ extern "C" size_t mmx_selfattn_ours_row_workspace_bytes(int n_layers, int B, int
 extern "C" int mmx_selfattn_ours_row(const void* const* attn_table, const void* const* grad_table, int n_layers, int B, int H, int T,
                                      int V, const void* text_len_dev, const void* vis_len_dev, void* out_dev, void* workspace_dev,
                                      size_t workspace_bytes, void* stream) {
-    MMX_CHECK_ARG(attn_table && grad_table && out_dev && workspace_dev, "mmx_selfattn_ours_row: null pointer");
-    MMX_CHECK_ARG(B > 0 && H > 0, "mmx_selfattn_ours_row: B=%d H=%d (both >= 1)", B, H);
-    MMX_CHECK_ARG(sa_sizes_ok(T, V), "mmx_selfattn_ours_row: T=%d V=%d outside T >= 2, V >= 1, T + V <= %d", T, V, kSaMaxN);
-    MMX_CHECK_ARG(n_layers >= 1 && n_layers <= kSaMaxTable, "mmx_selfattn_ours_row: n_layers=%d outside 1..%d", n_layers, kSaMaxTable);
-    const int N = T + V;
-    const int strips = (N * N + kSaMeanStrip - 1) / kSaMeanStrip;
-    const int64_t groups = static_cast<int64_t>(B) * n_layers * strips;
-    MMX_CHECK_ARG(groups <= 2147483647LL, "mmx_selfattn_ours_row: B=%d x n_layers=%d x %d strips is beyond a one-dimensional grid", B,
-                  n_layers, strips);
-    const size_t need = mmx_selfattn_ours_row_workspace_bytes(n_layers, B, T, V);
-    MMX_CHECK_ARG(workspace_bytes >= need,
-                  "mmx_selfattn_ours_row: workspace of %zu bytes needed (mmx_selfattn_ours_row_workspace_bytes), got %zu", need,
-                  workspace_bytes);
-    MMX_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace_dev) & 15) == 0, "mmx_selfattn_ours_row: the workspace must be 16-byte aligned");
-    SaOursArgs m;
-    memset(&m, 0, sizeof(m));
-    for (int l = 0; l < n_layers; ++l) {
-        MMX_CHECK_ARG(attn_table[l] && grad_table[l], "mmx_selfattn_ours_row: null pointer in a table (entry %d)", l);
-        m.attn[l] = static_cast<const float*>(attn_table[l]);
-        m.grad[l] = static_cast<const float*>(grad_table[l]);
-    }
-    const size_t f = sizeof(float), nb = static_cast<size_t>(B);
-    const void* outs[2] = {out_dev, workspace_dev};
-    const size_t out_sizes[2] = {f * nb * N, need};
-    bool alias = ranges_overlap(outs[0], out_sizes[0], outs[1], out_sizes[1]);
-    for (int o = 0; o < 2; ++o) {
-        for (int l = 0; l < n_layers; ++l)
-            alias |= ranges_overlap(outs[o], out_sizes[o], attn_table[l], f * nb * H * N * N) ||
-                     ranges_overlap(outs[o], out_sizes[o], grad_table[l], f * nb * H * N * N);
-        alias |= ranges_overlap(outs[o], out_sizes[o], text_len_dev, sizeof(int) * nb);
-        alias |= ranges_overlap(outs[o], out_sizes[o], vis_len_dev, sizeof(int) * nb);
-    }
-    MMX_CHECK_ARG(!alias, "mmx_selfattn_ours_row: the output or the workspace may not alias an input or each other");
-    m.n_layers = n_layers; m.B = B; m.H = H; m.T = T; m.V = V; m.strips = strips;
-    m.text_len = static_cast<const int*>(text_len_dev);
-    m.vis_len = static_cast<const int*>(vis_len_dev);
-    m.ws = static_cast<float*>(workspace_dev);
-    SaRolloutArgs a;                   // the row kernel reads the sizes, the lengths, the workspace and the output: no slab
-    memset(&a, 0, sizeof(a));
-    a.n_layers = n_layers; a.B = B; a.H = H; a.T = T; a.V = V; a.strips = strips;
-    a.text_len = m.text_len; a.vis_len = m.vis_len; a.ws = m.ws;
-    a.out = static_cast<float*>(out_dev);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    sa_ours_means_kernel<<<static_cast<unsigned>(groups), kSaThreads, 0, s>>>(m);
-    MMX_LAUNCH_CHECK("sa_ours_means_kernel");
-    sa_rollout_row_kernel<<<static_cast<unsigned>(B), kSaThreads, 0, s>>>(a);
-    MMX_LAUNCH_CHECK("sa_rollout_row_kernel");
-    return MMX_OK;
+    MMX_CHECK_ARG(grad_table, "mmx_selfattn_ours_row: null pointer");
+    return sa_chain_row(attn_table, grad_table, n_layers, B, H, T, V, text_len_dev, vis_len_dev, out_dev, workspace_dev, workspace_bytes,
+                        stream);
 }
