@@ -31,6 +31,16 @@ MAX_LAYERS = 48
 _vp, _i, _i64, _sz, _f, _u = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float, C.c_uint
 _vpp = C.POINTER(C.c_void_p)
 
+# the groups the attention prototypes are made of, in the words of their declarations in include/mmx_relevancy.h
+_T = [_vp, _i64, _i64, _i64]                    # a strided tensor: pointer, batch / head / token stride
+_QKV = [_vp] * 3 + [_i64] * 9                   # q, k, v, then their three stride triples
+_MASK = [_vp, _i64, _i64]                       # mask, mask_sb, mask_sq
+_PROBS = [_vp, _i64]                            # probs, probs_sb
+_GRADS = [_vp] * 4 + [_i64] * 9                 # dprobs, dq, dk, dv, then the stride triples of dq, dk, dv
+_DIMS = [_i] * 5 + [_f, _i]                     # B, H, Nq, Nk, D, scale, scale_mode
+_WS = [_vp, _sz, _vp]                           # workspace, workspace_bytes, stream
+_BWD_EX = _QKV + _PROBS + [_i] + _T + _T + _GRADS + _DIMS + [_i]     # ..., slab_dtype, dO, forward O, ..., need_dqkv
+
 _PROTOTYPES = {
     "mmx_abi_version": (_i, []),
     "mmx_last_error": (C.c_char_p, []),
@@ -69,41 +79,27 @@ _PROTOTYPES = {
     "mmx_otsu_masks": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "mmx_rollout_workspace_bytes": (_sz, [_i, _i]),
     "mmx_rollout_chain": (_i, [_vpp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "mmx_attn_capture_fwd": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64,
-                                  _i, _i, _i, _i, _i, _f, _i, _vp]),
-    "mmx_attn_capture_fwd_ex": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _i, _vp, _i64, _i64, _i64,
-                                     _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "mmx_attn_capture_fwd": (_i, _QKV + _MASK + [_vp] + _T + _DIMS + [_vp]),                      # probs | O | stream
+    "mmx_attn_capture_fwd_ex": (_i, _QKV + _MASK + [_vp, _i] + _T + _DIMS + [_vp]),               # probs, slab_dtype
     "mmx_attn_live_shape": (_i, [_i, _i, _i]),
-    "mmx_attn_capture_fwd_live": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _i, _vp, _i64, _i64, _i64,
-                                       _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
-    "mmx_attn_capture_bwd_live": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
-                                  + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _sz, _vp]),
-    "mmx_attn_fwd": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _i, _vp]),
-    "mmx_attn_fwd_live": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _i, _vp,
-                               _vp]),
+    "mmx_attn_capture_fwd_live": (_i, _QKV + _MASK + [_vp, _i] + _T + _DIMS + [_vp, _vp]),        # ..., eot, stream
+    "mmx_attn_capture_bwd_live": (_i, _QKV + _PROBS + [_i] + _T + _GRADS + _DIMS + [_i, _vp] + _WS),      # need_dqkv, eot
+    "mmx_attn_fwd": (_i, _QKV + _MASK + _T + _DIMS + [_vp]),
+    "mmx_attn_fwd_live": (_i, _QKV + _MASK + _T + _DIMS + [_vp, _vp]),
     "mmx_patch_ranks": (_i, [_vp, _vp, _i, _i, _vp]),
     "mmx_perturb_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mmx_perturb_patches": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mmx_selfattn_perturb_regions": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i, _i64, _i, _vp]),
     "mmx_selfattn_perturb_text": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
-    "mmx_attn_capture_bwd_ex": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64,
-                                     _vp, _vp, _vp, _vp]
-                                + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
-    "mmx_attn_capture_bwd_rowrel": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
-                                         _i64, _vp, _vp, _vp, _vp]
-                                    + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mmx_attn_capture_bwd_ex": (_i, _BWD_EX + _WS),
+    "mmx_attn_capture_bwd_rowrel": (_i, _BWD_EX + [_vp, _vp] + _WS),                              # rel_in, rel_out
     "mmx_attn_capture_bwd_rowrel_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "mmx_attn_capture_bwd_rowrel_f32": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp, _i64,
-                                             _i64, _i64, _vp, _vp, _vp, _vp]
-                                        + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mmx_attn_capture_bwd_rowrel_f32": (_i, _BWD_EX + [_vp, _vp] + _WS),
     "mmx_attn_capture_bwd_rowrel_f32_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "mmx_attn_capture_bwd_rowrel_f32_grouped": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _i, _vp, _i64, _i64, _i64, _vp,
-                                                     _i64, _i64, _i64, _vp, _vp, _vp, _vp]
-                                                + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "mmx_attn_capture_bwd_rowrel_f32_grouped": (_i, _BWD_EX + [_vp, _vp, _i] + _WS),              # rel_in, rel_out, n_images
     "mmx_attn_capture_bwd_rowrel_f32_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mmx_attn_capture_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
-    "mmx_attn_capture_bwd": (_i, [_vp, _vp, _vp] + [_i64] * 9 + [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]
-                             + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
+    "mmx_attn_capture_bwd": (_i, _QKV + _PROBS + _T + _GRADS + _DIMS + [_i] + _WS),
     "mmx_attn_relprop": (_i, [_vp] * 5 + [_i64] * 15 + [_vp] * 5 + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _vp]),
     "mmx_attn_relprop_phase": (_i, [_vp] * 5 + [_i64] * 15 + [_vp] * 5 + [_i64] * 9 + [_i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp]),
     "mmx_detr_decoder_rows_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -1,4 +1,6 @@
-// Argument blocks shared by the tiled (attention_kernels.hip) and whole-head (attention_small.hip) kernels.
+// Argument blocks shared by the tiled (attention_kernels.hip), whole-head (attention_head.hip), streaming (attention_stream.hip)
+// and bf16-MFMA (attention_bf16.hip, attention_bf16_v3.hip) kernels.  The entries of attention_kernels.hip value-initialise one
+// (`AttnBwdArgs a{};`) and fill it once; kernels take it by value, so a new member goes behind the last one.
 #pragma once
 #include "mmx_common.h"
 
@@ -13,7 +15,7 @@ struct AttnFwdArgs {
     float* probs; float* o; Strides os;
     int B, H, Nq, Nk, D;
     float scale; int scale_mode;
-    int debug;  // profiling only (attention_small.hip)
+    int debug;  // profiling only (attention_head.hip); 0 from every entry
     int slab_dt;  // MMX_F32 | MMX_F16 | MMX_BF16: element type behind `probs` (non-fp32: streaming kernels only)
     int mma_bf16; // 1: products on v_mfma_f32_16x16x32_bf16 (operands rounded to bf16, fp32 accumulate, fp32 softmax)
     int tile_skip = 0;  // whole-head kernels: skip the products of key tiles that are masked out for a whole wave (attention_head.hip)

@@ -305,6 +305,41 @@ static int launch_dyn(K kern, const A& args, dim3 grid, size_t lds, hipStream_t 
 
 using namespace mmx;
 
+// ---------------------------------------------------------------------------------------------- host side
+// Every launching entry below: its own refusals, ONE fill of the value-initialised argument struct straight from its parameters
+// (the set_* helpers), one run function (attn_fwd_run / attn_bwd_run: the shared checks in their fixed order, then the dispatch).
+struct Sizes { int B, H, Nq, Nk, D; float scale; int scale_mode; };
+
+template <typename A>   // what AttnFwdArgs and AttnBwdArgs share: q / k / v and the sizes
+static void set_qkv(A& a, const void* q, Strides qs, const void* k, Strides ks, const void* v, Strides vs, const Sizes& n) {
+    a.q = static_cast<const float*>(q); a.k = static_cast<const float*>(k); a.v = static_cast<const float*>(v);
+    a.qs = qs; a.ks = ks; a.vs = vs;
+    a.B = n.B; a.H = n.H; a.Nq = n.Nq; a.Nk = n.Nk; a.D = n.D; a.scale = n.scale; a.scale_mode = n.scale_mode;
+}
+
+static void set_fwd(AttnFwdArgs& a, const void* mask, int64_t mask_sb, int64_t mask_sq, void* probs, int slab_dtype, void* o,
+                    Strides os) {
+    a.mask = static_cast<const float*>(mask); a.mask_sb = mask_sb; a.mask_sq = mask_sq;
+    a.probs = static_cast<float*>(probs); a.o = static_cast<float*>(o); a.os = os;
+    a.mma_bf16 = (slab_dtype & MMX_ATTN_MMA_BF16) ? 1 : 0;
+    a.slab_dt = slab_dtype & ~MMX_ATTN_MMA_BF16;
+}
+
+// o / oos: the forward's output, optional (mmx_attn_capture_bwd_live has none)
+static void set_slabs(AttnBwdArgs& a, const void* probs, int64_t probs_sb, const void* dout, Strides os, void* dprobs, const void* o,
+                      Strides oos) {
+    a.probs = static_cast<const float*>(probs); a.probs_sb = probs_sb;
+    a.dout = static_cast<const float*>(dout); a.os = os;
+    a.dprobs = static_cast<float*>(dprobs);
+    a.o = static_cast<const float*>(o); a.oos = oos;
+    if (reinterpret_cast<uintptr_t>(o) % 16 || oos.sb % 4 || oos.sh % 4 || oos.sn % 4) a.o = nullptr;   // a hint only
+}
+
+static void set_dqkv(AttnBwdArgs& a, void* dq, Strides dqs, void* dk, Strides dks, void* dv, Strides dvs, int need_dqkv) {
+    a.dq = static_cast<float*>(dq); a.dk = static_cast<float*>(dk); a.dv = static_cast<float*>(dv);
+    a.dqs = dqs; a.dks = dks; a.dvs = dvs; a.need_dqkv = need_dqkv;
+}
+
 static int check_attn_dims(const char* fn, int B, int H, int Nq, int Nk, int D, int scale_mode) {
     MMX_CHECK_ARG(B > 0 && H > 0 && Nq > 0 && Nk > 0 && D > 0, "%s: non-positive size", fn);
     MMX_CHECK_ARG(B <= 65535 && H <= 65535, "%s: B/H exceed the grid limit 65535", fn);
@@ -314,6 +349,40 @@ static int check_attn_dims(const char* fn, int B, int H, int Nq, int Nk, int D, 
         return MMX_ENOTSUP;
     }
     return MMX_OK;
+}
+
+// The forward of every entry.  `fn` is the name the messages use (the capture entries all say mmx_attn_capture_fwd; only the
+// live-shape refusal names the _live entry).  a.no_probs (mmx_attn_fwd[_live], the inference forward): the capture forward's fp32
+// dispatch with the no-slab instantiations.  a.eot (the _live entries): the whole-head kernels' LIVE instantiations or nothing --
+// the other kernels would read every row.
+static int attn_fwd_run(const AttnFwdArgs& a, const char* fn, hipStream_t s) {
+    MMX_CHECK_ARG(a.q && a.k && a.v && (a.probs || a.no_probs) && a.o, "%s: null pointer", fn);
+    MMX_CHECK_ARG(a.slab_dt == MMX_F32 || a.slab_dt == MMX_F16 || a.slab_dt == MMX_BF16, "%s: slab dtype %d", fn, a.slab_dt);
+    int rc = check_attn_dims(fn, a.B, a.H, a.Nq, a.Nk, a.D, a.scale_mode);
+    if (rc) return rc;
+    const bool exact = a.slab_dt == MMX_F32 && !a.mma_bf16;
+    if (a.eot) {
+        if (exact && attn_fwd_head_try(a, s, &rc)) return rc;
+        set_error("%s%s: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels (mmx_attn_live_shape)", fn,
+                  a.no_probs ? "" : "_live", a.Nq, a.Nk, a.D);
+        return MMX_ENOTSUP;
+    }
+    if (!exact) {   // half-precision slabs / bf16 MFMA: the streaming kernels only
+        if (attn_fwd_stream_try(a, s, &rc)) return rc;
+        set_error("%s: fp16 / bf16 capture slabs and MMX_ATTN_MMA_BF16 need head_dim %% 4 == 0 (<= 64) and 16-byte aligned "
+                  "q/k/v views", fn);
+        return MMX_ENOTSUP;
+    }
+    if (attn_fwd_head_try(a, s, &rc)) return rc;    // short sequences: a wave owns 16 query rows, scores in registers
+    if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: K/V streamed, nothing of size Nk on chip
+    const dim3 grid((a.Nq + kTQ - 1) / kTQ, a.H, a.B);
+    const size_t lds = attn_lds_bytes(a.D <= 32 ? 32 : 64, a.Nk);
+    if (a.no_probs) {
+        if (a.D <= 32) return launch_dyn(attn_capture_fwd_kernel<32, true>, a, grid, lds, s, "attn_capture_fwd_kernel<32, nop>");
+        return launch_dyn(attn_capture_fwd_kernel<64, true>, a, grid, lds, s, "attn_capture_fwd_kernel<64, nop>");
+    }
+    if (a.D <= 32) return launch_dyn(attn_capture_fwd_kernel<32>, a, grid, lds, s, "attn_capture_fwd_kernel<32>");
+    return launch_dyn(attn_capture_fwd_kernel<64>, a, grid, lds, s, "attn_capture_fwd_kernel<64>");
 }
 
 extern "C" int mmx_attn_capture_fwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,
@@ -326,56 +395,16 @@ extern "C" int mmx_attn_capture_fwd(const void* q_dev, const void* k_dev, const 
                                    scale_mode, stream);
 }
 
-static int attn_fwd_impl(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
-                                       int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
-                                       int64_t v_sh, int64_t v_sn, const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
-                                       void* probs_dev, int slab_dtype, void* o_dev, int64_t o_sb, int64_t o_sh,
-                                       int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
-                                       void* stream, const void* eot_dev) {
-    MMX_CHECK_ARG(q_dev && k_dev && v_dev && probs_dev && o_dev, "mmx_attn_capture_fwd: null pointer");
-    const int mma_bf16 = (slab_dtype & MMX_ATTN_MMA_BF16) ? 1 : 0;
-    slab_dtype &= ~MMX_ATTN_MMA_BF16;
-    MMX_CHECK_ARG(slab_dtype == MMX_F32 || slab_dtype == MMX_F16 || slab_dtype == MMX_BF16,
-                  "mmx_attn_capture_fwd: slab dtype %d", slab_dtype);
-    int rc = check_attn_dims("mmx_attn_capture_fwd", B, H, Nq, Nk, D, scale_mode);
-    if (rc) return rc;
-    AttnFwdArgs a;
-    a.q = static_cast<const float*>(q_dev); a.k = static_cast<const float*>(k_dev); a.v = static_cast<const float*>(v_dev);
-    a.qs = {q_sb, q_sh, q_sn}; a.ks = {k_sb, k_sh, k_sn}; a.vs = {v_sb, v_sh, v_sn};
-    a.mask = static_cast<const float*>(mask_dev); a.mask_sb = mask_sb; a.mask_sq = mask_sq;
-    a.probs = static_cast<float*>(probs_dev); a.o = static_cast<float*>(o_dev); a.os = {o_sb, o_sh, o_sn};
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D; a.scale = scale; a.scale_mode = scale_mode; a.debug = 0;
-    a.slab_dt = slab_dtype;
-    a.mma_bf16 = mma_bf16;
-    dim3 grid((Nq + kTQ - 1) / kTQ, H, B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (eot_dev) {      // live lengths: the whole-head kernels' LIVE instantiations or nothing (the other kernels would read every row)
-        a.eot = static_cast<const long long*>(eot_dev);
-        if (slab_dtype == MMX_F32 && !mma_bf16 && attn_fwd_head_try(a, s, &rc)) return rc;
-        set_error("mmx_attn_capture_fwd_live: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels "
-                  "(mmx_attn_live_shape)", Nq, Nk, D);
-        return MMX_ENOTSUP;
-    }
-    if (slab_dtype != MMX_F32 || mma_bf16) {   // half-precision slabs / bf16 MFMA: the streaming kernels only
-        if (attn_fwd_stream_try(a, s, &rc)) return rc;
-        set_error("mmx_attn_capture_fwd: fp16 / bf16 capture slabs and MMX_ATTN_MMA_BF16 need head_dim %% 4 == 0 "
-                  "(<= 64) and 16-byte aligned q/k/v views");
-        return MMX_ENOTSUP;
-    }
-    if (attn_fwd_head_try(a, s, &rc)) return rc;    // short sequences: a wave owns 16 query rows, scores in registers
-    if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: K/V streamed, nothing of size Nk on chip
-    if (D <= 32) return launch_dyn(attn_capture_fwd_kernel<32>, a, grid, attn_lds_bytes(32, Nk), s, "attn_capture_fwd_kernel<32>");
-    return launch_dyn(attn_capture_fwd_kernel<64>, a, grid, attn_lds_bytes(64, Nk), s, "attn_capture_fwd_kernel<64>");
-}
-
 extern "C" int mmx_attn_capture_fwd_ex(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
                                        int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
                                        int64_t v_sh, int64_t v_sn, const void* mask_dev, int64_t mask_sb, int64_t mask_sq,
                                        void* probs_dev, int slab_dtype, void* o_dev, int64_t o_sb, int64_t o_sh,
                                        int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
                                        void* stream) {
-    return attn_fwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev, mask_sb, mask_sq,
-                         probs_dev, slab_dtype, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, stream, nullptr);
+    AttnFwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_fwd(a, mask_dev, mask_sb, mask_sq, probs_dev, slab_dtype, o_dev, {o_sb, o_sh, o_sn});
+    return attn_fwd_run(a, "mmx_attn_capture_fwd", static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmx_attn_live_shape(int Nq, int Nk, int D) {
@@ -395,50 +424,23 @@ extern "C" int mmx_attn_capture_fwd_live(const void* q_dev, const void* k_dev, c
                                          int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode,
                                          const void* eot_dev, void* stream) {
     MMX_CHECK_ARG(eot_dev && mask_dev, "mmx_attn_capture_fwd_live: null eot / mask (the lengths stand on a causal mask)");
-    return attn_fwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev, mask_sb, mask_sq,
-                         probs_dev, slab_dtype, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, stream, eot_dev);
+    AttnFwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_fwd(a, mask_dev, mask_sb, mask_sq, probs_dev, slab_dtype, o_dev, {o_sb, o_sh, o_sn});
+    a.eot = static_cast<const long long*>(eot_dev);
+    return attn_fwd_run(a, "mmx_attn_capture_fwd", static_cast<hipStream_t>(stream));
 }
 
-// The inference forward: the capture forward's fp32 dispatch with the no-slab instantiations.  eot_dev: live lengths
-// (mmx_attn_fwd_live): the whole-head kernels' LIVE instantiations or nothing -- the other kernels would read every row.
-static int attn_fwd_nop_impl(const char* fn, const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,
-                             int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
-                             const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
-                             int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, const void* eot_dev,
-                             void* stream) {
-    MMX_CHECK_ARG(q_dev && k_dev && v_dev && o_dev, "%s: null pointer", fn);
-    int rc = check_attn_dims(fn, B, H, Nq, Nk, D, scale_mode);
-    if (rc) return rc;
-    AttnFwdArgs a;
-    a.q = static_cast<const float*>(q_dev); a.k = static_cast<const float*>(k_dev); a.v = static_cast<const float*>(v_dev);
-    a.qs = {q_sb, q_sh, q_sn}; a.ks = {k_sb, k_sh, k_sn}; a.vs = {v_sb, v_sh, v_sn};
-    a.mask = static_cast<const float*>(mask_dev); a.mask_sb = mask_sb; a.mask_sq = mask_sq;
-    a.probs = nullptr; a.o = static_cast<float*>(o_dev); a.os = {o_sb, o_sh, o_sn};
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D; a.scale = scale; a.scale_mode = scale_mode; a.debug = 0;
-    a.slab_dt = MMX_F32;
-    a.mma_bf16 = 0;
-    a.no_probs = 1;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (eot_dev) {
-        a.eot = static_cast<const long long*>(eot_dev);
-        if (attn_fwd_head_try(a, s, &rc)) return rc;
-        set_error("%s: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels (mmx_attn_live_shape)", fn, Nq, Nk, D);
-        return MMX_ENOTSUP;
-    }
-    if (attn_fwd_head_try(a, s, &rc)) return rc;    // the whole-head kernel wherever the capture forward picks it
-    if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: one sweep with a running maximum
-    dim3 grid((Nq + kTQ - 1) / kTQ, H, B);
-    if (D <= 32)
-        return launch_dyn(attn_capture_fwd_kernel<32, true>, a, grid, attn_lds_bytes(32, Nk), s, "attn_capture_fwd_kernel<32, nop>");
-    return launch_dyn(attn_capture_fwd_kernel<64, true>, a, grid, attn_lds_bytes(64, Nk), s, "attn_capture_fwd_kernel<64, nop>");
-}
-
+// The inference forward: no capture slab.
 extern "C" int mmx_attn_fwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh, int64_t q_sn,
                             int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh, int64_t v_sn,
                             const void* mask_dev, int64_t mask_sb, int64_t mask_sq, void* o_dev, int64_t o_sb, int64_t o_sh,
                             int64_t o_sn, int B, int H, int Nq, int Nk, int D, float scale, int scale_mode, void* stream) {
-    return attn_fwd_nop_impl("mmx_attn_fwd", q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev,
-                             mask_sb, mask_sq, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, nullptr, stream);
+    AttnFwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_fwd(a, mask_dev, mask_sb, mask_sq, nullptr, MMX_F32, o_dev, {o_sb, o_sh, o_sn});
+    a.no_probs = 1;
+    return attn_fwd_run(a, "mmx_attn_fwd", static_cast<hipStream_t>(stream));
 }
 
 // mmx_attn_fwd with a live length per sample (AttnFwdArgs::eot): the no-slab forward of a causally masked self-attention whose rows
@@ -450,26 +452,16 @@ extern "C" int mmx_attn_fwd_live(const void* q_dev, const void* k_dev, const voi
                                  const void* eot_dev, void* stream) {
     MMX_CHECK_ARG(eot_dev && mask_dev, "mmx_attn_fwd_live: null eot / mask (the lengths stand on a causal mask)");
     MMX_CHECK_ARG(Nq == Nk, "mmx_attn_fwd_live: a self-attention is expected, got Nq=%d Nk=%d", Nq, Nk);
-    return attn_fwd_nop_impl("mmx_attn_fwd_live", q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, mask_dev,
-                             mask_sb, mask_sq, o_dev, o_sb, o_sh, o_sn, B, H, Nq, Nk, D, scale, scale_mode, eot_dev, stream);
+    AttnFwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_fwd(a, mask_dev, mask_sb, mask_sq, nullptr, MMX_F32, o_dev, {o_sb, o_sh, o_sn});
+    a.no_probs = 1;
+    a.eot = static_cast<const long long*>(eot_dev);
+    return attn_fwd_run(a, "mmx_attn_fwd_live", static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t mmx_attn_capture_bwd_workspace_bytes(int B, int H, int Nq) {
     return sizeof(float) * static_cast<size_t>(B) * H * Nq;
-}
-
-extern "C" int mmx_attn_capture_bwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,
-                                    int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh,
-                                    int64_t v_sn, const void* probs_dev, int64_t probs_sb, const void* do_dev, int64_t o_sb, int64_t o_sh,
-                                    int64_t o_sn, void* dprobs_dev, void* dq_dev, void* dk_dev, void* dv_dev,
-                                    int64_t dq_sb, int64_t dq_sh, int64_t dq_sn, int64_t dk_sb, int64_t dk_sh,
-                                    int64_t dk_sn, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq,
-                                    int Nk, int D, float scale, int scale_mode, int need_dqkv, void* workspace_dev,
-                                    size_t workspace_bytes, void* stream) {
-    return mmx_attn_capture_bwd_ex(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev,
-                                   probs_sb, MMX_F32, do_dev, o_sb, o_sh, o_sn, nullptr, 0, 0, 0, dprobs_dev, dq_dev, dk_dev, dv_dev, dq_sb,
-                                   dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
-                                   scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream);
 }
 
 namespace mmx {
@@ -486,9 +478,7 @@ __global__ __launch_bounds__(256) void rel_row_update_kernel(const float* __rest
     v_out[b * N + k] = v_in[b * N + k] + sum * inv_h;
 }
 }  // namespace
-}  // namespace mmx
 
-namespace mmx {
 int rel_row_update(const float* v_in, const float* part, float* out, int B, int J, int N, float inv_h, hipStream_t s) {
     rel_row_update_kernel<<<dim3((N + 255) / 256, B), 256, 0, s>>>(v_in, part, out, J, N, inv_h);
     MMX_LAUNCH_CHECK("rel_row_update_kernel");
@@ -520,125 +510,115 @@ extern "C" size_t mmx_attn_capture_bwd_rowrel_workspace_bytes(int B, int H, int 
     return rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk) + mmx::attn_bwd_bf16_v3_prep_bytes(H, Nk);
 }
 
-static int attn_bwd_impl(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
-                                       int64_t q_sh, int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb,
-                                       int64_t v_sh, int64_t v_sn, const void* probs_dev, int64_t probs_sb, int slab_dtype,
-                                       const void* do_dev, int64_t o_sb, int64_t o_sh, int64_t o_sn, const void* fwd_o_dev,
-                                       int64_t fo_sb, int64_t fo_sh, int64_t fo_sn, void* dprobs_dev,
-                                       void* dq_dev, void* dk_dev, void* dv_dev, int64_t dq_sb, int64_t dq_sh,
-                                       int64_t dq_sn, int64_t dk_sb, int64_t dk_sh, int64_t dk_sn, int64_t dv_sb,
-                                       int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D, float scale,
-                                       int scale_mode, int need_dqkv, void* workspace_dev, size_t workspace_bytes,
-                                       void* stream, const void* rel_in_dev, void* rel_out_dev, bool rel_f32 = false,
-                                       int grp_k = 0, const void* eot_dev = nullptr) {
-    const bool rel = rel_in_dev != nullptr;
-    MMX_CHECK_ARG(v_dev && probs_dev && do_dev && (dprobs_dev || rel), "mmx_attn_capture_bwd: null pointer");
-    const int io_bf16 = (slab_dtype & MMX_ATTN_IO_BF16) ? 1 : 0;
+// What a backward entry hands to attn_bwd_run besides the kernel arguments.  A new mode goes here (and, where the kernels read
+// it, into AttnBwdArgs behind the last member), not into a parameter list.
+enum class RowMode { kNone, kBf16, kF32 };   // row-relevancy mode: off, the bf16-MFMA kernels (_rowrel), exact fp32 (_rowrel_f32*)
+struct AttnBwdMode {
+    RowMode row;
+    void* workspace; size_t workspace_bytes;   // delta [| partial relevancy rows [| bf16 operand images]]
+    int slab_dtype;                            // the entry's raw word: MMX_F32 / _F16 / _BF16 | MMX_ATTN_MMA_BF16 | MMX_ATTN_IO_BF16
+};
+
+static int check_bwd_workspace(const char* fn, const AttnBwdMode& m, size_t need) {
+    if (m.workspace && m.workspace_bytes >= need) return MMX_OK;
+    set_error("%s: workspace %zu < %zu", fn, m.workspace_bytes, need);
+    return MMX_EWORKSPACE;
+}
+
+// The backward of every entry: the shared checks in their fixed order (null pointers, row mode and its workspace, slab dtype,
+// sizes, need_dqkv), the members of `a` that follow from the mode record, then the dispatch.
+static int attn_bwd_run(AttnBwdArgs a, const AttnBwdMode& m, hipStream_t s) {
+    const bool rel = m.row != RowMode::kNone;
+    const int B = a.B, H = a.H, Nq = a.Nq, Nk = a.Nk;
+    MMX_CHECK_ARG(a.v && a.probs && a.dout && (a.dprobs || rel), "mmx_attn_capture_bwd: null pointer");
+    const bool rel_f32 = m.row == RowMode::kF32;
+    const char* rel_fn = rel_f32 ? "mmx_attn_capture_bwd_rowrel_f32" : "mmx_attn_capture_bwd_rowrel";
+    int rc;
+    if (rel) {
+        MMX_CHECK_ARG(a.rel_out && Nq == Nk, "%s: needs rel_out and self-attention (Nq == Nk)", rel_fn);
+        if (rel_f32) MMX_CHECK_ARG(m.slab_dtype == MMX_F32, "%s: fp32 slabs and exact-fp32 kernels only (dtype %d)", rel_fn, m.slab_dtype);
+        else MMX_CHECK_ARG(m.slab_dtype & MMX_ATTN_MMA_BF16, "%s: MMX_ATTN_MMA_BF16 kernels only", rel_fn);
+        rc = check_bwd_workspace(rel_fn, m, rel_f32 ? mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk)
+                                                    : mmx_attn_capture_bwd_rowrel_workspace_bytes(B, H, Nq, Nk));
+        if (rc) return rc;
+    }
+    a.mma_bf16 = (m.slab_dtype & MMX_ATTN_MMA_BF16) ? 1 : 0;
     // (MMX_ATTN_IO_BF16 without MMX_ATTN_MMA_BF16: exact-fp32 arithmetic on a bf16 gradient stream -- the whole-head kernels only)
-    if (rel && rel_f32) {
-        MMX_CHECK_ARG(rel_out_dev && Nq == Nk, "mmx_attn_capture_bwd_rowrel_f32: needs rel_out and self-attention (Nq == Nk)");
-        MMX_CHECK_ARG(slab_dtype == MMX_F32, "mmx_attn_capture_bwd_rowrel_f32: fp32 slabs and exact-fp32 kernels only (dtype %d)",
-                      slab_dtype);
-        if (!workspace_dev || workspace_bytes < mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk)) {
-            set_error("mmx_attn_capture_bwd_rowrel_f32: workspace %zu < %zu", workspace_bytes,
-                      mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk));
-            return MMX_EWORKSPACE;
-        }
-    } else if (rel) {
-        MMX_CHECK_ARG(rel_out_dev && Nq == Nk, "mmx_attn_capture_bwd_rowrel: needs rel_out and self-attention (Nq == Nk)");
-        MMX_CHECK_ARG(slab_dtype & MMX_ATTN_MMA_BF16, "mmx_attn_capture_bwd_rowrel: MMX_ATTN_MMA_BF16 kernels only");
-        if (!workspace_dev || workspace_bytes < mmx_attn_capture_bwd_rowrel_workspace_bytes(B, H, Nq, Nk)) {
-            set_error("mmx_attn_capture_bwd_rowrel: workspace %zu < %zu", workspace_bytes,
-                      mmx_attn_capture_bwd_rowrel_workspace_bytes(B, H, Nq, Nk));
-            return MMX_EWORKSPACE;
-        }
-    }
-    const int mma_bf16 = (slab_dtype & MMX_ATTN_MMA_BF16) ? 1 : 0;
-    slab_dtype &= ~(MMX_ATTN_MMA_BF16 | MMX_ATTN_IO_BF16);
-    MMX_CHECK_ARG(slab_dtype == MMX_F32 || slab_dtype == MMX_F16 || slab_dtype == MMX_BF16,
-                  "mmx_attn_capture_bwd: slab dtype %d", slab_dtype);
-    int rc = check_attn_dims("mmx_attn_capture_bwd", B, H, Nq, Nk, D, scale_mode);
+    a.io_bf16 = (m.slab_dtype & MMX_ATTN_IO_BF16) ? 1 : 0;
+    a.slab_dt = m.slab_dtype & ~(MMX_ATTN_MMA_BF16 | MMX_ATTN_IO_BF16);
+    MMX_CHECK_ARG(a.slab_dt == MMX_F32 || a.slab_dt == MMX_F16 || a.slab_dt == MMX_BF16, "mmx_attn_capture_bwd: slab dtype %d",
+                  a.slab_dt);
+    rc = check_attn_dims("mmx_attn_capture_bwd", B, H, Nq, Nk, a.D, a.scale_mode);
     if (rc) return rc;
-    if (need_dqkv) {
-        MMX_CHECK_ARG(q_dev && k_dev && dq_dev && dk_dev && dv_dev, "mmx_attn_capture_bwd: null q/k/dq/dk/dv");
-        if (!workspace_dev || workspace_bytes < mmx_attn_capture_bwd_workspace_bytes(B, H, Nq)) {
-            set_error("mmx_attn_capture_bwd: workspace %zu < %zu", workspace_bytes,
-                      mmx_attn_capture_bwd_workspace_bytes(B, H, Nq));
-            return MMX_EWORKSPACE;
-        }
+    if (a.need_dqkv) {
+        MMX_CHECK_ARG(a.q && a.k && a.dq && a.dk && a.dv, "mmx_attn_capture_bwd: null q/k/dq/dk/dv");
+        rc = check_bwd_workspace("mmx_attn_capture_bwd", m, mmx_attn_capture_bwd_workspace_bytes(B, H, Nq));
+        if (rc) return rc;
     }
-    AttnBwdArgs a;
-    a.q = static_cast<const float*>(q_dev); a.k = static_cast<const float*>(k_dev); a.v = static_cast<const float*>(v_dev);
-    a.qs = {q_sb, q_sh, q_sn}; a.ks = {k_sb, k_sh, k_sn}; a.vs = {v_sb, v_sh, v_sn};
-    a.probs = static_cast<const float*>(probs_dev); a.probs_sb = probs_sb;
-    a.dout = static_cast<const float*>(do_dev); a.os = {o_sb, o_sh, o_sn};
-    a.o = static_cast<const float*>(fwd_o_dev); a.oos = {fo_sb, fo_sh, fo_sn};
-    if (reinterpret_cast<uintptr_t>(fwd_o_dev) % 16 || fo_sb % 4 || fo_sh % 4 || fo_sn % 4) a.o = nullptr;   // a hint only
-    a.dprobs = static_cast<float*>(dprobs_dev);
-    a.dq = static_cast<float*>(dq_dev); a.dk = static_cast<float*>(dk_dev); a.dv = static_cast<float*>(dv_dev);
-    a.dqs = {dq_sb, dq_sh, dq_sn}; a.dks = {dk_sb, dk_sh, dk_sn}; a.dvs = {dv_sb, dv_sh, dv_sn};
-    a.delta = static_cast<float*>(workspace_dev);
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.D = D; a.scale = scale; a.scale_mode = scale_mode; a.need_dqkv = need_dqkv;
-    a.slab_dt = slab_dtype;
-    a.mma_bf16 = mma_bf16;
-    a.io_bf16 = io_bf16;
-    a.rel_v = static_cast<const float*>(rel_in_dev);
-    a.rel_part = rel ? reinterpret_cast<float*>(static_cast<char*>(workspace_dev) + rowrel_delta_bytes(B, H, Nq)) : nullptr;
-    a.rel_out = static_cast<float*>(rel_out_dev);
-    a.grp_k = grp_k;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (eot_dev) {      // live lengths: the whole-head kernels' LIVE instantiations or nothing
-        a.eot = static_cast<const long long*>(eot_dev);
-        if (!rel && slab_dtype == MMX_F32 && !mma_bf16 && !io_bf16 && attn_bwd_head_try(a, s, &rc)) return rc;
+    a.delta = static_cast<float*>(m.workspace);
+    a.rel_part = rel ? reinterpret_cast<float*>(static_cast<char*>(m.workspace) + rowrel_delta_bytes(B, H, Nq)) : nullptr;
+    const bool exact = a.slab_dt == MMX_F32 && !a.mma_bf16;
+    if (a.eot) {      // live lengths: the whole-head kernels' LIVE instantiations or nothing
+        if (!rel && exact && !a.io_bf16 && attn_bwd_head_try(a, s, &rc)) return rc;
         set_error("mmx_attn_capture_bwd_live: Nq=%d Nk=%d D=%d is not served by the live-length whole-head kernels "
-                  "(mmx_attn_live_shape)", Nq, Nk, D);
+                  "(mmx_attn_live_shape)", Nq, Nk, a.D);
         return MMX_ENOTSUP;
     }
-    if (rel && rel_f32) {
-        if (attn_bwd_head_try(a, s, &rc)) return rc;    // N <= 128: one partial row per head
-        // the exact-fp32 key-side streaming kernel reads dP back from the slab (the row is extra work, not another schedule)
-        MMX_CHECK_ARG(dprobs_dev || !need_dqkv, "mmx_attn_capture_bwd_rowrel_f32: this shape runs the streaming kernels, whose "
-                      "key side reads dP back: need_dqkv needs a dprobs slab");
-        if (!attn_bwd_stream_try(a, s, &rc)) {
-            set_error("mmx_attn_capture_bwd_rowrel_f32: needs head_dim %% 4 == 0 (<= 64) and 16-byte aligned views");
-            return MMX_ENOTSUP;
-        }
-        return rc;      // (the path that ran has also launched rel_row_update over the partial rows it made)
-    }
     if (rel) {
-        const size_t used = rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk);
-        if (attn_bwd_bf16_v3_try(a, static_cast<char*>(workspace_dev) + used, workspace_bytes - used, s, &rc)) return rc;
+        const size_t used = rowrel_delta_bytes(B, H, Nq) + rowrel_part_bytes(B, H, Nq, Nk);   // bf16: the operand images lie behind
+        if (rel_f32) {
+            if (attn_bwd_head_try(a, s, &rc)) return rc;    // N <= 128: one partial row per head
+            // the exact-fp32 key-side streaming kernel reads dP back from the slab (the row is extra work, not another schedule)
+            MMX_CHECK_ARG(a.dprobs || !a.need_dqkv, "mmx_attn_capture_bwd_rowrel_f32: this shape runs the streaming kernels, whose "
+                          "key side reads dP back: need_dqkv needs a dprobs slab");
+        } else if (attn_bwd_bf16_v3_try(a, static_cast<char*>(m.workspace) + used, m.workspace_bytes - used, s, &rc)) {
+            return rc;
+        }
         if (!attn_bwd_stream_try(a, s, &rc)) {
-            set_error("mmx_attn_capture_bwd_rowrel: needs head_dim %% 4 == 0 (<= 64) and 16-byte aligned views");
+            set_error("%s: needs head_dim %% 4 == 0 (<= 64) and 16-byte aligned views", rel_fn);
             return MMX_ENOTSUP;
         }
         return rc;      // (the path that ran has also launched rel_row_update over the partial rows it made)
     }
-    if (slab_dtype != MMX_F32 || mma_bf16) {
+    if (!exact) {
         if (attn_bwd_stream_try(a, s, &rc)) return rc;
         set_error("mmx_attn_capture_bwd: fp16 / bf16 capture slabs and MMX_ATTN_MMA_BF16 need head_dim %% 4 == 0 "
                   "(<= 64) and 16-byte aligned views");
         return MMX_ENOTSUP;
     }
     if (attn_bwd_head_try(a, s, &rc)) return rc;    // short sequences: a wave owns 16 query rows, scores in registers
-    if (io_bf16) {
+    if (a.io_bf16) {
         set_error("mmx_attn_capture_bwd: MMX_ATTN_IO_BF16 without MMX_ATTN_MMA_BF16 is served by the whole-head kernels only "
                   "(fp32 slabs, Nk <= 128, Nq <= 256, head_dim %% 4 == 0 and <= 64, 8-byte aligned gradient rows)");
         return MMX_ENOTSUP;
     }
     if (attn_bwd_stream_try(a, s, &rc)) return rc;  // long sequences
-    dim3 gq((Nq + kTQ - 1) / kTQ, H, B), gk((Nk + 15) / 16, H, B);
-    if (D <= 32) {
+    const dim3 gq((Nq + kTQ - 1) / kTQ, H, B), gk((Nk + 15) / 16, H, B);
+    if (a.D <= 32) {
         rc = launch_dyn(attn_capture_bwd_q_kernel<32>, a, gq, attn_lds_bytes(32, Nk), s, "attn_capture_bwd_q_kernel<32>");
-        if (rc || !need_dqkv) return rc;
+        if (rc || !a.need_dqkv) return rc;
         attn_capture_bwd_kv_kernel<32><<<gk, 256, 0, s>>>(a);
     } else {
         rc = launch_dyn(attn_capture_bwd_q_kernel<64>, a, gq, attn_lds_bytes(64, Nk), s, "attn_capture_bwd_q_kernel<64>");
-        if (rc || !need_dqkv) return rc;
+        if (rc || !a.need_dqkv) return rc;
         attn_capture_bwd_kv_kernel<64><<<gk, 256, 0, s>>>(a);
     }
     MMX_LAUNCH_CHECK("attn_capture_bwd_kv_kernel");
     return MMX_OK;
+}
+
+extern "C" int mmx_attn_capture_bwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,
+                                    int64_t q_sn, int64_t k_sb, int64_t k_sh, int64_t k_sn, int64_t v_sb, int64_t v_sh,
+                                    int64_t v_sn, const void* probs_dev, int64_t probs_sb, const void* do_dev, int64_t o_sb, int64_t o_sh,
+                                    int64_t o_sn, void* dprobs_dev, void* dq_dev, void* dk_dev, void* dv_dev,
+                                    int64_t dq_sb, int64_t dq_sh, int64_t dq_sn, int64_t dk_sb, int64_t dk_sh,
+                                    int64_t dk_sn, int64_t dv_sb, int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq,
+                                    int Nk, int D, float scale, int scale_mode, int need_dqkv, void* workspace_dev,
+                                    size_t workspace_bytes, void* stream) {
+    return mmx_attn_capture_bwd_ex(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev,
+                                   probs_sb, MMX_F32, do_dev, o_sb, o_sh, o_sn, nullptr, 0, 0, 0, dprobs_dev, dq_dev, dk_dev, dv_dev, dq_sb,
+                                   dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
+                                   scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream);
 }
 
 extern "C" int mmx_attn_capture_bwd_ex(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
@@ -651,10 +631,11 @@ extern "C" int mmx_attn_capture_bwd_ex(const void* q_dev, const void* k_dev, con
                                        int64_t dv_sh, int64_t dv_sn, int B, int H, int Nq, int Nk, int D, float scale,
                                        int scale_mode, int need_dqkv, void* workspace_dev, size_t workspace_bytes,
                                        void* stream) {
-    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
-                         slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
-                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
-                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, nullptr, nullptr);
+    AttnBwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_slabs(a, probs_dev, probs_sb, do_dev, {o_sb, o_sh, o_sn}, dprobs_dev, fwd_o_dev, {fo_sb, fo_sh, fo_sn});
+    set_dqkv(a, dq_dev, {dq_sb, dq_sh, dq_sn}, dk_dev, {dk_sb, dk_sh, dk_sn}, dv_dev, {dv_sb, dv_sh, dv_sn}, need_dqkv);
+    return attn_bwd_run(a, {RowMode::kNone, workspace_dev, workspace_bytes, slab_dtype}, static_cast<hipStream_t>(stream));
 }
 
 // mmx_attn_capture_bwd_ex with a live length per sample (AttnBwdArgs::eot), the backward of mmx_attn_capture_fwd_live: rows past
@@ -669,10 +650,12 @@ extern "C" int mmx_attn_capture_bwd_live(const void* q_dev, const void* k_dev, c
                                          int scale_mode, int need_dqkv, const void* eot_dev, void* workspace_dev,
                                          size_t workspace_bytes, void* stream) {
     MMX_CHECK_ARG(eot_dev, "mmx_attn_capture_bwd_live: null eot");
-    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
-                         slab_dtype, do_dev, o_sb, o_sh, o_sn, nullptr, 0, 0, 0, dprobs_dev, dq_dev, dk_dev,
-                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
-                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, nullptr, nullptr, false, 0, eot_dev);
+    AttnBwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_slabs(a, probs_dev, probs_sb, do_dev, {o_sb, o_sh, o_sn}, dprobs_dev, nullptr, {});
+    set_dqkv(a, dq_dev, {dq_sb, dq_sh, dq_sn}, dk_dev, {dk_sb, dk_sh, dk_sn}, dv_dev, {dv_sb, dv_sh, dv_sn}, need_dqkv);
+    a.eot = static_cast<const long long*>(eot_dev);
+    return attn_bwd_run(a, {RowMode::kNone, workspace_dev, workspace_bytes, slab_dtype}, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmx_attn_capture_bwd_rowrel(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
@@ -687,10 +670,12 @@ extern "C" int mmx_attn_capture_bwd_rowrel(const void* q_dev, const void* k_dev,
                                            int need_dqkv, const void* rel_in_dev, void* rel_out_dev,
                                            void* workspace_dev, size_t workspace_bytes, void* stream) {
     MMX_CHECK_ARG(rel_in_dev && rel_out_dev, "mmx_attn_capture_bwd_rowrel: null relevancy row");
-    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
-                         slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
-                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
-                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev);
+    AttnBwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_slabs(a, probs_dev, probs_sb, do_dev, {o_sb, o_sh, o_sn}, dprobs_dev, fwd_o_dev, {fo_sb, fo_sh, fo_sn});
+    set_dqkv(a, dq_dev, {dq_sb, dq_sh, dq_sn}, dk_dev, {dk_sb, dk_sh, dk_sn}, dv_dev, {dv_sb, dv_sh, dv_sn}, need_dqkv);
+    a.rel_v = static_cast<const float*>(rel_in_dev); a.rel_out = static_cast<float*>(rel_out_dev);
+    return attn_bwd_run(a, {RowMode::kBf16, workspace_dev, workspace_bytes, slab_dtype}, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmx_attn_capture_bwd_rowrel_f32(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
@@ -705,10 +690,12 @@ extern "C" int mmx_attn_capture_bwd_rowrel_f32(const void* q_dev, const void* k_
                                                int need_dqkv, const void* rel_in_dev, void* rel_out_dev,
                                                void* workspace_dev, size_t workspace_bytes, void* stream) {
     MMX_CHECK_ARG(rel_in_dev && rel_out_dev, "mmx_attn_capture_bwd_rowrel_f32: null relevancy row");
-    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
-                         slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
-                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
-                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev, true);
+    AttnBwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_slabs(a, probs_dev, probs_sb, do_dev, {o_sb, o_sh, o_sn}, dprobs_dev, fwd_o_dev, {fo_sb, fo_sh, fo_sn});
+    set_dqkv(a, dq_dev, {dq_sb, dq_sh, dq_sn}, dk_dev, {dk_sb, dk_sh, dk_sn}, dv_dev, {dv_sb, dv_sh, dv_sn}, need_dqkv);
+    a.rel_v = static_cast<const float*>(rel_in_dev); a.rel_out = static_cast<float*>(rel_out_dev);
+    return attn_bwd_run(a, {RowMode::kF32, workspace_dev, workspace_bytes, slab_dtype}, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmx_attn_capture_bwd_rowrel_f32_grouped(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb,
@@ -727,10 +714,11 @@ extern "C" int mmx_attn_capture_bwd_rowrel_f32_grouped(const void* q_dev, const 
     MMX_CHECK_ARG(n_images >= 1 && B >= 1 && B % n_images == 0,
                   "mmx_attn_capture_bwd_rowrel_f32_grouped: %d targets are not a whole number per image over %d images", B,
                   n_images);
-    // one target per image: the per-sample mode itself (same kernels, same order)
-    const int grp_k = B / n_images > 1 ? B / n_images : 0;
-    return attn_bwd_impl(q_dev, k_dev, v_dev, q_sb, q_sh, q_sn, k_sb, k_sh, k_sn, v_sb, v_sh, v_sn, probs_dev, probs_sb,
-                         slab_dtype, do_dev, o_sb, o_sh, o_sn, fwd_o_dev, fo_sb, fo_sh, fo_sn, dprobs_dev, dq_dev, dk_dev,
-                         dv_dev, dq_sb, dq_sh, dq_sn, dk_sb, dk_sh, dk_sn, dv_sb, dv_sh, dv_sn, B, H, Nq, Nk, D, scale,
-                         scale_mode, need_dqkv, workspace_dev, workspace_bytes, stream, rel_in_dev, rel_out_dev, true, grp_k);
+    AttnBwdArgs a{};
+    set_qkv(a, q_dev, {q_sb, q_sh, q_sn}, k_dev, {k_sb, k_sh, k_sn}, v_dev, {v_sb, v_sh, v_sn}, {B, H, Nq, Nk, D, scale, scale_mode});
+    set_slabs(a, probs_dev, probs_sb, do_dev, {o_sb, o_sh, o_sn}, dprobs_dev, fwd_o_dev, {fo_sb, fo_sh, fo_sn});
+    set_dqkv(a, dq_dev, {dq_sb, dq_sh, dq_sn}, dk_dev, {dk_sb, dk_sh, dk_sn}, dv_dev, {dv_sb, dv_sh, dv_sn}, need_dqkv);
+    a.rel_v = static_cast<const float*>(rel_in_dev); a.rel_out = static_cast<float*>(rel_out_dev);
+    a.grp_k = B / n_images > 1 ? B / n_images : 0;   // one target per image: the per-sample mode itself (same kernels, same order)
+    return attn_bwd_run(a, {RowMode::kF32, workspace_dev, workspace_bytes, slab_dtype}, static_cast<hipStream_t>(stream));
 }

@@ -1254,14 +1254,46 @@ def rollout_chain(layers, normalize):
 
 # ------------------------------------------------------------------------------------------- attention capture
 def _bhnd_strides(t, layout):
-    """Element strides (batch, head, token) of a ``[B, N, H, D]``-viewable tensor with contiguous D."""
-    if t.stride(-1) != 1:
+    """Element strides (batch, head, token) of a ``[B, N, H, D]``-viewable tensor with contiguous D; ``(0, 0, 0)`` for ``None``."""
+    if t is None:
+        return 0, 0, 0
+    s = t.stride()                                   # one walk per operand: these run on every eager call
+    if s[-1] != 1:
         raise MMXError("attention operands need a contiguous head_dim")
     if layout == "bnhd":
-        return t.stride(0), t.stride(2), t.stride(1)
+        return s[0], s[2], s[1]
     if layout == "bhnd":
-        return t.stride(0), t.stride(1), t.stride(2)
+        return s[0], s[1], s[2]
     raise MMXError("layout %r" % layout)
+
+
+def _attn_dims(q, k, layout):
+    """``(B, H, Nq, Nk, D)`` of the operands ``q`` and ``k`` in ``layout``."""
+    if layout == "bnhd":
+        B, Nq, H, D = q.shape
+        return B, H, Nq, k.shape[1], D
+    if layout == "bhnd":
+        B, H, Nq, D = q.shape
+        return B, H, Nq, k.shape[2], D
+    raise MMXError("layout %r" % layout)
+
+
+def _strided(t, layout):
+    """``(pointer, batch stride, head stride, token stride)`` of an optional operand: a null pointer and zeros for ``None``."""
+    return (_p(t), *_bhnd_strides(t, layout))
+
+
+def _qkv_args(q, k, v, layout):
+    """The prefix of every attention entry: the three pointers, then the three stride triples (of ``None`` s: nulls and zeros)."""
+    return (_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout))
+
+
+def _attn_bwd_args(layout, qkv, probs, probs_sb, slab_dtype, d_o, o, dprobs, grads, dims, scale, scale_mode, need_dqkv):
+    """The operand block every backward entry starts with, up to ``need_dqkv``: ``qkv`` / ``grads`` are ``(q, k, v)`` / ``(dq, dk,
+    dv)`` (``None`` s without ``need_dqkv``), ``dims`` is ``(B, H, Nq, Nk, D)``; ``o=False``: the entry takes no forward output."""
+    return (*_qkv_args(*qkv, layout), _p(probs), probs_sb, slab_dtype, _p(d_o), *_bhnd_strides(d_o, layout),
+            *(() if o is False else _strided(o, layout)), _p(dprobs), *_qkv_args(*grads, layout), *dims, float(scale), scale_mode,
+            int(need_dqkv))
 
 
 def _mask_strides(mask, Nk):
@@ -1289,12 +1321,7 @@ def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, m
     _dev(q, k, v, probs_out, mask, out)
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
         raise MMXError("attention capture op is fp32 in this ABI version")
-    if layout == "bnhd":
-        B, Nq, H, D = q.shape
-        Nk = k.shape[1]
-    else:
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
+    B, H, Nq, Nk, D = _attn_dims(q, k, layout)
     if probs_out.dtype not in _DTYPES or not probs_out.is_contiguous() or probs_out.numel() != B * H * Nq * Nk:
         raise MMXError("probs_out must be a contiguous fp32 / fp16 / bf16 [B,H,Nq,Nk] slab")
     if out is not None and (out.dtype != torch.float32 or out.shape != q.shape):
@@ -1305,17 +1332,15 @@ def attn_capture_fwd(q, k, v, probs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, m
         if mask is None or mma_bf16:
             raise MMXError("attn_capture_fwd: live= stands on a causal mask and the exact-fp32 kernels")
         o = out if out is not None else live._out(q, D)
-        check(lib().mmx_attn_capture_fwd_live(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
-                                              *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(probs_out), _DTYPES[probs_out.dtype],
-                                              _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
+        check(lib().mmx_attn_capture_fwd_live(*_qkv_args(q, k, v, layout), _p(mask), msb, msq, _p(probs_out), _DTYPES[probs_out.dtype],
+                                              *_strided(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
                                               _p(live.eot), _stream()), "mmx_attn_capture_fwd_live")
         return o
     o = out if out is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    check(lib().mmx_attn_capture_fwd_ex(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
-                                        *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(probs_out),
+    check(lib().mmx_attn_capture_fwd_ex(*_qkv_args(q, k, v, layout), _p(mask), msb, msq, _p(probs_out),
                                         _DTYPES[probs_out.dtype] | (_lib.MMX_ATTN_MMA_BF16 if mma_bf16 else 0),
-                                        _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D,
-                                        float(scale), scale_mode, _stream()), "mmx_attn_capture_fwd")
+                                        *_strided(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode, _stream()),
+          "mmx_attn_capture_fwd")
     return o
 
 
@@ -1331,12 +1356,7 @@ def attn_fwd(q, k, v, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="b
     _dev(q, k, v, mask, out)
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
         raise MMXError("attn_fwd is exact fp32 (no bf16 / fp16 mode yet), got %s" % str(q.dtype).replace("torch.", ""))
-    if layout == "bnhd":
-        B, Nq, H, D = q.shape
-        Nk = k.shape[1]
-    else:
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
+    B, H, Nq, Nk, D = _attn_dims(q, k, layout)
     if out is not None and (out.dtype != torch.float32 or out.shape != q.shape):
         raise MMXError("attn_fwd: out must be fp32 of q's shape %s" % (tuple(q.shape),))
     mask, msb, msq = _mask_strides(mask, Nk)
@@ -1345,14 +1365,12 @@ def attn_fwd(q, k, v, scale, scale_mode=_lib.SCALE_Q_FIRST, mask=None, layout="b
         if mask is None:
             raise MMXError("attn_fwd: live= stands on a causal mask")
         o = out if out is not None else live._out(q, D)
-        check(lib().mmx_attn_fwd_live(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout),
-                                      *_bhnd_strides(v, layout), _p(mask), msb, msq, _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk,
-                                      D, float(scale), scale_mode, _p(live.eot), _stream()), "mmx_attn_fwd_live")
+        check(lib().mmx_attn_fwd_live(*_qkv_args(q, k, v, layout), _p(mask), msb, msq, *_strided(o, layout), B, H, Nq, Nk, D,
+                                      float(scale), scale_mode, _p(live.eot), _stream()), "mmx_attn_fwd_live")
         return o
     o = out if out is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    check(lib().mmx_attn_fwd(_p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
-                             _p(mask), msb, msq, _p(o), *_bhnd_strides(o, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
-                             _stream()), "mmx_attn_fwd")
+    check(lib().mmx_attn_fwd(*_qkv_args(q, k, v, layout), _p(mask), msb, msq, *_strided(o, layout), B, H, Nq, Nk, D, float(scale),
+                             scale_mode, _stream()), "mmx_attn_fwd")
     return o
 
 
@@ -1524,17 +1542,12 @@ def head_kernel_shape(n_q, n_k, head_dim, slab_dtype=torch.float32):
     return lds <= 160 * 1024 and not (ntk >= 7 and ntq > 8)
 
 
-def _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode, need_dqkv, layout, out, o, mma_bf16,
-                              rel_row, images):
-    """``attn_capture_bwd(images=M)``: the grouped row mode (per-image forward operands, per-target everything else)."""
+def _attn_capture_bwd_grouped(q, k, probs, d_o, dprobs_out, layout, mma_bf16, rel_row, images):
+    """The refusals of ``attn_capture_bwd(images=M)``, the grouped row mode (per-image forward operands, per-target everything
+    else); the call itself is the exact-fp32 ``rel_row`` branch's, over the ``T`` targets."""
     if rel_row is None or mma_bf16:
         raise MMXError("attn_capture_bwd: images= is the grouped exact-fp32 row mode: it needs rel_row and mma_bf16=False")
-    if layout == "bnhd":
-        M, Nq, H, D = q.shape
-        Nk = k.shape[1]
-    else:
-        M, H, Nq, D = q.shape
-        Nk = k.shape[2]
+    M, _H, Nq, Nk, _D = _attn_dims(q, k, layout)
     T = d_o.shape[0]
     if images != M or probs.shape[0] != M or images < 1 or T % images:
         raise MMXError("attn_capture_bwd: images=%d needs q/k/v/probs of batch %d and a d_o batch that is a multiple of it "
@@ -1545,35 +1558,9 @@ def _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode
         raise MMXError("attn_capture_bwd: grouped rel_row needs an fp32 d_o")
     if dprobs_out is not None and (dprobs_out.dtype != torch.float32 or dprobs_out.shape[0] != T):
         raise MMXError("attn_capture_bwd: grouped dprobs_out must be fp32 with batch %d" % T)
-    if d_o.stride(-1) != 1:
-        d_o = d_o.contiguous()
     if probs.stride(-1) != 1 or not probs.is_contiguous():
         raise MMXError("attn_capture_bwd: grouped probs must be a contiguous [M, H, N, N] slab")
-    dq = dk = dv = None
-    zero3 = (0, 0, 0)
-    if need_dqkv:
-        if out is not None:
-            dq, dk, dv = out
-        else:
-            dq, dk, dv = (torch.empty((T,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device) for t in (q, k, v))
-    if o is not None and (o.dtype != torch.float32 or o.stride(-1) != 1):
-        o = None                                               # only a hint: fall back to the two-sweep form
-    rel_row = rel_row.contiguous()
-    rel_out = torch.empty_like(rel_row)
-    dprobs = dprobs_out
-    if dprobs is None and need_dqkv and not head_kernel_shape(Nq, Nk, D, probs.dtype):
-        dprobs = _workspace(4 * T * H * Nq * Nk, q.device, "attn_rowrel_dp").view(torch.float32)
-    need = lib().mmx_attn_capture_bwd_rowrel_f32_grouped_workspace_bytes(T, H, Nq, Nk)
-    ws = _workspace(need, q.device, "attn_bwd")
-    check(lib().mmx_attn_capture_bwd_rowrel_f32_grouped(
-        _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
-        _p(probs), H * Nq * Nk, _DTYPES[probs.dtype], _p(d_o), *_bhnd_strides(d_o, layout),
-        _p(o), *(_bhnd_strides(o, layout) if o is not None else zero3), _p(dprobs), _p(dq), _p(dk), _p(dv),
-        *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
-        *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
-        T, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(rel_row), _p(rel_out), images, _p(ws), need,
-        _stream()), "mmx_attn_capture_bwd_rowrel_f32_grouped")
-    return dq, dk, dv, rel_out
+    return T
 
 
 def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCALE_Q_FIRST, need_dqkv=True,
@@ -1599,20 +1586,16 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
                              or (batch is not None and batch != q.shape[0]) or d_o.dtype != torch.float32):
         raise MMXError("attn_capture_bwd: live= is the plain fp32 capture backward (a dprobs slab, an fp32 d_o, one forward per "
                        "gradient; no rel_row / images / mma_bf16)")
+    targets = None
     if images is not None:
-        return _attn_capture_bwd_grouped(q, k, v, probs, d_o, dprobs_out, scale, scale_mode, need_dqkv, layout, out, o,
-                                         mma_bf16, rel_row, int(images))
+        images = int(images)
+        targets = _attn_capture_bwd_grouped(q, k, probs, d_o, dprobs_out, layout, mma_bf16, rel_row, images)
     if probs.dtype not in _DTYPES or (dprobs_out is not None and probs.dtype != dprobs_out.dtype):
         raise MMXError("attn_capture_bwd: probs / dprobs slabs must share one of fp32 / fp16 / bf16")
     if dprobs_out is None and rel_row is None:
         raise MMXError("attn_capture_bwd: no dprobs slab (only the row-relevancy mode runs without one)")
-    if layout == "bnhd":
-        B, Nq, H, D = q.shape
-        Nk = k.shape[1]
-    else:
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
-    shared = batch is not None and batch != B
+    B, H, Nq, Nk, D = _attn_dims(q, k, layout)
+    shared = targets is None and batch is not None and batch != B
     if shared:
         if B != 1:
             raise MMXError("shared-forward backward needs batch-1 q/k/v")
@@ -1620,6 +1603,8 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
         q, k, v = (t.expand(B, *t.shape[1:]) for t in (q, k, v))      # stride-0 views, no copy
         if o is not None:
             o = o.expand(B, *o.shape[1:])
+    if targets is not None:
+        B = targets                                  # per target from here on; q / k / v / probs / o keep their batch of images
     probs_sb = 0 if shared else H * Nq * Nk
     if d_o.stride(-1) != 1:
         d_o = d_o.contiguous()
@@ -1635,74 +1620,50 @@ def attn_capture_bwd(q, k, v, probs, d_o, dprobs_out, scale, scale_mode=_lib.SCA
         if out is not None:
             dq, dk, dv = out
         else:
-            dq, dk, dv = (torch.empty(tuple(t.shape), dtype=d_o.dtype, device=t.device) for t in (q, k, v))
-        need = lib().mmx_attn_capture_bwd_workspace_bytes(B, H, Nq)
-        ws = _workspace(need, q.device, "attn_bwd")
-    zero3 = (0, 0, 0)
+            dq, dk, dv = (torch.empty((B,) + tuple(t.shape[1:]), dtype=d_o.dtype, device=t.device) for t in (q, k, v))
+        if rel_row is None:                                    # (the row modes size their own workspace: delta is its first part)
+            need = lib().mmx_attn_capture_bwd_workspace_bytes(B, H, Nq)
+            ws = _workspace(need, q.device, "attn_bwd")
     if o is not None and (o.dtype != torch.float32 or o.stride(-1) != 1):
         o = None                                               # only a hint: fall back to the two-sweep form
-    if rel_row is not None and not mma_bf16:
-        if rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (B, Nq) or Nq != Nk or probs.dtype != torch.float32:
-            raise MMXError("attn_capture_bwd: exact-fp32 rel_row needs fp32 [B, N] rows and fp32 slabs of a self-attention")
-        if io_bf16:
-            raise MMXError("attn_capture_bwd: exact-fp32 rel_row needs an fp32 d_o")
-        rel_row = rel_row.contiguous()
-        rel_out = torch.empty_like(rel_row)
-        dprobs = dprobs_out
-        if dprobs is None and need_dqkv and not head_kernel_shape(Nq, Nk, D, probs.dtype):
-            dprobs = _workspace(4 * B * H * Nq * Nk, q.device, "attn_rowrel_dp").view(torch.float32)
-        need = lib().mmx_attn_capture_bwd_rowrel_f32_workspace_bytes(B, H, Nq, Nk)
-        ws = _workspace(need, q.device, "attn_bwd")
-        check(lib().mmx_attn_capture_bwd_rowrel_f32(
-            _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
-            _p(probs), probs_sb, _DTYPES[probs.dtype], _p(d_o), *_bhnd_strides(d_o, layout),
-            _p(o), *(_bhnd_strides(o, layout) if o is not None else zero3), _p(dprobs), _p(dq), _p(dk), _p(dv),
-            *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
-            *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
-            B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(rel_row), _p(rel_out), _p(ws), need, _stream()),
-            "mmx_attn_capture_bwd_rowrel_f32")
-        return dq, dk, dv, rel_out
+    slab = _DTYPES[probs.dtype]
+
+    def operands(slab_dtype, dprobs, d_o_=d_o, grads=(dq, dk, dv), fwd_o=o):
+        return _attn_bwd_args(layout, (q, k, v), probs, probs_sb, slab_dtype, d_o_, fwd_o, dprobs, grads, (B, H, Nq, Nk, D), scale,
+                              scale_mode, need_dqkv)
     if rel_row is not None:
-        if not mma_bf16 or rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (B, Nq) or Nq != Nk:
-            raise MMXError("attn_capture_bwd: rel_row must be fp32 [B, N] of a self-attention, with mma_bf16=True")
+        if not mma_bf16:
+            if rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (B, Nq) or Nq != Nk or probs.dtype != torch.float32:
+                raise MMXError("attn_capture_bwd: exact-fp32 rel_row needs fp32 [B, N] rows and fp32 slabs of a self-attention")
+            if io_bf16:
+                raise MMXError("attn_capture_bwd: exact-fp32 rel_row needs an fp32 d_o")
+            name, tail, dprobs = "mmx_attn_capture_bwd_rowrel_f32", (), dprobs_out
+            if targets is not None:
+                name, tail = name + "_grouped", (images,)
+            if dprobs is None and need_dqkv and not head_kernel_shape(Nq, Nk, D, probs.dtype):
+                dprobs = _workspace(4 * B * H * Nq * Nk, q.device, "attn_rowrel_dp").view(torch.float32)
+        else:
+            if rel_row.dtype != torch.float32 or tuple(rel_row.shape) != (B, Nq) or Nq != Nk:
+                raise MMXError("attn_capture_bwd: rel_row must be fp32 [B, N] of a self-attention, with mma_bf16=True")
+            name, tail, slab, dprobs = "mmx_attn_capture_bwd_rowrel", (), slab | flags, dprobs_out
         rel_row = rel_row.contiguous()
         rel_out = torch.empty_like(rel_row)
-        need = lib().mmx_attn_capture_bwd_rowrel_workspace_bytes(B, H, Nq, Nk)
+        need = getattr(lib(), name + "_workspace_bytes")(B, H, Nq, Nk)
         ws = _workspace(need, q.device, "attn_bwd")
-        check(lib().mmx_attn_capture_bwd_rowrel(
-            _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
-            _p(probs), probs_sb, _DTYPES[probs.dtype] | flags, _p(d_o), *_bhnd_strides(d_o, layout),
-            _p(o), *(_bhnd_strides(o, layout) if o is not None else zero3), _p(dprobs_out), _p(dq), _p(dk), _p(dv),
-            *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
-            *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
-            B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(rel_row), _p(rel_out), _p(ws), need, _stream()),
-            "mmx_attn_capture_bwd_rowrel")
+        check(getattr(lib(), name)(*operands(slab, dprobs), _p(rel_row), _p(rel_out), *tail, _p(ws), need, _stream()), name)
         return dq, dk, dv, rel_out
     if live is not None:
         _live_attn_check("attn_capture_bwd", live, B, Nq, Nk, probs)
-        check(lib().mmx_attn_capture_bwd_live(
-            _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
-            _p(probs), probs_sb, _DTYPES[probs.dtype], _p(d_o), *_bhnd_strides(d_o, layout), _p(dprobs_out), _p(dq), _p(dk), _p(dv),
-            *(_bhnd_strides(dq, layout) if need_dqkv else zero3), *(_bhnd_strides(dk, layout) if need_dqkv else zero3),
-            *(_bhnd_strides(dv, layout) if need_dqkv else zero3),
-            B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(live.eot), _p(ws), need, _stream()),
-            "mmx_attn_capture_bwd_live")
+        check(lib().mmx_attn_capture_bwd_live(*operands(slab, dprobs_out, fwd_o=False), _p(live.eot), _p(ws), need, _stream()),
+              "mmx_attn_capture_bwd_live")
         return dq, dk, dv
-
-    def call(d_o_, dq_, dk_, dv_, flags_):
-        return lib().mmx_attn_capture_bwd_ex(
-            _p(q), _p(k), _p(v), *_bhnd_strides(q, layout), *_bhnd_strides(k, layout), *_bhnd_strides(v, layout),
-            _p(probs), probs_sb, _DTYPES[probs.dtype] | flags_, _p(d_o_), *_bhnd_strides(d_o_, layout),
-            _p(o), *(_bhnd_strides(o, layout) if o is not None else zero3), _p(dprobs_out), _p(dq_), _p(dk_), _p(dv_),
-            *(_bhnd_strides(dq_, layout) if need_dqkv else zero3), *(_bhnd_strides(dk_, layout) if need_dqkv else zero3),
-            *(_bhnd_strides(dv_, layout) if need_dqkv else zero3),
-            B, H, Nq, Nk, D, float(scale), scale_mode, int(need_dqkv), _p(ws), need, _stream())
-    rc = call(d_o, dq, dk, dv, flags)
+    rc = lib().mmx_attn_capture_bwd_ex(*operands(slab | flags, dprobs_out), _p(ws), need, _stream())
     if rc == _lib.MMX_ENOTSUP and io_bf16 and not mma_bf16:
         # the whole-head kernel is the only exact-fp32 kernel with bf16 gradient I/O; it turned this call down at run time (a view
         # it cannot load 8 bytes at a time, or option attn_head = 0): same arithmetic on an fp32 d_o, results rounded once to bf16
         f32 = [torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device) for t in (q, k, v)] if need_dqkv else [None] * 3
-        check(call(d_o.float(), *f32, flags & ~_lib.MMX_ATTN_IO_BF16), "mmx_attn_capture_bwd")
+        check(lib().mmx_attn_capture_bwd_ex(*operands(slab | flags & ~_lib.MMX_ATTN_IO_BF16, dprobs_out, d_o.float(), f32), _p(ws),
+                                            need, _stream()), "mmx_attn_capture_bwd")
         if need_dqkv:
             for dst, src in zip((dq, dk, dv), f32):
                 dst.copy_(src)
@@ -1725,12 +1686,7 @@ def attn_relprop(q, k, v, probs, o, cam_o, scale, scale_mode=_lib.SCALE_Q_FIRST,
     _dev(*given)
     if any(t.dtype != torch.float32 for t in given):
         raise MMXError("attn_relprop: fp32 operands only")
-    if layout == "bnhd":
-        B, Nq, H, D = q.shape
-        Nk = k.shape[1]
-    else:
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
+    B, H, Nq, Nk, D = _attn_dims(q, k, layout)
     for name, t in (("probs", probs if values else None), ("cam_scores", cam_scores)):
         if t is not None and (not t.is_contiguous() or t.numel() != B * H * Nq * Nk):
             raise MMXError("attn_relprop: %s must be a contiguous [B,H,Nq,Nk] slab" % name)
@@ -1742,12 +1698,10 @@ def attn_relprop(q, k, v, probs, o, cam_o, scale, scale_mode=_lib.SCALE_Q_FIRST,
     cam_probs = torch.empty(B, H, Nq, Nk, dtype=torch.float32, device=q.device) if values else None
     cam_q, cam_k = (new(q), new(k)) if scores else (None, None)
     cam_v = new(v) if values else None
-    zero3 = (0, 0, 0)
-    st = lambda t: zero3 if t is None else _bhnd_strides(t, layout)           # noqa: E731
-    check(lib().mmx_attn_relprop_phase(_p(q), _p(k), _p(v), _p(o), _p(cam_o), *st(q), *st(k), *st(v), *st(o), *st(cam_o),
-                                       _p(probs), _p(cam_probs), _p(cam_q), _p(cam_k), _p(cam_v), *st(cam_q), *st(cam_k),
-                                       *st(cam_v), B, H, Nq, Nk, D, float(scale), scale_mode, _p(cam_scores), int(phase),
-                                       _stream()), "mmx_attn_relprop_phase")
+    qkv, (po, *so), (pc, *sc) = _qkv_args(q, k, v, layout), _strided(o, layout), _strided(cam_o, layout)
+    check(lib().mmx_attn_relprop_phase(*qkv[:3], po, pc, *qkv[3:], *so, *sc, _p(probs), _p(cam_probs),
+                                       *_qkv_args(cam_q, cam_k, cam_v, layout), B, H, Nq, Nk, D, float(scale), scale_mode,
+                                       _p(cam_scores), int(phase), _stream()), "mmx_attn_relprop_phase")
     return cam_probs, cam_q, cam_k, cam_v
 
 
