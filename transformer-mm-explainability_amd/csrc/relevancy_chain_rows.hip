@@ -17,7 +17,7 @@
 // the overlap the two-launch form never had (and the first, non-persistent version of this file did not get either: two
 // co-resident workgroups ran their phases in step -- profiles/r06_chain_rows_probe.txt).  Blocks of one sample run on ONE XCD at a
 // time (xcd_contiguous_id), so that sample's R_in (1.3 MB at 577 tokens) is served by that L2.
-// R_in == nullptr: the chain's first layer, R_in = I: R_out = I + A_bar, written by the matrix waves from the image.
+// R_in == nullptr: the chain's first layer, R_in = I: R_out = I + A_bar . I, written by the matrix waves from the image.
 #include "mmx_common.h"
 
 #include <type_traits>
@@ -156,11 +156,24 @@ __global__ __launch_bounds__(512, 2) void chain_rows_layer_kernel(const RowsArgs
         } else if (!(a.debug & 64)) {
             const int b = blk / nrb, r0 = (blk % nrb) * kRows;
             float* out = a.R_out + static_cast<int64_t>(b) * NN;
-            if (a.R_in == nullptr) {                                   // first layer of a chain: R_out = I + A_bar
+            if (a.R_in == nullptr) {                                   // first layer of a chain: R_out = I + A_bar . I
+                // A_bar . I is A_bar wherever the rest of the row is finite; a NaN or inf ELSEWHERE in the row meets a zero of the
+                // identity there (0 * inf = NaN), as in torch.bmm: one wave per row counts the row's non-finite elements first
                 const int rows = min(kRows, N - r0);
-                for (int e = tid; e < rows * N; e += 256) {
-                    const int row = e / N, col = e - row * N;
-                    out[static_cast<int64_t>(r0 + row) * N + col] = img[row * SA + col] + (r0 + row == col ? 1.f : 0.f);
+                for (int row = wave; row < rows; row += 4) {
+                    int bad = 0;
+                    for (int col = lane; col < N; col += 64) {
+                        const float v = img[row * SA + col];
+                        bad += (v - v != 0.f) ? 1 : 0;                 // v - v: 0 for a finite v, NaN for inf / NaN
+                    }
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+                    for (int col = lane; col < N; col += 64) {
+                        const float v = img[row * SA + col];
+                        const int others = bad - ((v - v != 0.f) ? 1 : 0);
+                        out[static_cast<int64_t>(r0 + row) * N + col] =
+                            others > 0 ? __builtin_nanf("") : v + (r0 + row == col ? 1.f : 0.f);
+                    }
                 }
             } else {
                 const float* Rb = a.R_in + static_cast<int64_t>(b) * NN;

@@ -287,14 +287,16 @@ __global__ __launch_bounds__(THREADS) void self_chain_fused_kernel(const ChainAr
 #pragma unroll
                     for (int u = 0; u < HPB; ++u) {
                         // heads in order: the same sum as the plain loop.  Every loaded register is USED unconditionally (a
-                        // head beyond H is a clamped duplicate, weighted 0): behind a branch the compiler would have to assume
+                        // head beyond H is a clamped duplicate of head H - 1): behind a branch the compiler would have to assume
                         // the skipped loads still pending and drain vmcnt before the next batch may overwrite their registers.
-                        const float w = (valid && hb * HPB + u < H) ? 1.f : 0.f;
+                        // The duplicate is SELECTED away, not multiplied by 0 (inf * 0 would plant a NaN where the reference has
+                        // +inf), as in chain_stream.h; on finite values the bits are those of the weighted form.
+                        const bool on = valid && hb * HPB + u < H;
 #pragma unroll
                         for (int jj = 0; jj < CPL; ++jj) {
                             const f32x4 x = __builtin_bit_cast(f32x4, gv[u * CPL + jj]) * __builtin_bit_cast(f32x4, av[u * CPL + jj]);
-                            s[jj][0] += relu_nan(x[0]) * w; s[jj][1] += relu_nan(x[1]) * w;
-                            s[jj][2] += relu_nan(x[2]) * w; s[jj][3] += relu_nan(x[3]) * w;
+                            s[jj][0] += on ? relu_nan(x[0]) : 0.f; s[jj][1] += on ? relu_nan(x[1]) : 0.f;
+                            s[jj][2] += on ? relu_nan(x[2]) : 0.f; s[jj][3] += on ? relu_nan(x[3]) : 0.f;
                         }
                     }
                     if (valid && hb == HB - 1) {
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(THREADS) void self_chain_fused_kernel(const ChainAr
                         if (k == nk - 1) __syncthreads();  // publish A_bar_l (pairs with the matrix waves' barrier of layer l)
                     }
                 };
-                // Two register sets; every issue is UNCONDITIONAL (past the end: the last batch again, consumed with weight 0)
+                // Two register sets; every issue is UNCONDITIONAL (past the end: the last batch again, consumed with nothing selected)
                 // so that the number of loads in flight is the same on every path -- with a conditional issue the compiler
                 // merges the two paths' wait counts and drains everything before each reduction.
                 u32x4 a0[4], g0[4], a1[4], g1[4];
