@@ -74,7 +74,7 @@ const char* mmx_last_error(void);
  *                        multiplies the group products (re-associated at the group boundaries).  fp32 slabs run the kernels with
  *                        barrier-free stream waves -- csrc/relevancy_chain_groups.hip (several groups: every A_bar of the group
  *                        resident in LDS) / csrc/relevancy_chain_cols.hip (one group, N >= 40: ring of A_bar images) --, everything
- *                        else the fused kernel of relevancy_kernels.hip | 1: the fused kernel everywhere (same bits) |
+ *                        else the fused kernel of relevancy_chain_fused.hip | 1: the fused kernel everywhere (same bits) |
  *                        4: same as 0 | 5: relevancy_chain_cols.hip for every
  *                        fp32 shape (strict layer order, bit-identical to "self_chain_groups" = 1)
  *   "self_chain_cols_c" / "self_chain_cols_nb"   0 auto (1 / as many as fit, <= 6) | workgroups per sample that split the COLUMNS of R

@@ -15,27 +15,27 @@ Bounds, per element, to first order in ``u = 2**-24``, each with the ``2**-126``
 of n fp32 terms on the fp32 MFMA or in FMA code errs by at most ``(n + 1) u sum |a_i b_i|`` in any order and grouping (zeros of the
 padding add nothing).
 
-* ``A_bar``: every term is >= 0, so sum |terms| = H A_bar.  One product (relevancy_kernels.hip:42 / 156, chain_stream.h:91,
-  relevancy_chain_rows.hip:97), H in-order additions (kernels:43-44 / 157-158, chain_stream.h:92-93, rows:99-100; the first one, onto 0,
-  is exact) and the division (kernels:47 / 171 / 312, chain_stream.h:96, rows:112):  ``e_A = (H + 2) u A_bar``.  The 16-bit element-wise
-  tail (kernels:50-56 / 161-165, rows:105-107) has the same count.
+* ``A_bar``: every term is >= 0, so sum |terms| = H A_bar.  One product, H in-order additions (the first one, onto 0, is exact) and the division (avg_heads_kernel in
+  relevancy_kernels.hip; reduce_chunk and the pipelined loop's consume in relevancy_chain_fused.hip; consume in chain_stream.h;
+  stream_block in relevancy_chain_rows.hip):  ``e_A = (H + 2) u A_bar``.  The 16-bit element-wise
+  tail of each has the same count.
 * one layer, ``P = A_bar |R|`` in float64:  ``E' = E + A_bar E + e_A |R| + (N + 1) u P + u |R'|`` -- the propagated error of R, the
-  error of A_bar, the product of N terms on v_mfma_f32_16x16x4_f32 (kernels:205-214, relevancy_chain_groups.hip:127-134,
-  relevancy_chain_cols.hip:136-142; 32x32x2 in rows:229-235 and bmm_f32_tiles.hip:165; bmm_f32_kernel kernels:505-517) and the addition
-  ``R + (A_bar . R)`` (kernels:216 / 532, groups:136, cols:144, rows:265 / 269, tiles:184).
-* layer groups (G > 1: kernels:354-430, groups:154-231): each ``P_g = prod (I + A_bar_l)`` carries its own ``E_g`` by the recurrence
-  above (group 0 starts at R_init); the combine ``acc <- P_g . acc`` (no addition: kernels:415, groups:223) adds
+  error of A_bar, the product of N terms on v_mfma_f32_16x16x4_f32 (chain_tile_product in chain_matrix.h for the three N <= 128
+  kernels; 32x32x2 in the rows kernel's multiply and in bmm_f32_tiles.hip; bmm_f32_kernel in relevancy_kernels.hip) and the addition
+  ``R + (A_bar . R)`` (each kernel's layer loop; the Cin addition of the product kernels' epilogues).
+* layer groups (G > 1: the hand-off + combine sections of self_chain_fused_kernel and self_chain_groups_kernel): each ``P_g = prod (I + A_bar_l)`` carries its own ``E_g`` by the recurrence
+  above (group 0 starts at R_init); the combine ``acc <- P_g . acc`` (no addition) adds
   ``|P_g| e_acc + E_g |acc| + (N + 1) u |P_g| |acc|``.  The reference stays the sequential chain: the bound licenses the re-association.
 * ``bmm`` (mmx_bmm_f32: both general tile sizes, trans_a, Cin, the bias row behind mmx_linear_f32, the tiles kernel):
-  ``(K + 1) u sum_k |a b|``, plus ``u |C|`` for the Cin addition (kernels:532, tiles:184).  nan_to_zero: a NaN of the reference is 0.
+  ``(K + 1) u sum_k |a b|``, plus ``u |C|`` for the Cin addition (the epilogues of bmm_f32_kernel and bmm_f32_tiles_kernel).  nan_to_zero: a NaN of the reference is 0.
 * split path and rows kernel: the one-layer recurrence with these pieces.  The rows kernel's first layer from the identity is
-  ``I + A_bar`` (rows:159-177): no product, ``e_A`` and the addition ``u |R'|`` (exact off the diagonal, where it adds 0).
-* ``chain_matvec`` (kernels:691-700): a term passes its product, at most 4 additions per chunk step of its lane
+  ``I + A_bar`` (chain_rows_layer_kernel, R_in == nullptr): no product, ``e_A`` and the addition ``u |R'|`` (exact off the diagonal, where it adds 0).
+* ``chain_matvec`` (chain_matvec_kernel): a term passes its product, at most 4 additions per chunk step of its lane
   (``ceil((N / 4) / 64)`` steps; the tail element adds one more), six shuffle steps, then the base:  ``(4 steps + 8) u sum |A y| + u |out|``.
-* ``chain_vecmat`` (kernels:712-734): product, up to 32 additions in the row chunk, ``ceil(N / 32)`` in the chunk sum, then the base:
+* ``chain_vecmat`` (chain_vecmat_partial_kernel, chain_vecmat_reduce_kernel): product, up to 32 additions in the row chunk, ``ceil(N / 32)`` in the chunk sum, then the base:
   ``(33 + ceil(N / 32)) u sum |x A| + u |out|``.
-* ``avg_heads_vecmat`` (kernels:763-795): ``e_A |x|`` on every term, the product with x (kernels:776), three additions of the four rows
-  in LDS (kernels:781), ``ceil(N / 4)`` in the chunk sum (kernels:794), the base:  ``sum_r |x_r| e_A + (4 + ceil(N / 4)) u sum |x A_bar| + u |out|``.
+* ``avg_heads_vecmat`` (avg_heads_vecmat_partial_kernel, avg_heads_vecmat_reduce_kernel): ``e_A |x|`` on every term, the product with x,
+  three additions of the four rows in LDS, ``ceil(N / 4)`` in the chunk sum, the base:  ``sum_r |x_r| e_A + (4 + ceil(N / 4)) u sum |x A_bar| + u |out|``.
 * ``relevancy_chain_row``: N <= 128 the row of the fused chain's bound; longer, ``x <- x + x A_bar_l`` from the top layer down with
   ``e' = e + e A_bar + |x| e_A + (33 + ceil(N / 32)) u |x| A_bar + u |x'|``.
 
@@ -72,16 +72,16 @@ def _al(n):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# routes: which kernel a chain case must reach (relevancy_kernels.hip:1073-1114, 1183-1288)
+# routes: which kernel a chain case must reach (chain_route in relevancy_chain.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 def groups_lds_ok(nt, per):
-    """``groups_lds_bytes`` <= 160 KiB (relevancy_chain_groups.hip:235-246)."""
+    """``groups_lds_bytes`` <= 160 KiB (``self_chain_groups_applies`` in relevancy_chain_groups.hip)."""
     return 4 * (max(per, 3) * nt * 16 * (nt * 16 + 4) + per * nt + 8) <= 160 * 1024
 
 
 def pipe_cpl(N, H, pipe):
-    """Chunks per lane of the fused kernel's pipelined stream loop, 0 = the plain loop (relevancy_kernels.hip:139-146, 238-239, 336-338,
-    1197)."""
+    """Chunks per lane of the fused kernel's pipelined stream loop, 0 = the plain loop (the work split, the pipelined form's condition and
+    ``run_cpl`` in self_chain_fused_kernel; the N * N >= 1600 rule of mmx_relevancy_self_chain_flags)."""
     NN, nt = N * N, -(-N // 16)
     if not pipe or NN < 1600 or nt >= 16:
         return 0
@@ -100,7 +100,7 @@ def pipe_cpl(N, H, pipe):
 
 
 def bmm_kernel(batch, M, N, K, trans_a=False, tiles=1):
-    """``launch_bmm`` (relevancy_kernels.hip:541-554) and ``bmm_f32_tiles_try`` (bmm_f32_tiles.hip:196-200) on 256 compute units."""
+    """``launch_bmm`` (relevancy_kernels.hip) and ``bmm_f32_tiles_try`` (bmm_f32_tiles.hip) on 256 compute units."""
     w64 = -(-N // 64) * -(-M // 64) * batch
     if tiles and not trans_a and M >= 96 and N >= 96 and K >= 32 and w64 >= CUS:
         return "tiles"
@@ -109,7 +109,9 @@ def bmm_kernel(batch, M, N, K, trans_a=False, tiles=1):
 
 def chain_route(c):
     """-> ``(kernel, G, cpl, bmm)``: ``fused`` | ``cols`` | ``groups`` | ``split`` | ``rows``; the group count (1 outside the N <= 128
-    kernels), the pipelined loop's chunks per lane (fused only, 0 = plain loop) and the product kernel of the split path."""
+    kernels), the pipelined loop's chunks per lane (fused only, 0 = plain loop) and the product kernel of the split path.  An independent
+    restatement of ``chain_route`` in csrc/relevancy_chain.hip (with ``chain_groups`` already applied: ``c["groups"]``), the tests' reference
+    for the dispatcher."""
     N, H, L, B, M = c["N"], c["H"], c["L"], c["B"], c["M"]
     nt = -(-N // 16)
     f32 = c["dtype"] == "f32"
@@ -127,7 +129,7 @@ def chain_route(c):
 
 
 def workspace_bytes(c):
-    """What ``mmx_self_chain_workspace_bytes`` must answer for the route (relevancy_kernels.hip:1103-1114)."""
+    """What ``mmx_self_chain_workspace_bytes`` must answer for the route (``chain_workspace_bytes`` in relevancy_chain.hip)."""
     N, B, M = c["N"], c["B"], c["M"]
     if -(-N // 16) <= 8 and M == 0:
         return 0 if c["kernel"] == "cols" or c["G"] == 1 else _al(4 * B) + _al(4 * B * c["G"] * N * N)
@@ -371,7 +373,7 @@ def abar32(a, g, mut=None, causal_flag=False):
 
 def k_groups(n, how):
     """The contraction index in the groups one MFMA instruction sums: ``mfma16`` k = 16 t + 4 q + r per (t, r)
-    (relevancy_kernels.hip:208-214); ``slab4`` four consecutive k (bmm_f32_kernel, kernels:505-517); ``pair`` {8 j + t, 8 j + 4 + t}
+    (chain_tile_product in chain_matrix.h); ``slab4`` four consecutive k (bmm_f32_kernel); ``pair`` {8 j + t, 8 j + 4 + t}
     (v_mfma_f32_32x32x2_f32: bmm_f32_tiles.hip:151-166, relevancy_chain_rows.hip:229-235)."""
     out = []
     if how == "mfma16":

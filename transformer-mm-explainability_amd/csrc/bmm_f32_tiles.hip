@@ -2,7 +2,7 @@
 // the N > 128 relevancy chain (R <- R + A_bar . R at 197 / 577 / 950-1050 tokens: DETR/modules/ExplanationGenerator.py:110-118,
 // ViT notebook cell 7:33, CLIP_explainability.ipynb cell 6:32 on ViT-L/14@336) and of the batched rules 6 / 7 / 10.
 //
-// the round-1..4 kernel (bmm_f32_kernel, relevancy_kernels.hip: 64 x 64 tiles, scalar 4-byte global loads,
+// the round-1..4 kernel (bmm_f32_kernel, still in relevancy_kernels.hip: 64 x 64 tiles, scalar 4-byte global loads,
 // scalar LDS stores, ds_read_b32 operands, two barriers per 32-wide K slab) ran at 32-40 % of the fp32 MFMA peak and lost to
 // rocBLAS.  This one (950 tokens: 0.597 of the peak, rocBLAS 0.587; 577: 0.507 / 0.487; 1024: 0.706 / 0.717):
 //   * TM x TN output tile per 256-thread workgroup (instantiated at 64 x 64), 4 waves as 2 x 2; a wave's (TM/2) x (TN/2) block is

@@ -149,6 +149,11 @@ __device__ __forceinline__ void slab_store(typename slab_elem<DT>::type* p, floa
 
 // clamp(x, min=0) with torch semantics: NaN propagates (fmaxf would drop it)
 __device__ __forceinline__ float relu_nan(float x) { return (x < 0.0f) ? 0.0f : x; }
+// one rounding to fp16, held in fp32: what torch does to the result of an op on fp16 tensors (fp32 arithmetic inside the op).  The
+// reference's half-precision chain (CLIP_explainability.ipynb cell 6:20,43 with an fp16 model) rounds grad * attn, the head mean,
+// A_bar . R and R + A_bar . R this way
+__device__ __forceinline__ float round_f16(float x) { return static_cast<float>(static_cast<_Float16>(x)); }
+__device__ __forceinline__ f32x4 round_f16(f32x4 v) { return f32x4{round_f16(v[0]), round_f16(v[1]), round_f16(v[2]), round_f16(v[3])}; }
 // torch's min / max: a NaN wins
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }
 __device__ __forceinline__ float max_nan(float a, float b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
@@ -278,16 +283,36 @@ __attribute__((format(printf, 3, 4))) inline int check_grid(const char* entry, i
 void attn_head_enable(int on);
 void attn_head_tile_skip(int on);
 bool attn_head_live_option(const char* key, int value);   // attention_head.hip: option "text_live_attn"
+// What an entry of the self-attention chain has validated, as its launchers take it (relevancy_chain.hip fills it)
+struct ChainCall {
+    const void* const* attn;   // [n_layers] probability slabs
+    const void* const* grad;   // [n_layers] gradient slabs
+    int n_layers, B, H, N;
+    int64_t attn_bstride;      // batch stride of the probability slabs in elements (H*N*N, or 0: one forward shared by the batch)
+    const float* R_init;       // or null: the identity
+    float* R_out;
+    int nt;                    // option "self_chain_nt": nt loads on the read-once slabs
+    int causal;                // MMX_CHAIN_CAUSAL
+    int debug;                 // option "debug_flags" (profiling only; relevancy_chain.hip has the bits)
+};
+// layer groups of the N <= 128 kernels (G = 1: none, no scratch)
+struct ChainGroups {
+    int G;
+    unsigned* counters;        // [B] arrival tickets
+    float* parts;              // [B][G][N*N] partial products
+};
+// relevancy_chain_fused.hip: all layers in one launch, one barrier per layer (K1); half_chain: the fp16-mode chain
+int self_chain_fused_launch(const ChainCall& c, int dtype, const ChainGroups& grp, int pipe, bool half_chain, hipStream_t s);
 // relevancy_chain_cols.hip: the chain split by columns of R over the workgroups of a sample, strict layer order (K1c)
 bool self_chain_cols_applies(int n_layers, int B, int H, int N);
-int self_chain_cols_launch(const void* const* attn_layers, const void* const* grad_layers, int n_layers, int B, int H, int N,
-                           int64_t attn_bstride, const void* R_init, void* R_out, int nt_policy, int debug, hipStream_t s);
+int self_chain_cols_launch(const ChainCall& c, hipStream_t s);
 void chain_cols_options(int c, int nb);
 // relevancy_chain_groups.hip: the layer-group chain with barrier-free stream waves (K1g)
 bool self_chain_groups_applies(int n_layers, int G, int H, int N);
-int self_chain_groups_launch(const void* const* attn_layers, const void* const* grad_layers, int n_layers, int B, int H, int N, int G,
-                             int64_t attn_bstride, const void* R_init, void* R_out, unsigned* counters, float* parts, int nt_policy,
-                             int debug, hipStream_t s);
+int self_chain_groups_launch(const ChainCall& c, const ChainGroups& grp, hipStream_t s);
+// relevancy_kernels.hip: A_bar = mean_h clamp(G * A, 0); r16: the product and the mean each rounded to fp16 (the fp16-mode chain)
+int avg_heads_launch(const void* attn_dev, const void* grad_dev, void* out_dev, int B, int H, int Nq, int Nk, int dtype,
+                     int64_t attn_bstride, void* stream, bool r16 = false);
 void attn_stream_enable(int on);
 void attn_fwd_split_enable(int on);
 void attn_bf16_v2_enable(int on);
@@ -300,10 +325,12 @@ int zero_async(void* dst, size_t bytes, hipStream_t s);
 // bmm_f32_tiles.hip: the large exact-fp32 products (32 x 32 x 2 MFMA, 64 x 64 tiles); false = not its shape
 // relevancy_chain_rows.hip: one layer R_out = R_in + mean_h clamp(G * A, 0) . R_in of the long-sequence chain in ONE launch
 bool chain_rows_layer_applies(int N);
-int chain_rows_layer_launch(const void* attn, const void* grad, const float* R_in, float* R_out, int B, int H, int N, int dtype,
-                            int64_t attn_bstride, hipStream_t s, int debug = 0);
+int chain_rows_layer_launch(const ChainCall& c, int l, const float* R_in, float* R_out, int dtype, hipStream_t s);   // layer l of the call
 bool bmm_f32_tiles_try(const float* A, const float* B, const float* Cin, float* C, int batch, int M, int N, int K, int trans_a,
                        int64_t sa, int64_t sb, int64_t sc, int nan_to_zero, int cin_is_row, hipStream_t s);
+// mmx_set_option (mmx_runtime.hip) asks each of these in turn: true = the key is this file's and the value was in its range
+bool chain_option(const char* key, int value);            // relevancy_chain.hip: options "self_chain_*", "debug_flags"
+bool bmm_option(const char* key, int value);              // relevancy_kernels.hip: option "bmm_tiles"
 bool text_live_rows_option(const char* key, int value);   // gemm_rows_f32.hip: options "text_live_rows", "text_live_rows_fwd", "gemm_rows_tm", "gemm_rows_tn", "gemm_rows_pf"
 int gemm_rows_tn_option();                                 // gemm_rows_f32.hip: option "gemm_rows_tn" as set (0: from the shape)
 bool gemm_rows_half_option(const char* key, int value);   // gemm_rows_f16.hip: option "text_live_rows_half"

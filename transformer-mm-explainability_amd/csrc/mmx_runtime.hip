@@ -1,4 +1,4 @@
-// Error reporting + HIP-event helpers of the C-ABI (include/mmx_relevancy.h).
+// Error reporting, the option table + HIP-event helpers of the C-ABI (include/mmx_relevancy.h).
 #include <stdarg.h>
 
 #include "mmx_common.h"
@@ -75,6 +75,42 @@ int identity_async(float* R, int batch, int N, hipStream_t s) {
 
 extern "C" int mmx_abi_version(void) { return MMX_ABI_VERSION; }
 extern "C" const char* mmx_last_error(void) { return mmx::g_err; }
+
+// Every file owns its options (a *_option function: true = the key is mine and the value was in range); the attention switches
+// take any value.
+extern "C" int mmx_set_option(const char* key, int value) {
+    using namespace mmx;
+    if (key && (chain_option(key, value) || bmm_option(key, value) || text_live_rows_option(key, value) ||
+                gemm_rows_half_option(key, value) || attn_head_live_option(key, value) || clip_head_option(key, value)))
+        return MMX_OK;
+    if (key && strcmp(key, "attn_head_tile_skip") == 0) {
+        if (value != 0 && value != 1) { set_error("mmx_set_option(attn_head_tile_skip): 0 or 1"); return MMX_EINVAL; }
+        attn_head_tile_skip(value);
+        return MMX_OK;
+    }
+    if (key && strcmp(key, "attn_head") == 0) {
+        attn_head_enable(value);
+        return MMX_OK;
+    }
+    if (key && strcmp(key, "attn_bf16_v3") == 0 && value >= 0 && value <= 3) {
+        attn_bf16_v3_enable(value);
+        return MMX_OK;
+    }
+    if (key && strcmp(key, "attn_bf16_v2") == 0) {
+        attn_bf16_v2_enable(value);
+        return MMX_OK;
+    }
+    if (key && strcmp(key, "attn_stream") == 0) {
+        attn_stream_enable(value);
+        return MMX_OK;
+    }
+    if (key && strcmp(key, "attn_fwd_split") == 0) {
+        attn_fwd_split_enable(value);
+        return MMX_OK;
+    }
+    set_error("mmx_set_option: unknown option/value %s=%d", key ? key : "(null)", value);
+    return MMX_EINVAL;
+}
 
 extern "C" int mmx_event_create(void** event_out) {
     if (!event_out) { mmx::set_error("mmx_event_create: null"); return MMX_EINVAL; }

@@ -25,6 +25,8 @@
 // a matrix wave follows tile by tile.  Back-pressure on the ring: a stream wave about to write layer l waits until every matrix wave
 // has finished layer l - NB (progress words in LDS) -- the matrix waves need 1.3 us per layer against ~5 us of streaming, so it
 // does not wait in practice.
+#include "chain_launch.h"
+#include "chain_matrix.h"
 #include "chain_stream.h"
 
 namespace mmx {
@@ -50,32 +52,24 @@ constexpr int kColsWaves = kColsThreads / 64;
 
 template <int NT>
 __global__ __launch_bounds__(kColsThreads) void self_chain_cols_kernel(const ColsArgs a) {
-    constexpr int NP = NT * 16;
-    constexpr int S = NP + 4;
+    constexpr int NP = kChainNP<NT>;
+    constexpr int S = kChainS<NT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // NB images (NP x S floats) + NB x NT arrival counters + 16 progress words
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int C = a.C, NB = a.NB;
-    // the C workgroups of a sample on ONE XCD (workgroup w runs on XCD w % 8).  A placement hint only.
-    int b, c;
-    {
-        const int w = blockIdx.x, full = (a.B >> 3) * 8 * C;
-        if (w < full) { b = (w & 7) + 8 * ((w >> 3) / C); c = (w >> 3) % C; }
-        else { b = (a.B >> 3) * 8 + (w - full) / C; c = (w - full) % C; }
-    }
+    int b, c;       // the C workgroups of a sample on one XCD
+    chain_xcd_placement(blockIdx.x, a.B, C, b, c);
     const int N = a.N, H = a.H, L = a.n_layers;
     const int NN = N * N;
     const int nown = (NT - c + C - 1) / C;                                     // slabs c, c + C, ... < NT
     unsigned* lds_cnt = reinterpret_cast<unsigned*>(smem + NB * NP * S);       // [NB][NT] elements landed per (slot, 16-row tile), cumulative
     unsigned* prog = lds_cnt + NB * NT;                                        // [16] layers finished per matrix wave
 
-    {   // pads must read as 0; counters = 0
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        const int n4 = (NB * NP * S + NB * NT + 16 + 3) >> 2;            // (rounded up: the allocation has the slack)
-        for (int i = tid; i < n4; i += kColsThreads) reinterpret_cast<f32x4*>(smem)[i] = z;
-    }
+    // pads must read as 0; counters = 0  (rounded up: the allocation has the slack)
+    chain_lds_zero(smem, (NB * NP * S + NB * NT + 16 + 3) >> 2, tid, kColsThreads);
     __syncthreads();
 
     const int NBLK = (a.nchunks + 63) >> 6;            // 64-chunk blocks per layer
@@ -103,44 +97,18 @@ __global__ __launch_bounds__(kColsThreads) void self_chain_cols_kernel(const Col
     } else {
         // =============================================================================================== matrix waves
         const int slab = c + wave * C;
-        const int col = slab * 16 + (lane & 15);
-        const int rq = (lane >> 4) * 4;
+        const ChainLane q = chain_lane(slab, lane);
         f32x4 Rold[NT], Rnew[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = t * 16 + rq + r;
-                float v = 0.f;
-                if (row < N && col < N)
-                    v = a.R_init ? a.R_init[static_cast<int64_t>(b) * NN + row * N + col] : (row == col ? 1.f : 0.f);
-                Rold[t][r] = v;
-            }
+        chain_slab_load<int>(Rold, a.R_init != nullptr, a.R_init, static_cast<int64_t>(b) * NN, N, q);
         bool poisoned = false;
         for (int l = 0; l < L; ++l) {
             const int slot = l % NB;
-            const unsigned uses = static_cast<unsigned>(l / NB + 1);
-            const float* Ab = smem + slot * NP * S + (lane & 15) * S + rq;
+            const unsigned uses = static_cast<unsigned>(l / NB + 1);    // arrival counts are cumulative over the uses of the slot
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti) {
-                const unsigned expect = uses * static_cast<unsigned>(max(0, min(N, ti * 16 + 16) - ti * 16) * N);
-                int turns = 0;
-                while (__hip_atomic_load(lds_cnt + slot * NT + ti, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < expect &&
-                       ++turns < (1 << 24))
-                    __builtin_amdgcn_s_sleep(1);
-                if (turns >= (1 << 24)) poisoned = true;        // never seen; if it happens the result says so (NaN), it does not lie
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (chain_tile_wait(lds_cnt + slot * NT + ti, N, ti, uses)) poisoned = true;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (!(a.debug & 1)) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        const f32x4 av = *reinterpret_cast<const f32x4*>(Ab + ti * 16 * S + t * 16);
-                        acc = mfma16x16x4(av[0], Rold[t][0], acc);
-                        acc = mfma16x16x4(av[1], Rold[t][1], acc);
-                        acc = mfma16x16x4(av[2], Rold[t][2], acc);
-                        acc = mfma16x16x4(av[3], Rold[t][3], acc);
-                    }
-                }
+                if (!(a.debug & 1)) acc = chain_tile_product(smem + slot * NP * S, ti, Rold, lane, q, std::false_type{}, slab);
                 Rnew[ti] = Rold[ti] + acc;                  // R + (A_bar . R): same association as the reference
             }
 #pragma unroll
@@ -150,14 +118,7 @@ __global__ __launch_bounds__(kColsThreads) void self_chain_cols_kernel(const Col
             if (lane == 0) __hip_atomic_store(prog + wave, static_cast<unsigned>(l + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         if (__hip_atomic_load(prog + 15, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) poisoned = true;
-        float* dst = a.R_out + static_cast<int64_t>(b) * NN;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = t * 16 + rq + r;
-                if (row < N && col < N) dst[row * N + col] = poisoned ? __builtin_nanf("") : Rold[t][r];
-            }
+        chain_slab_store<int>(a.R_out + static_cast<int64_t>(b) * NN, 0, Rold, N, q, false, poisoned);
     }
 }
 
@@ -193,44 +154,19 @@ bool self_chain_cols_applies(int n_layers, int B, int H, int N) {
     return n_layers >= 1 && nt <= 8 && cols_lds_bytes(nt, 1) <= 160 * 1024 && static_cast<size_t>(H) * N * N * 4 < (1ull << 31);
 }
 
-template <int NT>
-static int cols_launch(const ColsArgs& r, hipStream_t s) {
-    const size_t lds = cols_lds_bytes(NT, r.NB);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_chain_cols_kernel<NT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    self_chain_cols_kernel<NT><<<r.B * r.C, kColsThreads, lds, s>>>(r);
-    MMX_LAUNCH_CHECK("self_chain_cols_kernel");
-    return MMX_OK;
-}
-
-int self_chain_cols_launch(const void* const* attn_layers, const void* const* grad_layers, int n_layers, int B, int H, int N,
-                           int64_t attn_bstride, const void* R_init, void* R_out, int nt_policy, int debug, hipStream_t s) {
+int self_chain_cols_launch(const ChainCall& c, hipStream_t s) {
     ColsArgs r;
-    memset(&r, 0, sizeof(r));
-    for (int l = 0; l < n_layers; ++l) { r.attn[l] = attn_layers[l]; r.grad[l] = grad_layers[l]; }
-    r.n_layers = n_layers; r.B = B; r.H = H; r.N = N;
-    cols_plan(n_layers, B, N, &r.C, &r.NB);
-    r.nchunks = (N * N + 3) / 4;
-    r.row_magic = static_cast<unsigned>((0x100000000ull + N - 1) / N);
-    r.R_init = static_cast<const float*>(R_init);
-    r.R_out = static_cast<float*>(R_out);
-    r.attn_bstride = attn_bstride;
-    r.nt = nt_policy & 1;              // `nt_policy`: bit 0 = nt loads on the read-once slabs, bit 1 = MMX_CHAIN_CAUSAL
-    r.causal = (nt_policy >> 1) & 1;
-    r.debug = debug;
-    switch ((N + 15) / 16) {
-        case 1: return cols_launch<1>(r, s);
-        case 2: return cols_launch<2>(r, s);
-        case 3: return cols_launch<3>(r, s);
-        case 4: return cols_launch<4>(r, s);
-        case 5: return cols_launch<5>(r, s);
-        case 6: return cols_launch<6>(r, s);
-        case 7: return cols_launch<7>(r, s);
-        default: return cols_launch<8>(r, s);
-    }
+    chain_fill_stream_args(r, c);
+    cols_plan(r.n_layers, r.B, r.N, &r.C, &r.NB);
+    r.debug = ((c.debug & 4) ? 1 : 0) | ((c.debug & 16) ? 2 : 0);      // option "debug_flags" -> this kernel's own bits
+    return dispatch_nt((r.N + 15) / 16, [&](auto nt_tag) -> int {
+        constexpr int NT = decltype(nt_tag)::value;
+        const size_t lds = cols_lds_bytes(NT, r.NB);
+        if (int rc = set_dynamic_lds(self_chain_cols_kernel<NT>, lds)) return rc;
+        self_chain_cols_kernel<NT><<<r.B * r.C, kColsThreads, lds, s>>>(r);
+        MMX_LAUNCH_CHECK("self_chain_cols_kernel");
+        return MMX_OK;
+    });
 }
 
 }  // namespace mmx

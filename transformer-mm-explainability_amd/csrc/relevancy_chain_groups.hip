@@ -7,7 +7,7 @@
 // Reference sites: CLIP_explainability.ipynb cell 6:22-32 / 45-55, CLIP/example.py:22-30, ViT notebook cell 7:28-33,
 // VisualBERT/.../ExplanationGenerator.py:86-93 (include/mmx_relevancy.h, mmx_relevancy_self_chain).
 //
-// What changed against self_chain_fused_kernel (relevancy_kernels.hip), which made stream and matrix waves meet at one s_barrier per
+// What changed against self_chain_fused_kernel (relevancy_chain_fused.hip), which made stream and matrix waves meet at one s_barrier per
 // layer and let the stream waves walk a whole layer as one chunk loop: round 5's relay experiments (a strict-order kernel fed through
 // L2, since removed: profiles/r05_chain_relay_probe.txt)
 // showed that stream waves which never wait -- each with its own register software pipeline over 64-chunk blocks -- reach 0.58 of the
@@ -20,6 +20,8 @@
 //     between the two roles anywhere;
 //   * hand-off and combine as before (write-through partial products, one ticket per sample, the last arriver multiplies), i.e.
 //     the products are re-associated at the group boundaries exactly as in self_chain_fused_kernel (same 1e-5 bound, same tests).
+#include "chain_launch.h"
+#include "chain_matrix.h"
 #include "chain_stream.h"
 
 namespace mmx {
@@ -47,22 +49,16 @@ constexpr int kGroupsWaves = kGroupsThreads / 64;
 
 template <int NT>
 __global__ __launch_bounds__(kGroupsThreads) void self_chain_groups_kernel(const GroupsArgs a) {
-    constexpr int NP = NT * 16;
-    constexpr int S = NP + 4;
+    constexpr int NP = kChainNP<NT>;
+    constexpr int S = kChainS<NT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // A_bar images (NP x S floats each) + per x NT counters + ticket
 
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int G = a.G;
-    // the G workgroups of a sample on ONE XCD (workgroup w runs on XCD w % 8): the partial products then meet in that XCD's L2.
-    // A placement hint only -- nothing below depends on it.
-    int b, g;
-    {
-        const int w = blockIdx.x, full = (a.B >> 3) * 8 * G;
-        if (w < full) { b = (w & 7) + 8 * ((w >> 3) / G); g = (w >> 3) % G; }
-        else { b = (a.B >> 3) * 8 + (w - full) / G; g = (w - full) % G; }
-    }
+    int b, g;       // the G workgroups of a sample on one XCD: the partial products then meet in that XCD's L2
+    chain_xcd_placement(blockIdx.x, a.B, G, b, g);
     const int N = a.N, H = a.H;
     const int per = (a.n_layers + G - 1) / G;
     const int l0 = min(a.n_layers, g * per), l1 = min(a.n_layers, l0 + per);
@@ -72,15 +68,11 @@ __global__ __launch_bounds__(kGroupsThreads) void self_chain_groups_kernel(const
     unsigned* lds_cnt = reinterpret_cast<unsigned*>(smem + images * NP * S);   // [per][NT] elements of A_bar_l landed per 16-row tile
     unsigned* ticket_lds = lds_cnt + per * NT;
 
-    {   // pads must read as 0; counters = 0
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        const int n4 = (images * NP * S + per * NT + 1 + 3) >> 2;        // (NP * S is a multiple of 4; the allocation is rounded up)
-        for (int i = tid; i < n4; i += kGroupsThreads) reinterpret_cast<f32x4*>(smem)[i] = z;
-    }
+    // pads must read as 0; counters = 0  (NP * S is a multiple of 4; the allocation is rounded up)
+    chain_lds_zero(smem, (images * NP * S + per * NT + 1 + 3) >> 2, tid, kGroupsThreads);
     __syncthreads();
 
-    const int col = wave * 16 + (lane & 15);
-    const int rq = (lane >> 4) * 4;
+    const ChainLane q = chain_lane(wave, lane);
     f32x4 Rold[NT], Rnew[NT];
     // MMX_CHAIN_CAUSAL and R starts as the identity: every A_bar_l, every R and every partial product is LOWER TRIANGULAR, so the
     // 16 x 16 tile (ti, tj) of a product is sum over tj <= t <= ti only -- 35 of the 125 tile products at 77 tokens.  The skipped
@@ -96,70 +88,29 @@ __global__ __launch_bounds__(kGroupsThreads) void self_chain_groups_kernel(const
         });
     } else {
         // =============================================================================================== matrix waves
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = t * 16 + rq + r;
-                float v = 0.f;
-                if (row < N && col < N)
-                    v = (a.R_init && g == 0) ? a.R_init[static_cast<int64_t>(b) * NN + row * N + col] : (row == col ? 1.f : 0.f);
-                Rold[t][r] = v;
-            }
+        chain_slab_load<int>(Rold, a.R_init && g == 0, a.R_init, static_cast<int64_t>(b) * NN, N, q);
         bool poisoned = false;
         for (int l = 0; l < L; ++l) {
-            const float* Ab = smem + l * NP * S + (lane & 15) * S + rq;
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti) {
                 // rows [16 ti, 16 ti + 16) of A_bar_l are all this wave's tile ti needs: the product runs behind the stream waves tile
-                // by tile, only the last tile of the group's last layer is exposed.  (Bounded like every wait here: the stream
-                // waves of this workgroup deliver in microseconds or something is broken.)
-                const unsigned expect = static_cast<unsigned>(max(0, min(N, ti * 16 + 16) - ti * 16) * N);
-                int turns = 0;
-                while (__hip_atomic_load(lds_cnt + l * NT + ti, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < expect &&
-                       ++turns < (1 << 24))
-                    __builtin_amdgcn_s_sleep(1);
-                if (turns >= (1 << 24)) poisoned = true;        // never seen; if it happens the result says so (NaN), it does not lie
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                // by tile, only the last tile of the group's last layer is exposed
+                if (chain_tile_wait(lds_cnt + l * NT + ti, N, ti, 1u)) poisoned = true;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (!(a.debug & 4)) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        if (tri && (t > ti || t < wave)) continue;      // (wave = this wave's column slab tj; wave-uniform)
-                        const f32x4 av = *reinterpret_cast<const f32x4*>(Ab + ti * 16 * S + t * 16);
-                        acc = mfma16x16x4(av[0], Rold[t][0], acc);
-                        acc = mfma16x16x4(av[1], Rold[t][1], acc);
-                        acc = mfma16x16x4(av[2], Rold[t][2], acc);
-                        acc = mfma16x16x4(av[3], Rold[t][3], acc);
-                    }
-                }
+                if (!(a.debug & 4)) acc = chain_tile_product(smem + l * NP * S, ti, Rold, lane, q, tri, wave);
                 Rnew[ti] = Rold[ti] + acc;                  // R + (A_bar . R): same association as the reference
             }
 #pragma unroll
             for (int t = 0; t < NT; ++t) Rold[t] = Rnew[t];
         }
-        float* dst = a.parts + (static_cast<int64_t>(b) * G + g) * NN;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = t * 16 + rq + r;
-                if (row < N && col < N)      // write-through: the hand-off below needs no L2 write-back fence
-                    __hip_atomic_store(dst + row * N + col, poisoned ? __builtin_nanf("") : Rold[t][r], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-            }
+        chain_slab_store<int>(a.parts + (static_cast<int64_t>(b) * G + g) * NN, 0, Rold, N, q, true, poisoned);
     }
     if (a.debug & 1) return;
 
     // ------------------------------------------------------------------ hand-off + combine
     // R = P_{G-1} . ... . P_1 . P_0 (P_0 already includes R_init): the sequential chain, re-associated at the group boundaries
     // (rounding-level difference, tests bound it at 1e-5).  Placement independent, no spinning: the LAST arriver of a sample multiplies.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores
-    __syncthreads();
-    if (tid == 0)
-        *ticket_lds = __hip_atomic_fetch_add(a.counters + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const unsigned ticket = *ticket_lds;
+    const unsigned ticket = chain_handoff_ticket(a.counters + b, ticket_lds, tid);
     if (ticket != static_cast<unsigned>(G - 1) || (a.debug & 8)) return;
     if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // (skipping it when all groups share an XCD gains nothing: measured)
     __syncthreads();
@@ -195,7 +146,7 @@ __global__ __launch_bounds__(kGroupsThreads) void self_chain_groups_kernel(const
     for (int q = 0; q < 4; ++q)
         if (q < G) prefetch(q, pre[q]);
     stash(X0, pre[0]);
-    const int li = lane & 15;
+    const int li = lane & 15, rq = q.rq;     // (both operands from LDS here: lane l reads row / column li, k = rq .. rq + 3)
 #pragma unroll
     for (int gg = 1; gg < 8; ++gg) {       // G <= 8 (option range)
         if (gg >= G) break;
@@ -245,49 +196,23 @@ bool self_chain_groups_applies(int n_layers, int G, int H, int N) {
     return groups_lds_bytes(nt, (n_layers + G - 1) / G) <= 160 * 1024;
 }
 
-template <int NT>
-static int groups_launch(const GroupsArgs& r, hipStream_t s) {
-    const size_t lds = groups_lds_bytes(NT, (r.n_layers + r.G - 1) / r.G);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(self_chain_groups_kernel<NT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    self_chain_groups_kernel<NT><<<r.B * r.G, kGroupsThreads, lds, s>>>(r);
-    MMX_LAUNCH_CHECK("self_chain_groups_kernel");
-    return MMX_OK;
-}
-
-int self_chain_groups_launch(const void* const* attn_layers, const void* const* grad_layers, int n_layers, int B, int H, int N, int G,
-                             int64_t attn_bstride, const void* R_init, void* R_out, unsigned* counters, float* parts, int nt_policy,
-                             int debug, hipStream_t s) {
-    if (static_cast<size_t>(H) * N * N * 4 >= (1ull << 31)) { set_error("self_chain_groups: head slabs beyond 2 GiB"); return MMX_ENOTSUP; }
+int self_chain_groups_launch(const ChainCall& c, const ChainGroups& grp, hipStream_t s) {
+    if (static_cast<size_t>(c.H) * c.N * c.N * 4 >= (1ull << 31)) { set_error("self_chain_groups: head slabs beyond 2 GiB"); return MMX_ENOTSUP; }
     GroupsArgs r;
-    memset(&r, 0, sizeof(r));
-    for (int l = 0; l < n_layers; ++l) { r.attn[l] = attn_layers[l]; r.grad[l] = grad_layers[l]; }
-    r.n_layers = n_layers; r.B = B; r.H = H; r.N = N; r.G = G;
-    r.nchunks = (N * N + 3) / 4;
-    r.row_magic = static_cast<unsigned>((0x100000000ull + N - 1) / N);
-    r.R_init = static_cast<const float*>(R_init);
-    r.R_out = static_cast<float*>(R_out);
-    r.parts = parts;
-    r.counters = counters;
-    r.attn_bstride = attn_bstride;
-    r.nt = nt_policy & 1;              // `nt_policy`: bit 0 = nt loads on the read-once slabs, bit 1 = MMX_CHAIN_CAUSAL
-    r.causal = (nt_policy >> 1) & 1;
-    r.debug = debug;
-    int zrc = zero_async(counters, sizeof(unsigned) * B, s);
+    chain_fill_stream_args(r, c);
+    r.G = grp.G;
+    r.parts = grp.parts;
+    r.counters = grp.counters;
+    int zrc = zero_async(r.counters, sizeof(unsigned) * r.B, s);
     if (zrc) return zrc;
-    switch ((N + 15) / 16) {
-        case 1: return groups_launch<1>(r, s);
-        case 2: return groups_launch<2>(r, s);
-        case 3: return groups_launch<3>(r, s);
-        case 4: return groups_launch<4>(r, s);
-        case 5: return groups_launch<5>(r, s);
-        case 6: return groups_launch<6>(r, s);
-        case 7: return groups_launch<7>(r, s);
-        default: return groups_launch<8>(r, s);
-    }
+    return dispatch_nt((r.N + 15) / 16, [&](auto nt_tag) -> int {
+        constexpr int NT = decltype(nt_tag)::value;
+        const size_t lds = groups_lds_bytes(NT, (r.n_layers + r.G - 1) / r.G);
+        if (int rc = set_dynamic_lds(self_chain_groups_kernel<NT>, lds)) return rc;
+        self_chain_groups_kernel<NT><<<r.B * r.G, kGroupsThreads, lds, s>>>(r);
+        MMX_LAUNCH_CHECK("self_chain_groups_kernel");
+        return MMX_OK;
+    });
 }
 
 }  // namespace mmx

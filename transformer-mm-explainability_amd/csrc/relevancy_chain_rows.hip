@@ -308,14 +308,13 @@ bool chain_rows_layer_applies(int N) {
     return N > 128 && N <= 636 && rows_lds_bytes(N, nullptr) <= 160 * 1024;
 }
 
-int chain_rows_layer_launch(const void* attn, const void* grad, const float* R_in, float* R_out, int B, int H, int N, int dtype,
-                            int64_t attn_bstride, hipStream_t s, int debug) {
+int chain_rows_layer_launch(const ChainCall& c, int l, const float* R_in, float* R_out, int dtype, hipStream_t s) {
     RowsArgs a;
-    a.debug = debug;
-    a.attn = attn; a.grad = grad; a.R_in = R_in; a.R_out = R_out;
-    a.B = B; a.H = H; a.N = N; a.attn_bstride = attn_bstride;
-    a.nblocks = B * ((N + kRows - 1) / kRows);
-    const size_t lds = rows_lds_bytes(N, &a.SA);
+    a.debug = c.debug;
+    a.attn = c.attn[l]; a.grad = c.grad[l]; a.R_in = R_in; a.R_out = R_out;
+    a.B = c.B; a.H = c.H; a.N = c.N; a.attn_bstride = c.attn_bstride;
+    a.nblocks = a.B * ((a.N + kRows - 1) / kRows);
+    const size_t lds = rows_lds_bytes(a.N, &a.SA);
     switch (dtype) {
         case MMX_F32: return dispatch_rows<MMX_F32>(a, lds, s);
         case MMX_F16: return dispatch_rows<MMX_F16>(a, lds, s);
