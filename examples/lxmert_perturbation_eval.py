@@ -41,12 +41,15 @@ def synthetic_item(k, regions, feat_dim, vocab, answers):
 # BATCHED_BASELINES (GeneratorBaselines.generate_*_batch, replayed from GraphedBaselinesBatch; --per-item-baselines puts them back
 # on the per-item route for A / B runs); the others run the reference's per-item generator call
 # (lxmert_explainability.GeneratorOurs / GeneratorBaselines / GeneratorOursAblationNoAggregation; the LRP ones on the body's
-# own relprop pass) followed by the same batched perturbation of that one item.
+# own relprop pass) followed by the same batched perturbation of that one item.  --batch-lrp 1 puts the four LRP methods of
+# BATCHED_LRP on one eager forward / backward / relprop per padded batch (GeneratorOurs.generate_ours_batch(use_lrp=True),
+# GeneratorBaselines.generate_transformer_attr_batch / generate_partial_lrp_batch); the default, 0, changes nothing.
 BATCHED_METHODS = {"ours_no_lrp": {}, "ours_no_lrp_no_norm": {"normalize_self_attention": False},
                    "ablation_no_self_in_10": {"apply_self_in_rule_10": False}}
 OTHER_METHODS = {"ours_with_lrp", "rollout", "partial_lrp", "transformer_att", "raw_attn", "attn_gradcam",
                  "ours_with_lrp_no_normalization", "ablation_no_aggregation"}
 BATCHED_BASELINES = {"rollout", "raw_attn", "attn_gradcam"}       # of OTHER_METHODS: no LRP pass, batched kernels exist
+BATCHED_LRP = {"ours_with_lrp", "ours_with_lrp_no_normalization", "transformer_att", "partial_lrp"}   # --batch-lrp 1: one eager pass per batch
 
 
 class ItemUsage:
@@ -98,10 +101,13 @@ def main():
                     help="round-1 behaviour: group items by question length, eager explain pass per group")
     ap.add_argument("--per-item-baselines", action="store_true",
                     help="rollout / raw_attn / attn_gradcam on the per-item route (one batch-1 explain call per item), for A/B runs")
+    ap.add_argument("--batch-lrp", type=int, choices=(0, 1), default=0,
+                    help="1: the four LRP methods explain a padded batch in one eager forward / backward / relprop (0: one item per call)")
     args = ap.parse_args()
     args.text, args.positive = args.is_text_pert, args.is_positive_pert
     batched_baseline = args.method in BATCHED_BASELINES and not args.per_item_baselines
-    per_item = args.method not in BATCHED_METHODS and not batched_baseline
+    batched_lrp = args.method in BATCHED_LRP and args.batch_lrp == 1
+    per_item = args.method not in BATCHED_METHODS and not batched_baseline and not batched_lrp
     if per_item:
         args.max_batch, args.bucket_by_length = 1, True                # one item per explain call, its own length
     rule_flags = BATCHED_METHODS.get(args.method, {})
@@ -158,6 +164,12 @@ def main():
                 graphed["explain"] = per_item_method(args.method, le, ItemUsage(model))
             usage_item = dict(batch)
             R_t_t, R_t_i = (r.unsqueeze(0) for r in graphed["explain"](usage_item))
+        elif batched_lrp:                      # an autograd pass and a relprop: eager, never captured
+            R_t_t, R_t_i = {"ours_with_lrp": lambda b: gen.generate_ours_batch(b, use_lrp=True),
+                            "ours_with_lrp_no_normalization": lambda b: gen.generate_ours_batch(b, use_lrp=True,
+                                                                                                normalize_self_attention=False),
+                            "transformer_att": base_gen.generate_transformer_attr_batch,
+                            "partial_lrp": base_gen.generate_partial_lrp_batch}[args.method](batch)
         elif args.bucket_by_length:
             R_t_t, R_t_i = getattr(base_gen, "generate_%s_batch" % args.method)(batch) if batched_baseline else \
                 gen.generate_ours_batch(batch, **rule_flags)

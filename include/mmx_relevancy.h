@@ -427,6 +427,44 @@ int mmx_lxmert_rollout(const void* const* text_attn, int n_text, const void* con
                        void* R_ti_dev, void* R_ii_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The LRP baselines of the bi-modal model for a PADDED batch of ragged questions (csrc/bimodal_baselines.hip), on the LRP cams that
+ * the body's relprop leaves in the capture slabs.  The contract of the block above holds word for word: fp32 [B, H, Nq, Nk] slabs,
+ * DEVICE int32 lengths (NULL = the full extent) clamped to 1..N inside the kernel, sample b computed from its LIVE block only, exact
+ * zeros outside it.  An entry outside the live block is never summed, multiplied into a live entry or divided by: its value -- a NaN
+ * included -- does not matter.  Fixed summation orders, no atomics.  Every argument is checked before any HIP call: null required
+ * pointers and null table entries, B / H <= 0, sizes outside 1..48, n_text < 1, n_img < 1, tables longer than
+ * MMX_BASELINES_MAX_TABLE, a workspace that is too small or not 16-byte aligned, and outputs that overlap an input or each other
+ * return MMX_EINVAL with a message in mmx_last_error().
+ *
+ * mmx_lxmert_attr: generate_transformer_attr (lxmert/lxmert/src/ExplanationGenerator.py:373-460 with avg_heads :18-23).
+ *   text_cam / text_grad: HOST tables of n_text >= 1 device slabs [B, H, T, T], the LRP cams and the gradients of the language layers,
+ *              then every x-layer's lang_self_att (:405-411, :431-435, :453-457);  img_cam / img_grad: n_img >= 1 slabs [B, H, I, I]:
+ *              r_layers, then visn_self_att of every x-layer but the last (:414-420, :437-441);  cross_cam_dev / cross_grad_dev: the
+ *              last x-layer's visual_attention [B, H, T, I] (:447-449).
+ *   Per sample, t = clamp(text_len[b], 1, T):  A_bar(C, G) = (sum_h max(0, G_h . C_h)) / H, the clamp per head before the sum (a NaN
+ *   stays a NaN, as torch.clamp keeps it), heads in ascending order;  R_tt = I_t, R_tt <- R_tt + A_bar_l R_tt for l = 0 .. n_text - 1
+ *   (:411);  R_ii the same over the image table (:420);  R_ti[:t, :] = A_bar(cross)[:t, :] (:451);  R_tt[0, 0] = 0 (:459).
+ *   outputs fp32: R_tt [B, T, T], R_ti [B, T, I] (zero beyond t), R_ii [B, I, I].
+ *   workspace: mmx_lxmert_attr_workspace_bytes(...) bytes (0 for arguments the entry would refuse), 16-byte aligned, caller-owned,
+ *   stream-ordered.
+ *   Two plain launches ordered by the stream: B x (n_text + n_img + 1) workgroups form every A_bar once (16-byte loads, every slab
+ *   read exactly once; the cross block is written straight to R_ti); one workgroup per sample then runs both chains from LDS on the
+ *   exact-fp32 MFMA (v_mfma_f32_16x16x4_f32).
+ *
+ * mmx_head_minmax_live: the per-map step of generate_partial_lrp (lxmert/lxmert/src/ExplanationGenerator.py:489-505): out [B, Nq, Nk],
+ *   out[b] = (m - min m) / (max m - min m) with m = mean_h cam[b, h] (:493, :498, :502-503), the extremes over the live
+ *   q_len[b] x k_len[b] block.  max == min gives 0 / 0 = NaN over the live block (a one-entry block included), as the reference's
+ *   expression does, and a NaN anywhere in the live block of m makes the whole live block NaN, as torch.min / torch.max do.
+ *   flags: MMX_HEAD_MEAN_ZERO_CLS writes out[b, 0, 0] = 0 AFTER the normalisation (:505).  One launch, one workgroup per sample. */
+size_t mmx_lxmert_attr_workspace_bytes(int n_text, int n_img, int B, int T, int I);
+int mmx_lxmert_attr(const void* const* text_cam, const void* const* text_grad, int n_text, const void* const* img_cam,
+                    const void* const* img_grad, int n_img, const void* cross_cam_dev, const void* cross_grad_dev, int B, int H, int T,
+                    int I, const void* text_len_dev, void* R_tt_dev, void* R_ti_dev, void* R_ii_dev, void* workspace_dev,
+                    size_t workspace_bytes, void* stream);
+int mmx_head_minmax_live(const void* cam_dev, void* out_dev, int B, int H, int Nq, int Nk, const void* q_len_dev,
+                         const void* k_len_dev, unsigned flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The attention-only baselines of the single-stream (VisualBERT-style) model for a PADDED batch of ragged questions
  * (csrc/selfattn_baselines.hip).  The reference explains one question per call and trims its text padding
  * (VisualBERT/mmf/models/visual_bert.py:578-588), so it never pads; here every slab is the fp32 [B, H, N, N] capture slab of a padded

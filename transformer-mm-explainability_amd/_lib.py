@@ -62,6 +62,9 @@ _PROTOTYPES = {
     "mmx_head_mean_live": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _u, _vp]),
     "mmx_lxmert_rollout_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "mmx_lxmert_rollout": (_i, [_vpp, _i, _vpp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmx_lxmert_attr_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mmx_lxmert_attr": (_i, [_vpp, _vpp, _i, _vpp, _vpp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mmx_head_minmax_live": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _u, _vp]),
     "mmx_selfattn_row_live_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mmx_selfattn_row_live": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mmx_selfattn_rollout_row_workspace_bytes": (_sz, [_i, _i, _i, _i]),

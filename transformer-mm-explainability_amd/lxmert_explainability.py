@@ -60,6 +60,29 @@ def _backward_on_answer(model_usage, input, index, use_lrp=False, backward=True)
     return model
 
 
+def _batch_lrp_pass(model, model_inputs, backward=True, index=None):
+    """The LRP methods' pass for a padded batch: ONE forward on the module path with grad mode on (``forward_tape`` clears the LRP
+    tapes, so this route never takes the tape path) [+ ONE backward with B one-hot seeds] + ONE ``model.relprop(one_hot [B, A],
+    alpha=1)`` -> ``(model, text_len)``.  ``index``: ``None`` (the arg-max answer per sample, picked on the device) or ``[B]`` answer
+    ids; ``text_len`` is ``attention_mask.sum(1)`` as a device int32 tensor (``None`` without a mask).  Nothing is read back to the
+    host.  ``bert_lrp`` takes every whole-tensor sum per sample and the pass has no mask rule: probabilities are exact zeros at
+    padded keys, so no relevance reaches a padded key or a padded query row."""
+    _require_relprop(model)
+    T, I = model_inputs["input_ids"].shape[1], model_inputs["visual_feats"].shape[1]
+    if max(T, I) > ops.LXMERT_FUSED_MAX_TOKENS:
+        raise NotImplementedError("the batched LRP methods run LDS-resident kernels (T, I <= %d)" % ops.LXMERT_FUSED_MAX_TOKENS)
+    with torch.enable_grad():
+        output = rules.forward_for_backward(model, lambda: model(**model_inputs).question_answering_score)   # [B, A]
+        idx = output.argmax(dim=-1) if index is None else torch.as_tensor(index, device=output.device).reshape(-1)
+        one_hot = torch.zeros_like(output).scatter_(1, idx.reshape(-1, 1), 1.0)
+        if backward:
+            model.zero_grad()
+            torch.sum(one_hot * output).backward(retain_graph=True)
+    model.relprop(one_hot.detach().clone(), alpha=1)
+    mask = model_inputs.get("attention_mask")
+    return model, (mask.sum(dim=1).to(torch.int32) if mask is not None else None)
+
+
 class GeneratorOurs:
     def __init__(self, model_usage, save_visualization=False):
         """``save_visualization`` is STORED and never read, exactly as in the reference (lxmert/lxmert/src/ExplanationGenerator.py:57-59,
@@ -84,7 +107,7 @@ class GeneratorOurs:
         return self.R_t_t, self.R_t_i
 
     def generate_ours_batch(self, model_inputs, index=None, normalize_self_attention=True, apply_self_in_rule_10=True,
-                            check_diag=True):
+                            check_diag=True, use_lrp=False):
         """B samples in ONE forward + ONE backward (B one-hot seeds) + ONE schedule launch.
 
         The evaluator (``perturbation.py:216-250``) explains one item per call; every per-item pass is ~1000 launches on
@@ -102,13 +125,17 @@ class GeneratorOurs:
         ...).  ``index``: ``None`` (arg-max answer per sample, chosen on the device) or ``[B]`` answer ids.
         ``check_diag``: ``True`` asserts ``handle_residual``'s ``diag >= 0`` now (one device->host read); ``"defer"``
         leaves the device word in ``self.diag_min`` and synchronises nothing (``GraphedGenerateOursBatch`` uses it).
+        ``use_lrp``: ``True`` runs the schedule on the LRP cams (the reference's ``generate_ours`` default, :131): the pass is
+        ``_batch_lrp_pass`` -- module path, one backward, one ``relprop`` -- whatever ``use_tape`` says.
         Returns ``(R_t_t [B, T, T], R_t_i [B, T, I])``; ``self.R_i_i`` / ``self.R_i_t`` hold the image-side matrices.
         """
-        self.use_lrp = False
+        self.use_lrp = use_lrp
         self.normalize_self_attention = normalize_self_attention
         self.apply_self_in_rule_10 = apply_self_in_rule_10
         model = self.model_usage.model
-        if self.use_tape and hasattr(model, "forward_tape"):
+        if use_lrp:
+            _batch_lrp_pass(model, model_inputs, backward=True, index=index)
+        elif self.use_tape and hasattr(model, "forward_tape"):
             # tape path (lxmert_model.forward_tape / backward_tape, bert_tape.py): no autograd graph through the encoder, packed
             # q/k/v GEMMs, fused add + LayerNorm, residual adds folded into GEMMs -- about half the launches of the route below
             output, state = model.forward_tape(**model_inputs)                                           # [B, A]
@@ -129,10 +156,11 @@ class GeneratorOurs:
         text_len = mask.sum(dim=1).to(torch.int32) if mask is not None else None       # stays on the device
         enc = model.lxmert.encoder
         xs = list(enc.x_layers)
+        u = use_lrp
         out = ops.lxmert_schedule(
-            [_pair(b.attention.self) for b in enc.layer], [_pair(b.attention.self) for b in enc.r_layers],
-            [_pair(b.visual_attention.att) for b in xs], [_pair(b.visual_attention_copy.att) for b in xs[:-1]],
-            [_pair(b.lang_self_att.self) for b in xs], [_pair(b.visn_self_att.self) for b in xs[:-1]],
+            [_pair(b.attention.self, u) for b in enc.layer], [_pair(b.attention.self, u) for b in enc.r_layers],
+            [_pair(b.visual_attention.att, u) for b in xs], [_pair(b.visual_attention_copy.att, u) for b in xs[:-1]],
+            [_pair(b.lang_self_att.self, u) for b in xs], [_pair(b.visn_self_att.self, u) for b in xs[:-1]],
             apply_normalization=normalize_self_attention, apply_self_in_rule_10=apply_self_in_rule_10,
             check_diag=check_diag, text_len=text_len)
         self.R_t_t, self.R_t_i, self.R_i_i, self.R_i_t = out[:4]
@@ -264,7 +292,9 @@ class GeneratorBaselines:
     """Attention-only baselines of the reference (:368-665): raw attention, attention GradCAM, rollout.
     ``generate_transformer_attr`` / ``generate_partial_lrp`` read LRP cams: they need a body with ``relprop`` (module docstring).
     ``generate_rollout_batch`` / ``generate_raw_attn_batch`` / ``generate_attn_gradcam_batch`` explain a padded batch of ragged
-    questions in one pass (``csrc/bimodal_baselines.hip``); ``GraphedBaselinesBatch`` replays them from one hipGraph."""
+    questions in one pass (``csrc/bimodal_baselines.hip``); ``GraphedBaselinesBatch`` replays them from one hipGraph.
+    ``generate_transformer_attr_batch`` / ``generate_partial_lrp_batch`` do the same for the two LRP baselines on ``_batch_lrp_pass``
+    (eager: an autograd pass and a ``relprop``, never captured)."""
 
     def __init__(self, model_usage, save_visualization=False):
         self.model_usage = model_usage
@@ -350,6 +380,29 @@ class GeneratorBaselines:
                 model(**model_inputs)
         mask = model_inputs.get("attention_mask")
         return model, (mask.sum(dim=1).to(torch.int32) if mask is not None else None)
+
+    def generate_transformer_attr_batch(self, model_inputs, index=None):
+        """``generate_transformer_attr`` (reference :373-460) for B padded samples: one forward, one backward with B one-hot seeds,
+        one ``relprop`` and ``mmx_lxmert_attr`` (two launches).  ``model_inputs`` / ``index`` as ``generate_attn_gradcam_batch``.
+        Returns ``(R_t_t [B, T, T], R_t_i [B, T, I])``, zero beyond each sample's question length; ``self.R_i_i [B, I, I]``."""
+        model, text_len = _batch_lrp_pass(self.model_usage.model, model_inputs, backward=True, index=index)
+        enc = model.lxmert.encoder
+        xs = list(enc.x_layers)
+        lang = [_pair(b.attention.self, True) for b in enc.layer] + [_pair(b.lang_self_att.self, True) for b in xs]
+        img = [_pair(b.attention.self, True) for b in enc.r_layers] + [_pair(b.visn_self_att.self, True) for b in xs[:-1]]
+        self.R_t_t, self.R_t_i, self.R_i_i = ops.lxmert_transformer_attr(lang, img, _pair(xs[-1].visual_attention.att, True),
+                                                                         text_len=text_len)
+        return self.R_t_t, self.R_t_i
+
+    def generate_partial_lrp_batch(self, model_inputs, index=None):
+        """``generate_partial_lrp`` (reference :462-506) for B padded samples: one forward, one ``relprop`` (no backward), two launches.
+        Each map is min-max normalised over its sample's live block."""
+        model, text_len = _batch_lrp_pass(self.model_usage.model, model_inputs, backward=False, index=index)
+        blk = model.lxmert.encoder.x_layers[-1]
+        self.R_t_i = ops.head_minmax_live(blk.visual_attention.att.get_attn_cam().detach(), q_len=text_len)
+        self.R_t_t = ops.head_minmax_live(blk.lang_self_att.self.get_attn_cam().detach(), q_len=text_len, k_len=text_len,
+                                          zero_cls=True)
+        return self.R_t_t, self.R_t_i
 
     def generate_raw_attn_batch(self, model_inputs):
         """``generate_raw_attn`` (reference :508-540) for B padded samples: one forward, two launches.  ``model_inputs`` as

@@ -1138,6 +1138,53 @@ def lxmert_rollout(text_attn, img_attn, cross_attn, text_len=None):
     return R_tt, R_ti, R_ii
 
 
+def head_minmax_live(cam, q_len=None, k_len=None, zero_cls=False):
+    """The per-map step of partial LRP on a padded batch: ``m = mean_h cam[b, h]`` on sample b's leading ``q_len[b] x k_len[b]`` block
+    of a ``[B, H, Nq, Nk]`` fp32 slab, ``(m - min m) / (max m - min m)`` with the extremes over that block, exact zeros outside it
+    -> ``[B, Nq, Nk]``.  ``max == min`` gives NaN over the block and a NaN in the block spreads over it, as in the reference's
+    expression; ``zero_cls`` writes ``out[b, 0, 0] = 0`` afterwards.  Arguments as ``head_mean_live``; one launch."""
+    what = "head_minmax_live"
+    cam = _slab(what, cam)
+    B, H, Nq, Nk = cam.shape
+    q_len, k_len = _lengths(what, q_len, B), _lengths(what, k_len, B)
+    out = torch.empty(B, Nq, Nk, dtype=torch.float32, device=cam.device)
+    check(lib().mmx_head_minmax_live(_p(cam), _p(out), B, H, Nq, Nk, _p(q_len), _p(k_len),
+                                     _lib.HEAD_MEAN_ZERO_CLS if zero_cls else 0, _stream()), "mmx_head_minmax_live")
+    return out
+
+
+def lxmert_transformer_attr(text_pairs, img_pairs, cross_pair, text_len=None):
+    """Transformer attribution of a padded LXMERT batch in two launches.  ``text_pairs``: ``(cam, grad)`` pairs of fp32
+    ``[B, H, T, T]`` slabs, the language layers, then every x-layer's language self-attention; ``img_pairs``: ``[B, H, I, I]`` pairs of
+    ``r_layers``, then the image self-attention of every x-layer but the last; ``cross_pair``: the last x-layer's ``[B, H, T, I]``
+    pair; ``text_len``: device int ``[B]`` or ``None``.  Returns ``(R_tt [B, T, T], R_ti [B, T, I], R_ii [B, I, I])``."""
+    what = "lxmert_transformer_attr"
+    text = [(_slab(what, c), _slab(what, g)) for c, g in text_pairs]
+    img = [(_slab(what, c), _slab(what, g)) for c, g in img_pairs]
+    cross_c, cross_g = _slab(what, cross_pair[0]), _slab(what, cross_pair[1])
+    B, H, T, I = cross_c.shape
+    if cross_g.shape != cross_c.shape or any(t.shape != (B, H, T, T) for pair in text for t in pair) or \
+            any(t.shape != (B, H, I, I) for pair in img for t in pair):
+        raise MMXError("lxmert_transformer_attr: the tables do not match the cross slab %s" % (tuple(cross_c.shape),))
+    text_len = _lengths(what, text_len, B)
+    dev = cross_c.device
+    R_tt = torch.empty(B, T, T, dtype=torch.float32, device=dev)
+    R_ti = torch.empty(B, T, I, dtype=torch.float32, device=dev)
+    R_ii = torch.empty(B, I, I, dtype=torch.float32, device=dev)
+    tc, _k0 = _lib.ptr_table([c.data_ptr() for c, _ in text])
+    tg, _k1 = _lib.ptr_table([g.data_ptr() for _, g in text])
+    ic, _k2 = _lib.ptr_table([c.data_ptr() for c, _ in img])
+    ig, _k3 = _lib.ptr_table([g.data_ptr() for _, g in img])
+    need = lib().mmx_lxmert_attr_workspace_bytes(len(text), len(img), B, T, I)
+    if need == 0:
+        raise MMXError("lxmert_transformer_attr: needs 1..%d text pairs, 1..%d image pairs and T, I <= %d (got %d, %d, T=%d, I=%d)"
+                       % (_lib.BASELINES_MAX_TABLE, _lib.BASELINES_MAX_TABLE, LXMERT_FUSED_MAX_TOKENS, len(text), len(img), T, I))
+    ws = _workspace(need, dev, tag="lxmert_attr")
+    check(lib().mmx_lxmert_attr(tc, tg, len(text), ic, ig, len(img), _p(cross_c), _p(cross_g), B, H, T, I, _p(text_len), _p(R_tt),
+                                _p(R_ti), _p(R_ii), _p(ws), need, _stream()), "mmx_lxmert_attr")
+    return R_tt, R_ti, R_ii
+
+
 # ------------------------------------------------------------------------------------------- single-stream baselines, padded batches
 SELFATTN_MAX_TOKENS = _lib.SELFATTN_MAX_TOKENS       # T + V of mmx_selfattn_row_live / mmx_selfattn_rollout_row
 
