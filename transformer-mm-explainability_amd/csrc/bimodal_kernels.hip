@@ -294,7 +294,6 @@ __global__ __launch_bounds__(kV2BmThreads) void lxmert_schedule_v2_kernel(const 
     stage(1);
     issue(2);
     __syncthreads();
-    bool crossed = false;        // R_ti / R_it are still zero before the first cross layer: rule 7 adds nothing
     for (int k = 0; k < v.nblk; ++k) {
         if (!(v.debug & 4)) {
             stage(k + 2);        // ring slot (k + 2) % 3 was last read by block k - 1, which ended with a barrier
@@ -330,14 +329,15 @@ __global__ __launch_bounds__(kV2BmThreads) void lxmert_schedule_v2_kernel(const 
                 add_mat(R_ti, park_sq, T, I);
                 add_mat(R_tt, park_ss, T, T);
             }
-            crossed = true;
             lds_barrier();
         } else {
-            // rules 6 + 7: R_ss += cam . R_ss ; R_sq += cam . R_sq, both from the old state (updates wait in the park buffers)
-            products(false, cam, ns, ns, Rss, ns, park_ss, false, Rsq, crossed ? nq : 0, park_sq, false);
+            // rules 6 + 7: R_ss += cam . R_ss ; R_sq += cam . R_sq, both from the old state (updates wait in the park buffers).  Rule 7
+            // also runs before the first cross layer, where R_sq is still zero: the reference multiplies there too, and a NaN in cam
+            // must reach R_sq (NaN * 0 = NaN) -- R_ii / R_tt read it in rule 11.
+            products(false, cam, ns, ns, Rss, ns, park_ss, false, Rsq, nq, park_sq, false);
             lds_barrier();
             add_mat(Rss, park_ss, ns, ns);
-            if (crossed) add_mat(Rsq, park_sq, ns, nq);
+            add_mat(Rsq, park_sq, ns, nq);
             lds_barrier();
         }
     }

@@ -44,7 +44,8 @@ struct DetrRowsArgs {
 
 // LDS: R and B as [QP][LD] (QP = 16 ceil(Q / 16) rows, zero padded: the MFMA tiles read whole 16 x 4 blocks), LD = QP + 1.
 // min that CARRIES a NaN (fminf drops it): the reference's ``assert diag.min() >= 0`` fails on a NaN diagonal, and so does the
-// word the Python wrapper reads (``NaN >= 0`` is false) -- ops.handle_residual's atomic_min_float keeps NaN bits the same way.
+// word the Python wrapper reads (``NaN >= 0`` is false).  The per-rule path's atomic_min_float (relevancy_kernels.hip) publishes a NaN
+// as 0xffc00000 for the same end.
 __device__ __forceinline__ float min_keep_nan(float m, float v) { return (m != m || v != v) ? __builtin_nanf("") : fminf(m, v); }
 
 // Rule 5 of the decoder SELF-attention maps, every (sample, layer) at once: B_l = mean_h clamp(G_l * A_l, 0) into the Bq scratch.  The maps do not

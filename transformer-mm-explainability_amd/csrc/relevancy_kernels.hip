@@ -188,8 +188,12 @@ static void launch_bmm(const float* A, const float* B, const float* Cin, float* 
 //   mode 1  rollout prep, normalised : out = (A + I)/rowsum(A + I)
 //   mode 2  rollout prep, plain      : out = A + I
 // =====================================================================================================
+// A NaN must stick (the reference's ``assert diag.min() >= 0`` fails on a NaN diagonal): it is published as 0xffc00000, which the
+// unsigned max keeps above every negative float and the signed min keeps below every non-negative one, whatever arrives later (a NaN
+// with the sign bit clear, 0x7fc00000, would be replaced by the next non-negative value's signed min).
 __device__ __forceinline__ void atomic_min_float(float* addr, float v) {
-    if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
+    if (v != v) atomicMax(reinterpret_cast<unsigned int*>(addr), 0xffc00000u);
+    else if (v >= 0.f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
