@@ -21,7 +21,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ops
+from . import graphed, ops
 from .rules import frozen_parameters as _Frozen
 
 def _plan(buffers, first, last, batch_size, shared, half_chain=False, causal=False):
@@ -195,17 +195,7 @@ class GraphedInterpret:
         # a trimmed run fixes the number of text positions at capture time: it must cover every later caption
         self.n_text = int(texts.argmax(dim=-1).max()) + 1 if trim_text_padding else None
         self._call = lambda: interpret(self.image, self.texts, model, self.image.device, _n_text=self.n_text, **kw)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        # thread_local: a collective backend's watchdog thread (RCCL, one rank per GPU) may poll events while this
-        # thread captures; only calls made by the capturing thread must be capture-safe
-        with ops.graph_capture(self.graph):
-            self.outputs = self._call()
+        self.graph, self.outputs, self._pinned_scratch = graphed.capture(self._call, warmup, model)
         # The graph bakes in the raw addresses of the towers' capture slabs and of the cached chain plans' scratch.  Pin
         # them: a later interpret() / GraphedInterpret on the same model with another batch, sharing mode or text length
         # makes ``Transformer._ensure_buffers`` install NEW slabs, and without this reference the old ones would be
@@ -227,7 +217,6 @@ class GraphedInterpret:
                 copy for blk in txt.resblocks
                 for w in (blk.attn.in_proj_weight, blk.attn.out_proj.weight, blk.mlp.c_fc.weight, blk.mlp.c_proj.weight)
                 for copy in ((ops._converted(w, torch.float16), ops.transposed_half_weight(w)) if half else (ops.transposed_weight(w),))]
-        self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
 
     def _reinstall(self):
         for tr, buf in zip((self.model.visual.transformer, self.model.transformer), self._pinned):

@@ -23,7 +23,7 @@ import collections
 
 import torch
 
-from . import ops, rules
+from . import graphed, ops, rules
 from .rules import avg_heads, compute_rollout_attention, handle_residual  # noqa: F401  (re-exported like the reference module)
 
 apply_self_attention_rules = rules.apply_self_attention_rules
@@ -674,42 +674,21 @@ class GraphedGenerateOursMulti:
         kw = dict(normalize_self_attention=normalize_self_attention, apply_self_in_rule_10=apply_self_in_rule_10,
                   check_diag="defer", rows_only=rows_only)
         self._call = lambda: self.gen.generate_ours_multi(self.img, self.targets, index=self.index, **kw)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.out = self._call()
-            self.diag_min = self.gen.diag_min
-        # the graph holds raw addresses of the attention modules' slabs and of scratch buffers that were allocated by the
-        # warm-up calls: keep them alive (an eager forward with another batch size replaces the modules' slabs)
-        self._pinned = ops.pinned_state(model)
+        self.graph, self.out, self._pinned = graphed.capture(self._call, warmup, model)
+        self.diag_min = self.gen.diag_min          # (what the captured call left on the generator: the graph's own buffer)
 
     def __call__(self, img, target_indices, index=None, check=True):
         targets = torch.as_tensor(target_indices, device=self.img.device).reshape(-1)
-        n = targets.numel()
         classes = None if index is None else torch.as_tensor(index, device=self.img.device).reshape(-1)
         self.img.copy_(img)
-        chunks = []
-        for i in range(0, n, self.K):
-            part = targets[i:i + self.K]
-            self.targets[:part.numel()] = part
-            self.index.fill_(-1)
-            if classes is not None:
-                self.index[:part.numel()] = classes[i:i + self.K]
-            if part.numel() < self.K:
-                self.targets[part.numel():] = part[-1]
-                self.index[part.numel():] = self.index[part.numel() - 1]
-            self.graph.replay()
+
+        def after_replay():
             if callable(check):                       # the caller folds the device word into its own check (no sync here)
                 check(self.diag_min)
             elif check and self.diag_min is not None:
                 assert self.diag_min.item() >= 0
-            chunks.append(self.out[:, :, :part.numel()].clone())
-        return torch.cat(chunks, dim=2) if len(chunks) != 1 else chunks[0]
+
+        return graphed.replay_slots(self.graph, self.K, self.targets, self.index, self.out, targets, classes, after_replay)
 
 
 class GraphedBaselinesMulti:
@@ -746,32 +725,10 @@ class GraphedBaselinesMulti:
         else:
             fn = getattr(self.gen, "generate_%s_multi" % method)
             self._call = lambda: fn(self.img, self.targets)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.out = self._call()
-        self._pinned = ops.pinned_state(model)        # slabs and scratch whose addresses the graph holds
+        self.graph, self.out, self._pinned = graphed.capture(self._call, warmup, model)
 
     def __call__(self, img, target_indices, index=None):
         targets = torch.as_tensor(target_indices, device=self.img.device).reshape(-1)
-        n = targets.numel()
         classes = None if index is None else torch.as_tensor(index, device=self.img.device).reshape(-1)
         self.img.copy_(img)
-        chunks = []
-        for i in range(0, n, self.K):
-            part = targets[i:i + self.K]
-            self.targets[:part.numel()] = part
-            self.index.fill_(-1)
-            if classes is not None:
-                self.index[:part.numel()] = classes[i:i + self.K]
-            if part.numel() < self.K:
-                self.targets[part.numel():] = part[-1]
-                self.index[part.numel():] = self.index[part.numel() - 1]
-            self.graph.replay()
-            chunks.append(self.out[:, :, :part.numel()].clone())
-        return torch.cat(chunks, dim=2) if len(chunks) != 1 else chunks[0]
+        return graphed.replay_slots(self.graph, self.K, self.targets, self.index, self.out, targets, classes)

@@ -21,7 +21,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ops, rules
+from . import graphed, ops, rules
 from .rules import avg_heads, compute_rollout_attention, handle_residual  # noqa: F401
 
 apply_self_attention_rules = rules.apply_self_attention_rules
@@ -493,30 +493,14 @@ class GraphedGenerateOursBatch:
         kw = dict(normalize_self_attention=normalize_self_attention, apply_self_in_rule_10=apply_self_in_rule_10,
                   check_diag="defer")
         self._call = lambda: self.gen.generate_ours_batch(self.static, self.static_index, **kw)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.outputs = self._call()
-            self.diag_min = self.gen.diag_min
-            self.R_i_i, self.R_i_t = self.gen.R_i_i, self.gen.R_i_t
-        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+        self.graph, self.outputs, self._pinned = graphed.capture(self._call, warmup, model)
+        self.diag_min = self.gen.diag_min          # (what the captured call left on the generator: the graph's own buffers)
+        self.R_i_i, self.R_i_t = self.gen.R_i_i, self.gen.R_i_t
 
     def __call__(self, inputs=None, index=None, check=True):
         if inputs is not None:
-            for k, v in inputs.items():
-                if v.shape != self.static[k].shape:
-                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
-                                     % (k, tuple(v.shape), tuple(self.static[k].shape)))
-                self.static[k].copy_(v)
-        if index is not None:
-            if self.static_index is None:
-                raise ValueError("the graph was captured with index=None (arg-max answers)")
-            self.static_index.copy_(torch.as_tensor(index))
+            graphed.copy_inputs(self.static, inputs, hint=graphed.PAD_HINT)
+        graphed.copy_index(self.static_index, index)
         self.graph.replay()
         if check == "deferred":
             # the same assert WITHOUT stalling this thread on the replay it has just launched (an evaluator wants to launch the next
@@ -570,28 +554,12 @@ class GraphedBaselinesBatch:
             self._call = lambda: self.gen.generate_raw_attn_batch(self.static)
         else:
             self._call = lambda: self.gen.generate_attn_gradcam_batch(self.static, self.static_index)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.outputs = self._call()
-            self.R_i_i = getattr(self.gen, "R_i_i", None)
-        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+        self.graph, self.outputs, self._pinned = graphed.capture(self._call, warmup, model)
+        self.R_i_i = getattr(self.gen, "R_i_i", None)
 
     def __call__(self, inputs=None, index=None):
         if inputs is not None:
-            for k, v in inputs.items():
-                if v.shape != self.static[k].shape:
-                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
-                                     % (k, tuple(v.shape), tuple(self.static[k].shape)))
-                self.static[k].copy_(v)
-        if index is not None:
-            if self.static_index is None:
-                raise ValueError("the graph was captured with index=None (arg-max answers)")
-            self.static_index.copy_(torch.as_tensor(index))
+            graphed.copy_inputs(self.static, inputs, hint=graphed.PAD_HINT)
+        graphed.copy_index(self.static_index, index)
         self.graph.replay()
         return self.outputs

@@ -32,7 +32,7 @@ import contextlib
 
 import torch
 
-from . import tuned_gemms
+from . import graphed, tuned_gemms
 
 PERT_STEPS = (0, 0.25, 0.5, 0.75, 0.8, 0.85, 0.9, 0.95, 1)
 
@@ -279,20 +279,10 @@ class GraphedImagePerturbation:
     Image test only: the text test reads the question lengths on the host (``perturbation_text``)."""
 
     def __init__(self, pert, batch, R_t_t, R_t_i, labels, is_positive_pert=False, warmup=2):
-        from . import ops
         self.pert, self.positive = pert, bool(is_positive_pert)
         self.static = {k: v.clone() for k, v in batch.items()}
         self.R_t_t, self.R_t_i, self.labels = R_t_t.clone(), R_t_i.clone(), labels.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.out = self._call()
-        self._pinned = ops.pinned_state(pert.model)
+        self.graph, self.out, self._pinned = graphed.capture(self._call, warmup, pert.model)
 
     def _call(self):
         cam_image, _ = normalize_cams_batch(self.R_t_t, self.R_t_i, self.static["attention_mask"])
@@ -300,10 +290,7 @@ class GraphedImagePerturbation:
         return LxmertPerturbation.accuracy(scores, self.labels)
 
     def __call__(self, batch, R_t_t, R_t_i, labels):
-        for k, v in batch.items():
-            if v.shape != self.static[k].shape:
-                raise ValueError("%s: %s, but the graph was captured for %s" % (k, tuple(v.shape), tuple(self.static[k].shape)))
-            self.static[k].copy_(v)
+        graphed.copy_inputs(self.static, batch)
         self.R_t_t.copy_(R_t_t)
         self.R_t_i.copy_(R_t_i)
         self.labels.copy_(labels)

@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ops, rules
+from . import graphed, ops, rules
 
 compute_rollout_attention = rules.compute_rollout_attention_batched
 
@@ -299,29 +299,14 @@ class GraphedGenerateOursBatch:
         self.static_index = None if index is None else torch.as_tensor(index, device=example["input_ids"].device).clone()
         self.gen = SelfAttentionGenerator(model)
         self._call = lambda: self.gen.generate_ours_batch(self.static, self.static_index, _n_text=self.n_text)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = self._call()
-        self._pinned = ops.pinned_state(model)
+        self.graph, self.output, self._pinned = graphed.capture(self._call, warmup, model)
 
     def __call__(self, input=None, index=None):
         if input is not None:
             if int(input["input_mask"].sum(1)[0]) != self.n_text:
                 raise ValueError("this graph was captured for %d text tokens" % self.n_text)
-            for k in self.KEYS:
-                if input[k].shape != self.static[k].shape:
-                    raise ValueError("%s: %s, captured for %s" % (k, tuple(input[k].shape), tuple(self.static[k].shape)))
-                self.static[k].copy_(input[k])
-        if index is not None:
-            if self.static_index is None:
-                raise ValueError("the graph was captured with index=None (arg-max answers)")
-            self.static_index.copy_(torch.as_tensor(index))
+            graphed.copy_inputs(self.static, input, self.KEYS, text="%s: %s, captured for %s")
+        graphed.copy_index(self.static_index, index)
         self.graph.replay()
         return self.output
 
@@ -354,28 +339,12 @@ class GraphedBaselinesBatch:
             self._call = lambda: self.gen.generate_raw_attn_batch(self.static)
         else:
             self._call = lambda: self.gen.generate_attn_gradcam_batch(self.static, self.static_index)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = self._call()
-        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+        self.graph, self.output, self._pinned = graphed.capture(self._call, warmup, model)
 
     def __call__(self, input=None, index=None):
         if input is not None:
-            for k in self.keys:
-                if input[k].shape != self.static[k].shape:
-                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
-                                     % (k, tuple(input[k].shape), tuple(self.static[k].shape)))
-                self.static[k].copy_(input[k])
-        if index is not None:
-            if self.static_index is None:
-                raise ValueError("the graph was captured with index=None (arg-max answers)")
-            self.static_index.copy_(torch.as_tensor(index))
+            graphed.copy_inputs(self.static, input, self.keys, hint=graphed.PAD_HINT)
+        graphed.copy_index(self.static_index, index)
         self.graph.replay()
         return self.output
 
@@ -398,27 +367,11 @@ class GraphedGenerateOursPadded:
         self.static_index = None if index is None else torch.as_tensor(index, device=example["input_ids"].device).clone()
         self.gen = SelfAttentionGenerator(model)
         self._call = lambda: self.gen.generate_ours_padded_batch(self.static, self.static_index)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = self._call()
-        self._pinned = ops.pinned_state(model)     # slabs / scratch the graph has raw addresses of (see ops.pinned_state)
+        self.graph, self.output, self._pinned = graphed.capture(self._call, warmup, model)
 
     def __call__(self, input=None, index=None):
         if input is not None:
-            for k in self.keys:
-                if input[k].shape != self.static[k].shape:
-                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
-                                     % (k, tuple(input[k].shape), tuple(self.static[k].shape)))
-                self.static[k].copy_(input[k])
-        if index is not None:
-            if self.static_index is None:
-                raise ValueError("the graph was captured with index=None (arg-max answers)")
-            self.static_index.copy_(torch.as_tensor(index))
+            graphed.copy_inputs(self.static, input, self.keys, hint=graphed.PAD_HINT)
+        graphed.copy_index(self.static_index, index)
         self.graph.replay()
         return self.output

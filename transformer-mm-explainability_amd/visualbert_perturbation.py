@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import graphed, ops
 from .lxmert_perturbation import PERT_STEPS, image_keep_masks, ranking
 
 # evaluation_loop.py:93-96: the image test removes regions on a finer scale near "all removed" than the text test
@@ -217,28 +217,13 @@ class GraphedVisualBertPerturbation:
         self.cams = example_cams.detach().clone()
         run = pert.perturbation_image_batch if modality == "image" else pert.perturbation_text_batch
         self._call = lambda: run(self.static, self.cams, self.positive)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = self._call()
-        self._pinned = ops.pinned_state(pert.model)
+        self.graph, self.output, self._pinned = graphed.capture(self._call, warmup, pert.model)
 
     def __call__(self, batch=None, cams=None):
         if batch is not None:
-            for k in self.KEYS:
-                if batch[k].shape != self.static[k].shape:
-                    raise ValueError("%s: %s, but the graph was captured for %s (pad the batch to the captured shape)"
-                                     % (k, tuple(batch[k].shape), tuple(self.static[k].shape)))
-                self.static[k].copy_(batch[k])
+            graphed.copy_inputs(self.static, batch, self.KEYS, hint=graphed.PAD_HINT)
         if cams is not None:
-            if cams.shape != self.cams.shape:
-                raise ValueError("cams: %s, but the graph was captured for %s" % (tuple(cams.shape), tuple(self.cams.shape)))
-            self.cams.copy_(cams)
+            graphed.copy_inputs({"cams": self.cams}, {"cams": cams})
         self.graph.replay()
         return self.output
 

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, graphed, ops
 from .capture import CaptureBuffers, attention_capture_packed
 
 
@@ -377,23 +377,22 @@ class GraphedRelevance:
         self.input = input.clone()
         self.indices = None if indices is None else torch.as_tensor(indices, device=input.device).reshape(-1).clone()
         call = lambda: generate_relevance_multi(model, self.input, self.indices, top_k)   # noqa: E731
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = call()
+        self._capture(model, call, warmup)
+
+    def _capture(self, model, call, warmup):
+        # the slabs the graph reads and writes (installed by the warm-up calls) stay alive with it
+        self.graph, self.output, self._pinned = graphed.capture(call, warmup, model, keep=lambda: (model.buffers_,))
+        self.buffers = model.buffers_
+
+    def _as_indices(self, indices):
+        return torch.as_tensor(indices, device=self.indices.device).reshape(-1)
 
     def __call__(self, input=None, indices=None):
         if input is not None:
             self.input.copy_(input)
-        if indices is not None:
-            if self.indices is None:
-                raise ValueError("this graph picks its classes itself (top_k mode)")
-            self.indices.copy_(torch.as_tensor(indices, device=self.indices.device).reshape(-1))
+        if indices is not None and self.indices is not None:
+            indices = self._as_indices(indices)
+        graphed.copy_index(self.indices, indices, "this graph picks its classes itself (top_k mode)")
         self.graph.replay()
         return self.output
 
@@ -433,17 +432,7 @@ class GraphedRelevanceBatch(GraphedRelevance):
         self.input = input.clone()
         self.indices = None if indices is None else torch.as_tensor(indices, device=input.device).reshape(-1).clone()
         call = lambda: generate_relevance_batch(model, self.input, self.indices)   # noqa: E731
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = call()
-        self.buffers = model.buffers_       # the slabs the graph reads and writes stay alive with it
-        self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
+        self._capture(model, call, warmup)
 
 
 def _fp32_body(model, who):
@@ -504,24 +493,7 @@ class GraphedRelevanceBatchMulti(GraphedRelevance):
         self.input = input.clone()
         self.indices = None if indices is None else torch.as_tensor(indices, device=input.device).clone()
         call = lambda: generate_relevance_batch_multi(model, self.input, self.indices, top_k)   # noqa: E731
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                call()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with ops.graph_capture(self.graph):
-            self.output = call()
-        self.buffers = model.buffers_       # the slabs the graph reads and writes stay alive with it
-        self._pinned_scratch = ops.pinned_state()          # grow-only scratch buffers the graph has raw addresses of
+        self._capture(model, call, warmup)
 
-    def __call__(self, input=None, indices=None):
-        if input is not None:
-            self.input.copy_(input)
-        if indices is not None:
-            if self.indices is None:
-                raise ValueError("this graph picks its classes itself (top_k mode)")
-            self.indices.copy_(torch.as_tensor(indices, device=self.indices.device).reshape(self.indices.shape))
-        self.graph.replay()
-        return self.output
+    def _as_indices(self, indices):
+        return torch.as_tensor(indices, device=self.indices.device).reshape(self.indices.shape)
