@@ -1,12 +1,14 @@
 // Argument blocks shared by the tiled (attention_kernels.hip), whole-head (attention_head.hip), streaming (attention_stream.hip)
 // and bf16-MFMA (attention_bf16.hip, attention_bf16_v3.hip) kernels.  The entries of attention_kernels.hip value-initialise one
 // (`AttnBwdArgs a{};`) and fill it once; kernels take it by value, so a new member goes behind the last one.
+// What those files share besides: attention_align.h (Strides, the one row-alignment test of the eligibility rules),
+// attention_launch.h (the launch helper and the head-dim / slab-type / key-tile dispatches), attention_bf16_words.h (device side:
+// packed-bf16 words, exp_fast, the LDS tile layouts of the bf16-MFMA generations).
 #pragma once
 #include "mmx_common.h"
+#include "attention_align.h"
 
 namespace mmx {
-
-struct Strides { int64_t sb, sh, sn; };
 
 struct AttnFwdArgs {
     const float *q, *k, *v;

@@ -20,6 +20,8 @@
 // Softmax-side arithmetic (delta, dS), accumulation and the relevancy reduction stay fp32, as in the first generation.
 #include "mmx_common.h"
 #include "attention_args.h"
+#include "attention_bf16_words.h"
+#include "attention_launch.h"
 
 #include <type_traits>
 
@@ -30,36 +32,9 @@ constexpr int kR = 64;        // query rows (query side) / keys (key side) per w
 constexpr int kT = 64;        // rows of the streamed operand per step
 constexpr int kTh = 256;
 constexpr int kDP = 64;       // padded head dim (D <= 64, D % 8 == 0)
-// LDS layouts, bank-conflict free for every access below under the lane-group rules of MI355X_MICROARCH.md (searched by
-// brute force over row strides / swizzles; the first version -- 72-element rows, no swizzle -- spent 22 % of its wave cycles
-// in SQ_LDS_BANK_CONFLICT: the transposed ds_write_b64 of 16 lanes hit 2 bank positions):
-//   row-major tile  [row][d]:  80-element (160 B) rows, no swizzle   (ds_write_b64 by (row, 4 d), ds_read_b128 by (row i, 8 g))
-//   transposed tile [d][row]:  80-element rows; the 4-row group index of a row is XOR-ed with (d / 4) & 15
-//                              (ds_write_b64 of 4 consecutive rows by 16 lanes of different d; ds_read_b64 by (d = i, group g))
-// (Unpadded 64-element rows with XOR swizzles are conflict-free too and would let THREE workgroups fit a CU, but the
-//  kernels need 162-184 VGPRs: under __launch_bounds__(256, 3) they spill 60-128 registers and run 4 x slower.)
-constexpr int kLR = kDP + 16;
-constexpr int kLT = kT + 16;
-
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned short bf16_t;
+// (LDS tile layouts kLR / kLT, the transposed tile's swizzle and the staging stores: attention_bf16_words.h)
 
 int g_attn_bf16_v2 = 1;
-
-__device__ __forceinline__ unsigned pk2(float lo, float hi) {      // two fp32 -> packed bf16 pair, round to nearest even
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    bf2 r;
-    r[0] = static_cast<__bf16>(lo);
-    r[1] = static_cast<__bf16>(hi);
-    return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4v v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 pack8(f32x4 lo, f32x4 hi) {
-    return as_bf16x8(u32x4v{pk2(lo[0], lo[1]), pk2(lo[2], lo[3]), pk2(hi[0], hi[1]), pk2(hi[2], hi[3])});
-}
-__device__ __forceinline__ float bflo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bfhi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
 // ---- a [64 rows x D] operand block in flight: thread f owns rows 4 (f / 16) .. + 3, columns 4 (f % 16) .. + 3 (a 4 x 4 block).
 // HALF: the operand is bf16 in global memory (8-byte loads), else fp32 (16-byte loads).  Raw words only: no ALU at fetch time.
@@ -92,26 +67,14 @@ __device__ __forceinline__ void block_rows(u32x2v (&rows)[4], const Block4x4<HAL
         const bool ok = blk.row0 + r4 + e < rows_total && c < D;
         u32x2v v;
         if constexpr (HALF) v = blk.raw[e];                          // (mul == 1 for the bf16 operand: dO)
-        else v = u32x2v{pk2(blk.raw[e][0] * mul, blk.raw[e][1] * mul), pk2(blk.raw[e][2] * mul, blk.raw[e][3] * mul)};
+        else v = u32x2v{pack2_bf16(blk.raw[e][0] * mul, blk.raw[e][1] * mul), pack2_bf16(blk.raw[e][2] * mul, blk.raw[e][3] * mul)};
         rows[e] = ok ? v : u32x2v{0u, 0u};
     }
 }
-__device__ __forceinline__ void store_row_major(bf16_t* tile, const u32x2v (&rows)[4], int tid) {
-    const int r4 = 4 * (tid >> 4), c = 4 * (tid & 15);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x2v*>(tile + (r4 + e) * kLR + c) = rows[e];
-}
 // transposed copy: element (row r4 + e, column c + dd) -> tile[c + dd][r4 + e]; 4 consecutive rows = one 8-byte store
 __device__ __forceinline__ void store_transposed(bf16_t* tile, const u32x2v (&rows)[4], int tid) {
-    const int c = 4 * (tid & 15);
 #pragma unroll
-    for (int dd = 0; dd < 4; ++dd) {
-        const int w = dd >> 1;
-        const unsigned sel = (dd & 1) ? 0x07060302u : 0x05040100u;     // high / low halves of (row e+1, row e)
-        const unsigned lo = __builtin_amdgcn_perm(rows[1][w], rows[0][w], sel);
-        const unsigned hi = __builtin_amdgcn_perm(rows[3][w], rows[2][w], sel);
-        *reinterpret_cast<u32x2v*>(tile + (c + dd) * kLT + 4 * ((tid >> 4) ^ (tid & 15))) = u32x2v{lo, hi};   // (c + dd) / 4 == tid & 15
-    }
+    for (int dd = 0; dd < 4; ++dd) store_transposed_col(tile, column_of(rows, dd), dd, tid);
 }
 
 // the wave's 16 rows of an operand as MFMA operand registers: lane (i, g) holds row `row`, d = 32 pr + 8 g .. + 7
@@ -128,8 +91,8 @@ __device__ __forceinline__ void load_rows8(bf16x8 (&op)[kDP / 32], const T* base
             v = *reinterpret_cast<const u32x4v*>(src);
         } else {
             const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
-            v = u32x4v{pk2(lo[0] * mul, lo[1] * mul), pk2(lo[2] * mul, lo[3] * mul), pk2(hi[0] * mul, hi[1] * mul),
-                       pk2(hi[2] * mul, hi[3] * mul)};
+            v = u32x4v{pack2_bf16(lo[0] * mul, lo[1] * mul), pack2_bf16(lo[2] * mul, lo[3] * mul), pack2_bf16(hi[0] * mul, hi[1] * mul),
+                       pack2_bf16(hi[2] * mul, hi[3] * mul)};
         }
         op[pr] = as_bf16x8(ok ? v : u32x4v{0u, 0u, 0u, 0u});
     }
@@ -155,10 +118,10 @@ __device__ __forceinline__ void tile_x_regs(f32x4 (&acc)[4], const bf16_t* tile,
 // one operand of the "contract over the tile's row index" products, from a TRANSPOSED tile [d][row]: row-slots (g, j) of
 // tile pair p (rows 32 p + 16 (j >> 2) + 4 g + (j & 3)) for d = 16 dt + i
 __device__ __forceinline__ bf16x8 transposed_operand(const bf16_t* tile, int dt, int p, int i, int g) {
-    const int sw = (4 * dt + (i >> 2)) & 15;                          // (d / 4) & 15 of d = 16 dt + i
+    const int d4 = 4 * dt + (i >> 2);                                  // d / 4 of d = 16 dt + i
     const bf16_t* row = tile + (16 * dt + i) * kLT;
-    const u32x2v lo = *reinterpret_cast<const u32x2v*>(row + 4 * ((8 * p + g) ^ sw));
-    const u32x2v hi = *reinterpret_cast<const u32x2v*>(row + 4 * ((8 * p + 4 + g) ^ sw));
+    const u32x2v lo = *reinterpret_cast<const u32x2v*>(row + transposed_slot(d4, 8 * p + g));
+    const u32x2v hi = *reinterpret_cast<const u32x2v*>(row + transposed_slot(d4, 8 * p + 4 + g));
     return as_bf16x8(u32x4v{lo[0], lo[1], hi[0], hi[1]});
 }
 
@@ -367,7 +330,7 @@ __global__ __launch_bounds__(kTh, 2) void attn_bwd_q_bf16_kernel(const AttnBwdAr
         if (d0 < a.D) {
             const f32x4 v = qacc[dt] * mul;
             if constexpr (IOH)
-                *reinterpret_cast<u32x2v*>(reinterpret_cast<bf16_t*>(a.dq) + off + d0) = u32x2v{pk2(v[0], v[1]), pk2(v[2], v[3])};
+                *reinterpret_cast<u32x2v*>(reinterpret_cast<bf16_t*>(a.dq) + off + d0) = u32x2v{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
             else
                 *reinterpret_cast<f32x4*>(a.dq + off + d0) = v;
         }
@@ -540,8 +503,8 @@ __global__ __launch_bounds__(kTh, 2) void attn_bwd_kv_bf16_kernel(const AttnBwdA
                 if (j < a.Nk && c0 < a.D) {
                     bf16_t* dk = reinterpret_cast<bf16_t*>(a.dk) + dk0 + static_cast<int64_t>(j) * a.dks.sn + c0;
                     bf16_t* dv = reinterpret_cast<bf16_t*>(a.dv) + dv0 + static_cast<int64_t>(j) * a.dvs.sn + c0;
-                    *reinterpret_cast<unsigned*>(dk) = odd ? pk2(ko, km) : pk2(km, ko);
-                    *reinterpret_cast<unsigned*>(dv) = odd ? pk2(vo, vm) : pk2(vm, vo);
+                    *reinterpret_cast<unsigned*>(dk) = odd ? pack2_bf16(ko, km) : pack2_bf16(km, ko);
+                    *reinterpret_cast<unsigned*>(dv) = odd ? pack2_bf16(vo, vm) : pack2_bf16(vm, vo);
                 }
             }
         } else {
@@ -560,42 +523,25 @@ __global__ __launch_bounds__(kTh, 2) void attn_bwd_kv_bf16_kernel(const AttnBwdA
 constexpr size_t kQLds = sizeof(bf16_t) * (2 * kT * kLR + 2 * kDP * kLT);
 constexpr size_t kKvLds = sizeof(bf16_t) * (2 * kT * kLR + 4 * kDP * kLT) + sizeof(float) * 4 * kT;
 
-template <typename K>
-int launch_v2(K kern, const AttnBwdArgs& a, dim3 grid, size_t lds, hipStream_t s, const char* name) {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    kern<<<grid, kTh, lds, s>>>(a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, name);
-    return MMX_OK;
-}
-
 template <int DT, bool IOH>
 int launch_dt_io(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
     int rc = MMX_OK;
     // the query side: dQ (and delta for the key side), the dP slab when one is wanted
-    if (a.need_dqkv || a.dprobs) rc = launch_v2(attn_bwd_q_bf16_kernel<DT, IOH>, a, gq, kQLds, s, "attn_bwd_q_bf16_kernel");
+    if (a.need_dqkv || a.dprobs) rc = launch_attn(attn_bwd_q_bf16_kernel<DT, IOH>, gq, kTh, kQLds, s, "attn_bwd_q_bf16_kernel", a);
     if (rc) return rc;
     if (a.rel_v) {
-        rc = a.need_dqkv ? launch_v2(attn_bwd_kv_bf16_kernel<DT, IOH, true, true>, a, gk, kKvLds, s, "attn_bwd_kv_bf16_kernel<rel>")
-                         : launch_v2(attn_bwd_kv_bf16_kernel<DT, IOH, true, false>, a, gk, kKvLds, s, "attn_bwd_kv_bf16_kernel<rel only>");
+        rc = a.need_dqkv ? launch_attn(attn_bwd_kv_bf16_kernel<DT, IOH, true, true>, gk, kTh, kKvLds, s, "attn_bwd_kv_bf16_kernel<rel>", a)
+                         : launch_attn(attn_bwd_kv_bf16_kernel<DT, IOH, true, false>, gk, kTh, kKvLds, s, "attn_bwd_kv_bf16_kernel<rel only>", a);
         if (rc) return rc;
         return rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);     // one partial row per head
     }
-    if (a.need_dqkv) rc = launch_v2(attn_bwd_kv_bf16_kernel<DT, IOH, false, true>, a, gk, kKvLds, s, "attn_bwd_kv_bf16_kernel");
+    if (a.need_dqkv) rc = launch_attn(attn_bwd_kv_bf16_kernel<DT, IOH, false, true>, gk, kTh, kKvLds, s, "attn_bwd_kv_bf16_kernel", a);
     return rc;
 }
 
 template <int DT>
 int launch_dt(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
     return a.io_bf16 ? launch_dt_io<DT, true>(a, gq, gk, s) : launch_dt_io<DT, false>(a, gq, gk, s);
-}
-
-bool al16(const void* p, const Strides& s, int elem) {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (s.sb * elem) % 16 == 0 && (s.sh * elem) % 16 == 0 && (s.sn * elem) % 16 == 0;
 }
 
 }  // namespace
@@ -606,23 +552,15 @@ void attn_bf16_v2_enable(int on) { g_attn_bf16_v2 = on & 1; }
 // bf16-MFMA mode with the forward's O at hand, head_dim % 8 == 0 (<= 64), 16-byte aligned operand rows.
 int attn_bwd_bf16_try(const AttnBwdArgs& a, hipStream_t s, int* rc_out) {
     if (!g_attn_bf16_v2 || !a.mma_bf16 || !a.o || a.D % 8 || a.D > kDP) return 0;
-    if (!al16(a.v, a.vs, 4) || !al16(a.o, a.oos, 4) || !al16(a.dout, a.os, a.io_bf16 ? 2 : 4)) return 0;
+    const int e = a.io_bf16 ? 2 : 4;                                      // bytes of a gradient element
+    if (!rows_aligned(a.v, a.vs, 4, 16, true) || !rows_aligned(a.o, a.oos, 4, 16, true) || !rows_aligned(a.dout, a.os, e, 16, true)) return 0;
     if (a.need_dqkv) {
-        if (!al16(a.q, a.qs, 4) || !al16(a.k, a.ks, 4)) return 0;
-        const int e = a.io_bf16 ? 2 : 4;
-        if (!al16(a.dq, a.dqs, e) || reinterpret_cast<uintptr_t>(a.dk) % 4 || reinterpret_cast<uintptr_t>(a.dv) % 4 ||
-            (a.dks.sn * e) % 4 || (a.dvs.sn * e) % 4 || (a.dks.sh * e) % 4 || (a.dvs.sh * e) % 4 || (a.dks.sb * e) % 4 ||
-            (a.dvs.sb * e) % 4)
-            return 0;
+        if (!rows_aligned(a.q, a.qs, 4, 16, true) || !rows_aligned(a.k, a.ks, 4, 16, true)) return 0;
+        // (dK / dV leave as single floats or (d, d + 1) bf16 pairs: 4-byte stores)
+        if (!rows_aligned(a.dq, a.dqs, e, 16, true) || !rows_aligned(a.dk, a.dks, e, 4, true) || !rows_aligned(a.dv, a.dvs, e, 4, true)) return 0;
     }
     dim3 gq(((a.Nq + kR - 1) / kR) * a.H * a.B), gk(((a.Nk + kR - 1) / kR) * a.H * a.B);
-    switch (a.slab_dt) {
-        case MMX_F32: *rc_out = launch_dt<MMX_F32>(a, gq, gk, s); break;
-        case MMX_F16: *rc_out = launch_dt<MMX_F16>(a, gq, gk, s); break;
-        case MMX_BF16: *rc_out = launch_dt<MMX_BF16>(a, gq, gk, s); break;
-        default: return 0;
-    }
-    return 1;
+    return by_slab_dtype(a.slab_dt, [&](auto dt) { *rc_out = launch_dt<decltype(dt)::value>(a, gq, gk, s); });
 }
 
 }  // namespace mmx

@@ -1,7 +1,7 @@
 // Third generation of the bf16-matrix-core attention BACKWARD, for the configuration BASELINE config 5 runs (CLIP
 // ViT-L/14@336, 577 tokens x 64, batch 128 per GPU): SHARED forward (q / k / v / P of ONE image, batch stride 0), bf16 gradient
 // stream (dO in, dq / dk / dv out), row-relevancy mode (no dP slab), q * d^-0.5 first.  Everything else stays on the
-// second generation (attention_bf16.hip), whose tile arithmetic this file keeps.
+// second generation (attention_bf16.hip), whose LDS tile layouts this file shares (attention_bf16_words.h).
 //
 // What the second generation paid per workgroup and per tile although the operands are the same for all B samples
 // (profiles/r02_cfg5_probe.txt: 21-26 % of the wave cycles in VALU at 2 waves / SIMD, 36-51 % parked):
@@ -23,8 +23,9 @@
 // registers are live at a time (the second generation's 162-184 VGPRs capped it at 2 waves per SIMD).
 #include "mmx_common.h"
 #include "attention_args.h"
+#include "attention_bf16_words.h"
+#include "attention_launch.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace mmx {
@@ -32,47 +33,19 @@ namespace {
 
 constexpr int kT = 64;        // rows of the streamed operand per step
 constexpr int kD = 64;        // head dim (exactly)
-constexpr int kLR = kD + 16;  // row-major LDS tile [row][d]: 80-element rows (conflict-free, see attention_bf16.hip)
-constexpr int kLT = kT + 16;  // transposed LDS tile [d][row]: 80-element rows, 4-row group index XOR (d / 4) & 15
-
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned short bf16_t;
+constexpr int kNW = 8;        // waves per workgroup of the third-generation pair: 128 query rows / keys, 4 waves per SIMD
+// (LDS tiles: the second generation's row-major [row][d] and swizzled transposed [d][row] layouts, attention_bf16_words.h)
 
 int g_attn_bf16_v3 = 3;       // 3 (default, round 6): query side as below, key side attn_bwd_kv_v4_kernel (32 keys per wave, 32x32x16 MFMA,
-                              // transpose reads) | 2: the third-generation pair |
-                              // 0: off (the call falls through to the second generation, attention_bf16.hip: the A / B arm of
-                              // test_bf16_backward_third_generation_equals_second), non-zero: 8-wave workgroups, 4 waves / SIMD on both kernels
-                              // (measured and removed in round 5: 4-wave workgroups; a fourth-generation key side with several key
-                              // blocks per wave -- 882-980 us vs 780 us per layer pair, profiles/r04_cfg5_probe.txt)
+                              // transpose reads) | 2 (any other non-zero value): the third-generation pair, 8-wave workgroups at
+                              // 4 waves / SIMD | 0: off (the call falls through to the second generation, attention_bf16.hip: the
+                              // A / B arm of test_bf16_backward_third_generation_equals_second)
 
 struct V3Images {
     const bf16_t *Vb, *KbT, *QbT, *Pq, *PT;
     int Np;
     const bf16_t *Qb, *PT32;      // fourth-generation key side: (scale q) rows, row-major like Vb; P^T blocked for 32-key waves
 };
-
-__device__ __forceinline__ unsigned pk2(float lo, float hi) {      // two fp32 -> packed bf16 pair, round to nearest even
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    bf2 r;
-    r[0] = static_cast<__bf16>(lo);
-    r[1] = static_cast<__bf16>(hi);
-    return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4v v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 pack8(f32x4 lo, f32x4 hi) {
-    return as_bf16x8(u32x4v{pk2(lo[0], lo[1]), pk2(lo[2], lo[3]), pk2(hi[0], hi[1]), pk2(hi[2], hi[3])});
-}
-__device__ __forceinline__ float bflo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bfhi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ f32x4 unpack4(u32x2v w) { return f32x4{bflo(w[0]), bfhi(w[0]), bflo(w[1]), bfhi(w[1])}; }
-
-// 4 rows x 4 columns of bf16 (rows[e] = columns c, c+1 | c+2, c+3 of row e) -> column dd as 4 consecutive rows (8 bytes)
-__device__ __forceinline__ u32x2v column_of(const u32x2v (&rows)[4], int dd) {
-    const int w = dd >> 1;
-    const unsigned sel = (dd & 1) ? 0x07060302u : 0x05040100u;
-    return u32x2v{__builtin_amdgcn_perm(rows[1][w], rows[0][w], sel), __builtin_amdgcn_perm(rows[3][w], rows[2][w], sel)};
-}
 
 // ======================================================================================================= prep kernels
 // which = 0: Vb (row-major), 1: KbT, 2: QbT (times scale).  One workgroup per (64-row tile, head, which); fp32 in, 16-byte
@@ -90,7 +63,7 @@ __global__ __launch_bounds__(256) void prep_qkv_kernel(const AttnBwdArgs a, bf16
         rows[e] = u32x2v{0u, 0u};
         if (row < a.Nk) {
             const f32x4 x = *reinterpret_cast<const f32x4*>(base + static_cast<int64_t>(row) * sn + c);
-            rows[e] = u32x2v{pk2(x[0] * mul, x[1] * mul), pk2(x[2] * mul, x[3] * mul)};
+            rows[e] = u32x2v{pack2_bf16(x[0] * mul, x[1] * mul), pack2_bf16(x[2] * mul, x[3] * mul)};
         }
     }
     if (which == 0 || which == 3) {
@@ -178,17 +151,17 @@ __device__ __forceinline__ void load_rows8(bf16x8 (&op)[kD / 32], const bf16_t* 
 
 // one operand of the "contract over the tile's row index" products, from a TRANSPOSED tile [d][row]: row-slots (g, j) of
 // tile pair p (rows 32 p + 16 (j >> 2) + 4 g + (j & 3)) for d = 16 dt + i.  The swizzled 4-row group index
-// (8 p + 4 hi + g) ^ ((4 dt + (i >> 2)) & 15) splits into a per-lane part (g ^ (i >> 2), bits 0-1) and a compile-time part
-// (dt ^ (2 p + hi), bits 2-3), so ONE lane address (transposed_lane_base) + immediate offsets serve all 16 reads of a tile
+// (8 p + 4 hi + g) ^ ((4 dt + (i >> 2)) & 15) (transposed_slot) splits into a per-lane part (g ^ (i >> 2), bits 0-1) and a compile-time
+// part (4 (dt ^ (2 p + hi)), bits 2-3), so ONE lane address (transposed_lane_base) + immediate offsets serve all 16 reads of a tile
 // (written with the XOR on the whole index the compiler kept 16-32 address registers live across the loop).
-__device__ __forceinline__ int transposed_lane_base(int i, int g) { return i * kLT + 4 * (g ^ (i >> 2)); }
+__device__ __forceinline__ int transposed_lane_base(int i, int g) { return i * kLT + transposed_slot(i >> 2, g); }
 __device__ __forceinline__ bf16x8 transposed_operand(const bf16_t* tile_lane, int dt, int p) {
     // two SEPARATE ds_read_b64 (2 LDS cycles each) instead of the ds_read2_b64 hipcc merges them into (8 cycles: each of its two
     // accesses is serviced as 4 x 16 lanes) -- and no register shuffle when the pieces come out in descending address order
     // (volatile keeps the two loads apart; the explicit LDS address space keeps them ds_read -- a volatile generic load is a flat_load)
     typedef const volatile __attribute__((address_space(3))) u32x2v* lds_b64_ptr;
-    const u32x2v lo = *(lds_b64_ptr)(tile_lane + 16 * dt * kLT + 16 * (dt ^ (2 * p)));
-    const u32x2v hi = *(lds_b64_ptr)(tile_lane + 16 * dt * kLT + 16 * (dt ^ (2 * p + 1)));
+    const u32x2v lo = *(lds_b64_ptr)(tile_lane + 16 * dt * kLT + transposed_slot(4 * dt, 8 * p));
+    const u32x2v hi = *(lds_b64_ptr)(tile_lane + 16 * dt * kLT + transposed_slot(4 * dt, 8 * p + 4));
     return as_bf16x8(u32x4v{lo[0], lo[1], hi[0], hi[1]});
 }
 
@@ -198,11 +171,6 @@ __device__ __forceinline__ void fetch_row_major(RawBlock& blk, const bf16_t* img
     const int r4 = 4 * (st >> 4), c = 4 * (st & 15);
 #pragma unroll
     for (int e = 0; e < 4; ++e) blk.raw[e] = *reinterpret_cast<const u32x2v*>(img + static_cast<int64_t>(row0 + r4 + e) * sn + c);
-}
-__device__ __forceinline__ void store_row_major(bf16_t* tile, const u32x2v (&rows)[4], int st) {
-    const int r4 = 4 * (st >> 4), c = 4 * (st & 15);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x2v*>(tile + (r4 + e) * kLR + c) = rows[e];
 }
 // the same block of a TRANSPOSED operand: raw[dd] = rows row0 + r4 .. + 3 of d = c + dd, from the staging-blocked image
 // [tile][thread][dd][4 rows] of one head (prep_qkv_kernel): 32 contiguous bytes per thread.  (Rounds 3-4 kept a [d][row] image:
@@ -217,29 +185,27 @@ __device__ __forceinline__ void fetch_transposed(RawBlock& blk, const bf16_t* im
     blk.raw[3] = u32x2v{hi[2], hi[3]};
 }
 __device__ __forceinline__ void store_transposed_raw(bf16_t* tile, const u32x2v (&cols)[4], int st) {
-    const int c = 4 * (st & 15);
 #pragma unroll
-    for (int dd = 0; dd < 4; ++dd)
-        *reinterpret_cast<u32x2v*>(tile + (c + dd) * kLT + 4 * ((st >> 4) ^ (st & 15))) = cols[dd];
+    for (int dd = 0; dd < 4; ++dd) store_transposed_col(tile, cols[dd], dd, st);
 }
 
 // ===================================================================================================== query side
 // delta = rowsum(dO * O), dP^T = V . dO^T, dS, dQ = dS . K  (orientation and accumulator layouts: attention_bf16.hip)
 //
-// A workgroup owns 16 NW query rows of NS consecutive SAMPLES of one head: the V / K tiles, the probabilities and every LDS
+// A workgroup owns 16 kNW query rows of NS consecutive SAMPLES of one head: the V / K tiles, the probabilities and every LDS
 // operand read of a tile are the same for all samples (shared forward), so they are fetched ONCE and used NS times -- the
 // shared operands were 3.3 GB of L2 -> CU traffic per launch at one sample per workgroup (4.7 TB/s, i.e. what bounded it).
 // Loads run TWO tiles ahead of their use (two register sets, loop unrolled by two): with one set the fetch of tile t + 2 could
 // only be issued after the wait for tile t + 1, so at most one tile per workgroup was ever in flight.
-template <int NW, int NS, int ABL = 0>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_q_v3_kernel(const AttnBwdArgs a, const V3Images im) {
-    constexpr int NB = kD / 16, R = 16 * NW, NOP = NW == 4 ? 2 : 1;
+template <int NS>
+__global__ __launch_bounds__(64 * kNW, 4) void attn_bwd_q_v3_kernel(const AttnBwdArgs a, const V3Images im) {
+    constexpr int NB = kD / 16, R = 16 * kNW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16_t* Vt = reinterpret_cast<bf16_t*>(smem_raw);                 // [2][kT][kLR]   V rows (row-major)
     bf16_t* Kt = Vt + 2 * kT * kLR;                                   // [2][kD][kLT]   K transposed
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
     const int st = tid & 255;
-    const bool stage_v = NW == 4 || tid < 256;
+    const bool stage_v = tid < 256;
     const int nrt = (a.Nq + R - 1) / R, nbg = (a.B + NS - 1) / NS;
     const int wg = xcd_contiguous_id(blockIdx.x, gridDim.x);
     // row tile fastest, then the sample group, the head slowest: the workgroups an XCD runs at a time (a contiguous id range)
@@ -286,8 +252,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_q_v3_kernel
 #pragma unroll
         for (int dt = 0; dt < NB; ++dt) qacc[s][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // NW == 4: every thread stages a block of V and one of K; NW == 8: waves 0-3 stage V, waves 4-7 K (ONE block per set)
-    RawBlock rs[2][NOP];
+    // waves 0-3 stage V, waves 4-7 K (ONE block per set)
+    RawBlock rs[2];
     // [half pp]: the words of sub-tiles 2 pp, 2 pp + 1.  The products read p_cur, which is only ever COPIED (top of `body`) out of
     // p_nxt, the destination of the loads: with the words loaded straight into the registers the MFMAs read (rounds 3-5: two sets,
     // two tiles ahead) hipcc's wait-count pass -- which merges the pending-load state of the prologue, the early exits and the
@@ -296,23 +262,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_q_v3_kernel
     u32x4v p_cur[2], p_nxt[2];
     auto fetch = [&](int kt, auto set) {
         constexpr int S = decltype(set)::value;
-        if constexpr (NW == 4) {
-            fetch_row_major(rs[S][0], vimg, kD, kt * kT, st);
-            fetch_transposed(rs[S][1], kimg, im.Np, kt * kT, st);
-        } else {
-            if (stage_v) fetch_row_major(rs[S][0], vimg, kD, kt * kT, st);
-            else fetch_transposed(rs[S][0], kimg, im.Np, kt * kT, st);
-        }
+        if (stage_v) fetch_row_major(rs[S], vimg, kD, kt * kT, st);
+        else fetch_transposed(rs[S], kimg, im.Np, kt * kT, st);
     };
     auto stage = [&](int buf, auto set) {
         constexpr int S = decltype(set)::value;
-        if constexpr (NW == 4) {
-            store_row_major(Vt + buf * kT * kLR, rs[S][0].raw, st);
-            store_transposed_raw(Kt + buf * kD * kLT, rs[S][1].raw, st);
-        } else {
-            if (stage_v) store_row_major(Vt + buf * kT * kLR, rs[S][0].raw, st);
-            else store_transposed_raw(Kt + buf * kD * kLT, rs[S][0].raw, st);
-        }
+        if (stage_v) store_row_major(Vt + buf * kT * kLR, rs[S].raw, st);
+        else store_transposed_raw(Kt + buf * kD * kLT, rs[S].raw, st);
     };
     auto p_issue = [&](u32x4v (&raw)[2], int kt) {
 #pragma unroll
@@ -324,8 +280,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_q_v3_kernel
         p_cur[0] = p_nxt[0];
         p_cur[1] = p_nxt[1];
         if (kt + 1 < ntiles) p_issue(p_nxt, kt + 1);                   // consumed one iteration from now
-        if (ABL != 2 && ABL != 6 && kt + 2 < ntiles) fetch(kt + 2, par);   // this set's tile kt went to LDS one iteration ago
-        if (ABL != 2 && ABL != 6 && kt + 1 < ntiles) stage(1 - PAR, std::integral_constant<int, 1 - PAR>{});   // waits for THAT set only
+        if (kt + 2 < ntiles) fetch(kt + 2, par);                       // this set's tile kt went to LDS one iteration ago
+        if (kt + 1 < ntiles) stage(1 - PAR, std::integral_constant<int, 1 - PAR>{});   // waits for THAT set only
         const bf16_t* Vcur = Vt + PAR * kT * kLR;
         const bf16_t* Kcur = Kt + PAR * kD * kLT + tlane;
 #pragma unroll
@@ -345,8 +301,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_q_v3_kernel
                         dpT[hh] = mfma16x16x32_bf16(op, dob[s][pr], dpT[hh]);
                     }
                 // dS[q][key] = P * (dP - delta) for keys 16 t + 4 g + r, t = 2 pp + hh (scale_mode Q_FIRST: no further factor)
-                dsb[s] = pack8(unpack4(u32x2v{p_cur[pp][0], p_cur[pp][1]}) * (dpT[0] - delta[s]),
-                               unpack4(u32x2v{p_cur[pp][2], p_cur[pp][3]}) * (dpT[1] - delta[s]));
+                dsb[s] = pack8(widen_bf16x4(u32x2v{p_cur[pp][0], p_cur[pp][1]}) * (dpT[0] - delta[s]),
+                               widen_bf16x4(u32x2v{p_cur[pp][2], p_cur[pp][3]}) * (dpT[1] - delta[s]));
                 // the V operands are RE-READ from LDS for the next sample (16 registers the budget of 4 waves / SIMD does not
                 // have): the clobber keeps the compiler from carrying them over
                 asm volatile("" ::: "memory");
@@ -380,17 +336,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_q_v3_kernel
 #pragma unroll
         for (int dt = 0; dt < NB; ++dt) {
             const f32x4 v = qacc[s][dt] * a.scale;
-            *reinterpret_cast<u32x2v*>(reinterpret_cast<bf16_t*>(a.dq) + off + 16 * dt + 4 * g) = u32x2v{pk2(v[0], v[1]), pk2(v[2], v[3])};
+            *reinterpret_cast<u32x2v*>(reinterpret_cast<bf16_t*>(a.dq) + off + 16 * dt + 4 * g) = u32x2v{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
         }
     }
 }
 
 // ===================================================================================================== key side
-// per 16 NW keys: dP recomputed, dV = P^T . dO, dK = dS^T . Q (DKV), and the row-relevancy partial of this head
+// per 16 kNW keys: dP recomputed, dV = P^T . dO, dK = dS^T . Q (DKV), and the row-relevancy partial of this head
 // rel_part[b][h][key] = sum_q rel_v[b][q] * clamp(dP * P, 0)[q][key]
-template <int NW, bool DKV, int ABL = 0>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kernel(const AttnBwdArgs a, const V3Images im) {
-    constexpr int NB = kD / 16, R = 16 * NW;
+template <bool DKV>
+__global__ __launch_bounds__(64 * kNW, 4) void attn_bwd_kv_v3_kernel(const AttnBwdArgs a, const V3Images im) {
+    constexpr int NB = kD / 16, R = 16 * kNW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16_t* dOr = reinterpret_cast<bf16_t*>(smem_raw);                // [2][kT][kLR]   dO rows (row-major)
     bf16_t* dOt = dOr + 2 * kT * kLR;                                 // [2][kD][kLT]   dO transposed
@@ -399,7 +355,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kerne
     float* vl = dl + 2 * kT;                                          // [2][kT]        rel_v of the staged query rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
     const int st = tid & 255;
-    const bool stage_do = NW == 4 || tid < 256, stage_q = DKV && (NW == 4 || tid >= 256);
+    const bool stage_do = tid < 256, stage_q = DKV && tid >= 256;
     const int nkt = (a.Nk + R - 1) / R;
     const int wg = xcd_contiguous_id(blockIdx.x, gridDim.x);
     const int b = (wg / nkt) % a.B, h = wg / (nkt * a.B);          // key tile fastest, then the sample, the head slowest (see the query side)
@@ -423,8 +379,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kerne
 
     const int ntiles = (a.Nq + kT - 1) / kT;
     const int tlane = transposed_lane_base(i, g);
-    RawBlock doreg, qreg_;
-    RawBlock& qreg = NW == 4 ? qreg_ : doreg;                        // NW == 8: waves 4-7 stage Q, ONE register block per thread
+    RawBlock doreg;
+    RawBlock& qreg = doreg;                                          // waves 4-7 stage Q: ONE register block per thread
     int do_row0 = 0;
     float dlreg = 0.f, vlreg = 0.f, racc = 0.f;
     auto fetch = [&](int qt) {
@@ -475,9 +431,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kerne
     for (int qt = 0; qt < ntiles; ++qt) {
         const int cur = qt & 1;
         if (qt + 1 < ntiles) {
-            if (ABL != 2 && ABL != 6) stage(cur ^ 1);
+            stage(cur ^ 1);
             p_issue(p_nxt, qt + 1);
-            if (ABL != 2 && ABL != 6 && qt + 2 < ntiles) fetch(qt + 2);
+            if (qt + 2 < ntiles) fetch(qt + 2);
         }
         const bf16_t* dOrc = dOr + cur * kT * kLR;
         const bf16_t* dOtc = dOt + cur * kD * kLT + tlane;
@@ -499,13 +455,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kerne
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 const int t = 2 * pp + hh;
-                const f32x4 p = unpack4(u32x2v{p_cur[pp][2 * hh], p_cur[pp][2 * hh + 1]});
+                const f32x4 p = widen_bf16x4(u32x2v{p_cur[pp][2 * hh], p_cur[pp][2 * hh + 1]});
                 const f32x4 vv = *reinterpret_cast<const f32x4*>(vl + cur * kT + 16 * t + 4 * g);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (ABL == 3 || ABL == 7) racc += dp[hh][r];
-                    else racc += vv[r] * relu_nan(p[r] * dp[hh][r]);
-                }
+                for (int r = 0; r < 4; ++r) racc += vv[r] * relu_nan(p[r] * dp[hh][r]);
                 if constexpr (DKV) {
                     const f32x4 dlv = *reinterpret_cast<const f32x4*>(dl + cur * kT + 16 * t + 4 * g);
                     ds[hh] = p * (dp[hh] - dlv);
@@ -516,7 +469,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kerne
                 // (the two 8-byte pieces of a transposed operand are read with two SEPARATE ds_read_b64: no merge into a half-rate
                 // ds_read2_b64, no register shuffle)
                 const bf16x8 p_op = as_bf16x8(p_cur[pp]);
-                const bf16x8 ds_op = ABL == 4 || ABL == 7 ? p_op : pack8(ds[0], ds[1]);
+                const bf16x8 ds_op = pack8(ds[0], ds[1]);
 #pragma unroll
                 for (int dt = 0; dt < NB; ++dt) {
                     vacc[dt] = mfma16x16x32_bf16(p_op, transposed_operand(dOtc, dt, pp), vacc[dt]);
@@ -557,8 +510,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) void attn_bwd_kv_v3_kerne
             if (j < a.Nk) {
                 bf16_t* dk = reinterpret_cast<bf16_t*>(a.dk) + dk0 + static_cast<int64_t>(j) * a.dks.sn + c0;
                 bf16_t* dv = reinterpret_cast<bf16_t*>(a.dv) + dv0 + static_cast<int64_t>(j) * a.dvs.sn + c0;
-                *reinterpret_cast<unsigned*>(dk) = odd ? pk2(ko, km) : pk2(km, ko);
-                *reinterpret_cast<unsigned*>(dv) = odd ? pk2(vo, vm) : pk2(vm, vo);
+                *reinterpret_cast<unsigned*>(dk) = odd ? pack2_bf16(ko, km) : pack2_bf16(km, ko);
+                *reinterpret_cast<unsigned*>(dv) = odd ? pack2_bf16(vo, vm) : pack2_bf16(vm, vo);
             }
         }
     }
@@ -710,7 +663,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_v4_kernel(const AttnBwdArg
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) {
                 const u32x4v w = p_cur[pp][rg >> 1];
-                const f32x4 p = unpack4(u32x2v{w[2 * (rg & 1)], w[2 * (rg & 1) + 1]});
+                const f32x4 p = widen_bf16x4(u32x2v{w[2 * (rg & 1)], w[2 * (rg & 1) + 1]});
                 const f32x4 vv = *reinterpret_cast<const f32x4*>(vl + cur * kT + 32 * pp + 8 * rg + 4 * hi);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) racc += vv[e] * relu_nan(p[e] * dp[4 * rg + e]);
@@ -755,8 +708,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_v4_kernel(const AttnBwdArg
             if (j < a.Nk) {
                 bf16_t* dk = reinterpret_cast<bf16_t*>(a.dk) + dk0 + static_cast<int64_t>(j) * a.dks.sn + c0;
                 bf16_t* dv = reinterpret_cast<bf16_t*>(a.dv) + dv0 + static_cast<int64_t>(j) * a.dvs.sn + c0;
-                *reinterpret_cast<unsigned*>(dk) = odd ? pk2(ko, km) : pk2(km, ko);
-                *reinterpret_cast<unsigned*>(dv) = odd ? pk2(vo, vm) : pk2(vm, vo);
+                *reinterpret_cast<unsigned*>(dk) = odd ? pack2_bf16(ko, km) : pack2_bf16(km, ko);
+                *reinterpret_cast<unsigned*>(dv) = odd ? pack2_bf16(vo, vm) : pack2_bf16(vm, vo);
             }
         }
     }
@@ -765,65 +718,24 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_v4_kernel(const AttnBwdArg
 constexpr size_t kQLds = sizeof(bf16_t) * (2 * kT * kLR + 2 * kD * kLT);
 constexpr size_t kKvLds = sizeof(bf16_t) * (2 * kT * kLR + 4 * kD * kLT) + sizeof(float) * 4 * kT;
 
-template <typename K>
-int launch_v3(K kern, const AttnBwdArgs& a, const V3Images& im, dim3 grid, int threads, size_t lds, hipStream_t s, const char* name) {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    kern<<<grid, threads, lds, s>>>(a, im);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, name);
-    return MMX_OK;
-}
-
-template <int NW>
 int run_v3(const AttnBwdArgs& a, const V3Images& im, hipStream_t s) {
-    constexpr int R = 16 * NW;
+    constexpr int R = 16 * kNW;
     constexpr int NS = 2;                                                // samples per query-side workgroup
-    dim3 gq(((a.Nq + R - 1) / R) * a.H * ((a.B + NS - 1) / NS)), gk(((a.Nk + R - 1) / R) * a.H * a.B);
+    const dim3 gq(((a.Nq + R - 1) / R) * a.H * ((a.B + NS - 1) / NS)), gk(((a.Nk + R - 1) / R) * a.H * a.B);
     int rc = MMX_OK;
-    const bool wide = g_attn_bf16_v3 >= 3;                              // fourth-generation key side (32 keys per wave)
-    const dim3 gk4(((a.Nk + 127) / 128) * a.H * a.B);
-    if (wide) {
+    if (a.need_dqkv) rc = launch_attn(attn_bwd_q_v3_kernel<NS>, gq, 64 * kNW, kQLds, s, "attn_bwd_q_v3_kernel", a, im);
+    if (rc) return rc;
+    if (g_attn_bf16_v3 >= 3) {                                           // fourth-generation key side (32 keys per wave)
         constexpr size_t lds4 = sizeof(bf16_t) * 4 * kT * kLR + sizeof(float) * 4 * kT;
-        if (a.need_dqkv) {
-            rc = launch_v3(attn_bwd_q_v3_kernel<NW, NS>, a, im, gq, 64 * NW, kQLds, s, "attn_bwd_q_v3_kernel");
-            if (rc) return rc;
-            rc = launch_v3(attn_bwd_kv_v4_kernel<true>, a, im, gk4, 256, lds4, s, "attn_bwd_kv_v4_kernel");
-        } else {
-            rc = launch_v3(attn_bwd_kv_v4_kernel<false>, a, im, gk4, 256, lds4, s, "attn_bwd_kv_v4_kernel<rel only>");
-        }
-        if (rc) return rc;
-        return rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);
-    }
-    if (a.need_dqkv) {
-#ifdef MMX_ATTN_ABLATE
-        static const int abl = getenv("MMX_ATTN_ABLATE") ? atoi(getenv("MMX_ATTN_ABLATE")) : 0;
-        auto qk = abl == 1 ? attn_bwd_q_v3_kernel<NW, NS, 1> : abl == 2 ? attn_bwd_q_v3_kernel<NW, NS, 2>
-                : abl == 6 ? attn_bwd_q_v3_kernel<NW, NS, 6> : attn_bwd_q_v3_kernel<NW, NS, 0>;
-        rc = launch_v3(qk, a, im, gq, 64 * NW, kQLds, s, "attn_bwd_q_v3_kernel");
-        if (rc) return rc;
-        auto kern = abl == 1 ? attn_bwd_kv_v3_kernel<NW, true, 1> : abl == 2 ? attn_bwd_kv_v3_kernel<NW, true, 2>
-                  : abl == 3 ? attn_bwd_kv_v3_kernel<NW, true, 3> : abl == 4 ? attn_bwd_kv_v3_kernel<NW, true, 4>
-                  : abl == 6 ? attn_bwd_kv_v3_kernel<NW, true, 6> : abl == 7 ? attn_bwd_kv_v3_kernel<NW, true, 7>
-                                                                                 : attn_bwd_kv_v3_kernel<NW, true, 0>;
-        rc = launch_v3(kern, a, im, gk, 64 * NW, kKvLds, s, "attn_bwd_kv_v3_kernel");
-#else
-        rc = launch_v3(attn_bwd_q_v3_kernel<NW, NS>, a, im, gq, 64 * NW, kQLds, s, "attn_bwd_q_v3_kernel");
-        if (rc) return rc;
-        rc = launch_v3(attn_bwd_kv_v3_kernel<NW, true>, a, im, gk, 64 * NW, kKvLds, s, "attn_bwd_kv_v3_kernel");
-#endif
+        const dim3 gk4(((a.Nk + 127) / 128) * a.H * a.B);
+        rc = a.need_dqkv ? launch_attn(attn_bwd_kv_v4_kernel<true>, gk4, 256, lds4, s, "attn_bwd_kv_v4_kernel", a, im)
+                         : launch_attn(attn_bwd_kv_v4_kernel<false>, gk4, 256, lds4, s, "attn_bwd_kv_v4_kernel<rel only>", a, im);
     } else {
-        rc = launch_v3(attn_bwd_kv_v3_kernel<NW, false>, a, im, gk, 64 * NW, kKvLds, s, "attn_bwd_kv_v3_kernel<rel only>");
+        rc = a.need_dqkv ? launch_attn(attn_bwd_kv_v3_kernel<true>, gk, 64 * kNW, kKvLds, s, "attn_bwd_kv_v3_kernel", a, im)
+                         : launch_attn(attn_bwd_kv_v3_kernel<false>, gk, 64 * kNW, kKvLds, s, "attn_bwd_kv_v3_kernel<rel only>", a, im);
     }
     if (rc) return rc;
     return rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);     // one partial row per head
-}
-
-bool al16(const void* p, const Strides& s, int elem) {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && (s.sh * elem) % 16 == 0 && (s.sn * elem) % 16 == 0;
 }
 
 }  // namespace
@@ -843,12 +755,13 @@ int attn_bwd_bf16_v3_try(const AttnBwdArgs& a, void* prep, size_t prep_bytes, hi
     if (a.D != kD || a.slab_dt != MMX_BF16 || a.scale_mode != MMX_SCALE_Q_FIRST || a.Nq != a.Nk) return 0;
     if (a.probs_sb != 0 || a.vs.sb != 0 || a.oos.sb != 0 || (a.need_dqkv && (a.qs.sb != 0 || a.ks.sb != 0))) return 0;
     if (!prep || prep_bytes < attn_bwd_bf16_v3_prep_bytes(a.H, a.Nk)) return 0;
-    if (!al16(a.v, a.vs, 4) || !al16(a.o, a.oos, 4) || !al16(a.dout, a.os, 2) || (a.os.sb * 2) % 16) return 0;
+    // (v / o, and q / k where they are read, are shared: batch stride 0 above)
+    if (!rows_aligned(a.v, a.vs, 4, 16, false) || !rows_aligned(a.o, a.oos, 4, 16, false) || !rows_aligned(a.dout, a.os, 2, 16, true)) return 0;
     if (a.need_dqkv) {
-        if (!al16(a.q, a.qs, 4) || !al16(a.k, a.ks, 4)) return 0;
-        if (!al16(a.dq, a.dqs, 2) || (a.dqs.sb * 2) % 8 || reinterpret_cast<uintptr_t>(a.dk) % 4 || reinterpret_cast<uintptr_t>(a.dv) % 4 ||
-            (a.dks.sn * 2) % 4 || (a.dvs.sn * 2) % 4 || (a.dks.sh * 2) % 4 || (a.dvs.sh * 2) % 4 || (a.dks.sb * 2) % 4 ||
-            (a.dvs.sb * 2) % 4)
+        if (!rows_aligned(a.q, a.qs, 4, 16, false) || !rows_aligned(a.k, a.ks, 4, 16, false)) return 0;
+        // dq: 16-byte rows per sample, the samples 8 bytes apart at least; dk / dv leave as (d, d + 1) pairs: 4-byte stores
+        if (!rows_aligned(a.dq, a.dqs, 2, 16, false) || (a.dqs.sb * 2) % 8 || !rows_aligned(a.dk, a.dks, 2, 4, true) ||
+            !rows_aligned(a.dv, a.dvs, 2, 4, true))
             return 0;
     }
     const int Np = (a.Nk + kT - 1) / kT * kT;
@@ -867,7 +780,7 @@ int attn_bwd_bf16_v3_try(const AttnBwdArgs& a, void* prep, size_t prep_bytes, hi
     e = hipGetLastError();
     if (e != hipSuccess) { *rc_out = hip_fail(e, "prep_p_kernel"); return 1; }
     const V3Images im{Vb, KbT, QbT, Pq, PT, Np, Qb, PT};
-    *rc_out = run_v3<8>(a, im, s);
+    *rc_out = run_v3(a, im, s);
     return 1;
 }
 

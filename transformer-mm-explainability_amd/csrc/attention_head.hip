@@ -26,24 +26,14 @@
 // Nq <= 256, 16-byte aligned q / k / v / dO rows.
 #include "mmx_common.h"
 #include "attention_args.h"
+#include "attention_bf16_words.h"
+#include "attention_launch.h"
 
 #include <type_traits>
 
 namespace mmx {
 
 namespace {
-
-// -DMMX_HEAD_TIMELINE (probe builds only, tools/probe_head_timeline.py): every wave of the backward records s_memtime at its phase
-// boundaries and lane 0 writes the differences (shader cycles) over row 0 of its head's dV -- the output is garbage in such a build.
-#ifdef MMX_HEAD_TIMELINE
-#define MMX_TL_DECL long long tl_[10]; int tl_n_ = 0
-#define MMX_TL_MARK() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tl_[tl_n_++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define MMX_TL_DECL
-#define MMX_TL_MARK() do { } while (0)
-#endif
-
-__device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
 // 16-byte store that only assumes 4-byte alignment (rows of an odd-Nk slab)
 __device__ __forceinline__ void stg4_u(float* p, f32x4 v) { reinterpret_cast<f32x4_u*>(p)->v = v; }
@@ -258,40 +248,29 @@ __device__ __forceinline__ void store_rows16(float* base, int64_t sn, int row, b
 // bf16 gradient I/O (IOH): the upstream gradient dO arrives as bf16 and dQ / dK / dV leave as bf16 (round to nearest even) -- the
 // bf16 gradient stream of a bf16 body (clip_model.backward_tape) through a SHORT tower: same exact-fp32 arithmetic in between, the two
 // conversion passes around the kernel (dO -> fp32, dq | dk | dv -> bf16: 33 launches and 4.5 ms per cfg-5 step) are gone.
-__device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    bf2 r;
-    r[0] = static_cast<__bf16>(lo);
-    r[1] = static_cast<__bf16>(hi);
-    return __builtin_bit_cast(unsigned, r);
-}
 template <int DP>
 __device__ __forceinline__ void load_rows16_bf16(f32x4 (&reg)[DP / 16], const unsigned short* base, int64_t sn, int row, int N,
                                                  int D, int g) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     const bool rv = row < N;
     const unsigned short* p = base + (rv ? static_cast<int64_t>(row) * sn : 0);
 #pragma unroll
     for (int kk = 0; kk < DP / 16; ++kk) {
         const int d = kk * 16 + 4 * g;
         const bool ok = rv && d < D;
-        const u32x2 w = *reinterpret_cast<const u32x2*>(p + (ok ? d : 0));
-        reg[kk] = ok ? f32x4{__uint_as_float(w[0] << 16), __uint_as_float(w[0] & 0xffff0000u), __uint_as_float(w[1] << 16),
-                             __uint_as_float(w[1] & 0xffff0000u)}
-                     : f32x4{0.f, 0.f, 0.f, 0.f};
+        const u32x2v w = *reinterpret_cast<const u32x2v*>(p + (ok ? d : 0));
+        reg[kk] = ok ? widen_bf16x4(w) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 }
 template <int DP>
 __device__ __forceinline__ void store_rows16_bf16(unsigned short* base, int64_t sn, int row, bool row_valid, int D, int g,
                                                   const f32x4 (&acc)[DP / 16], float mul) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     if (!row_valid) return;
     unsigned short* p = base + static_cast<int64_t>(row) * sn + 4 * g;
 #pragma unroll
     for (int td = 0; td < DP / 16; ++td)
         if (td * 16 + 4 * g < D) {
             const f32x4 v = acc[td] * mul;
-            *reinterpret_cast<u32x2*>(p + td * 16) = u32x2{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
+            *reinterpret_cast<u32x2v*>(p + td * 16) = u32x2v{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
         }
 }
 
@@ -479,8 +458,6 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     const bool strip_live = !LIVE || wave * 16 < L;    // wave-uniform
 
     stagger(a.debug >> 8);
-    MMX_TL_DECL;
-    MMX_TL_MARK();                                                   // 0: start
     // this wave's rows of dO (and Q') and its chunks of P: global -> registers, issued before the LDS staging
     f32x4 doreg[KK], qreg[KK], preg[NTK];
     if constexpr (IOH)
@@ -501,9 +478,7 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     } else {
         stage_one<DP, 4>(Vs, LSA, vb, a.vs.sn, Lk, LIVE ? nt * 16 : NPk, a.D, tid, nthreads);
     }
-    MMX_TL_MARK();                                                   // 1: V / K staged (this wave's part)
     lds_barrier();
-    MMX_TL_MARK();                                                   // 2: after the first barrier
     // REL: consume the weight here, where the staging has retired its load: used after the dP stores, it cost a vmcnt(0) on them
     float w = REL && qv ? vq : 0.f;
     if constexpr (REL) asm volatile("" : "+v"(w));   // (pins the select here: the compiler sinks it to its use otherwise)
@@ -517,7 +492,6 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
     } else {
         tiles_kd<DP, NTK, LSA>(acc, Vs, doreg, c16, g);
     }
-    MMX_TL_MARK();                                                   // 3: dP tiles done (waits for dO rows)
     float* dprow = a.dprobs + (head * a.Nq + (qv ? q : 0)) * a.Nk;
     float dot = 0.f;
 #pragma unroll
@@ -570,7 +544,6 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
             acc[t][r] = ds;
         }
 
-    MMX_TL_MARK();                                                   // 4: dP stored, delta reduced, dS (waits for P chunks)
     // ---- phase B: dQ = dS.K, dS straight from the accumulators
     if (strip_live) {
         f32x4 dq[KK];
@@ -584,12 +557,10 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
             store_rows16<DP>(a.dq + b * a.dqs.sb + h * a.dqs.sh, a.dqs.sn, q, lv, a.D, g, dq, q_first ? a.scale : 1.f);
     }
 
-    MMX_TL_MARK();                                                   // 5: dQ done and stored
     // ---- phase C: dK = dS^T.Q' (pass 0), dV = P^T.dO (pass 1); contraction over q = across waves, through LDS
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         lds_barrier();                                           // previous readers of this LDS region are done
-        MMX_TL_MARK();                                               // 6 / 8: barrier passed
         if (strip_live) {                                        // (LIVE: the rows of a dead strip are not read below)
 #pragma unroll
             for (int t = 0; t < NTK; ++t)
@@ -644,29 +615,10 @@ __global__ __launch_bounds__(NTK >= 7 ? 512 : 1024) void attn_bwd_head_kernel(co
             if constexpr (IOH) store_rows16_bf16<DP>(outh, osn, key, key < Lk, a.D, g, o, 1.f);
             else store_rows16<DP>(outb, osn, key, key < Lk, a.D, g, o, 1.f);
         }
-        MMX_TL_MARK();                                               // 7 / 9: pass done
     }
-#ifdef MMX_HEAD_TIMELINE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    {
-        const long long tend = __builtin_readcyclecounter();
-        __syncthreads();
-        if (lane == 0 && wave < 5) {
-            float* out = a.dv + b * a.dvs.sb + h * a.dvs.sh + wave * 12;
-            for (int i = 1; i < 10; ++i) out[i - 1] = static_cast<float>(tl_[i] - tl_[0]);
-            out[9] = static_cast<float>(tend - tl_[0]);
-            out[10] = static_cast<float>(tl_[0] & 0xffffff);
-        }
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------- host side
-static bool aligned16(const void* p, int64_t s0, int64_t s1, int64_t s2) {
-    return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(s0 * 4) | static_cast<uintptr_t>(s1 * 4) |
-             static_cast<uintptr_t>(s2 * 4)) & 15u) == 0;
-}
-
 static int g_attn_head = 1;   // 0: skip these kernels (tests / A-B profiling run the older paths)
 static int g_attn_head_tile_skip = 1;   // option "attn_head_tile_skip": masked-tile skip (with_tile_count); 0 for A / B runs
 void attn_head_tile_skip(int on) { g_attn_head_tile_skip = on ? 1 : 0; }
@@ -693,80 +645,25 @@ static size_t bwd_head_lds(int DP, int NTK, int NTQ, bool rel = false) {
     return sizeof(float) * ((ab > c ? ab : c) + (rel ? 16 + static_cast<size_t>(NTQ) * NTK * 16 : static_cast<size_t>(NTQ)));
 }
 
-template <typename K, typename A>
-static int launch_head(K kern, const A& args, int threads, size_t lds, hipStream_t s, const char* name, int nz = 1) {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    kern<<<dim3(args.H, args.B, nz), threads, lds, s>>>(args);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, name);
-    return MMX_OK;
+// the dense kernels for every (padded head dim, key-tile count); every launch of this file has the grid (H, B[, nz])
+template <bool NOP>
+static int fwd_head_dispatch(const AttnFwdArgs& a, int NTK, dim3 grid, int threads, size_t lds, hipStream_t s) {
+    return by_head_dim(a.D, [&](auto dp) {
+        return by_key_tiles(NTK, [&](auto ntk) {
+            return launch_attn(attn_fwd_head_kernel<decltype(dp)::value, decltype(ntk)::value, NOP>, grid, threads, lds, s,
+                               NOP ? "attn_fwd_head_kernel<nop>" : "attn_fwd_head_kernel", a);
+        });
+    });
 }
 
-#define MMX_HEAD_CASE(KERN, DPV, N)                                                                            \
-    case N:                                                                                                    \
-        return launch_head(KERN<DPV, N>, a, threads, lds, s, #KERN)
-
-template <int DP>
-static int fwd_head_dispatch(const AttnFwdArgs& a, int NTK, int threads, size_t lds, hipStream_t s) {
-    switch (NTK) {
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 1);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 2);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 3);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 4);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 5);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 6);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 7);
-        MMX_HEAD_CASE(attn_fwd_head_kernel, DP, 8);
-    }
-    return MMX_ENOTSUP;
-}
-
-#define MMX_HEAD_CASE_NOP(DPV, N)                                                                              \
-    case N:                                                                                                    \
-        return launch_head(attn_fwd_head_kernel<DPV, N, true>, a, threads, lds, s, "attn_fwd_head_kernel<nop>", nz)
-
-template <int DP>
-static int fwd_head_dispatch_nop(const AttnFwdArgs& a, int NTK, int threads, size_t lds, hipStream_t s) {
-    int nz = 1;
-    if (NTK >= 7 && threads > 512) {        // (those instantiations are capped at 8 waves: two workgroups per head)
-        const int ntq = threads / 64;
-        nz = 2;
-        threads = 64 * ((ntq + 1) / 2);
-    }
-    switch (NTK) {
-        MMX_HEAD_CASE_NOP(DP, 1);
-        MMX_HEAD_CASE_NOP(DP, 2);
-        MMX_HEAD_CASE_NOP(DP, 3);
-        MMX_HEAD_CASE_NOP(DP, 4);
-        MMX_HEAD_CASE_NOP(DP, 5);
-        MMX_HEAD_CASE_NOP(DP, 6);
-        MMX_HEAD_CASE_NOP(DP, 7);
-        MMX_HEAD_CASE_NOP(DP, 8);
-    }
-    return MMX_ENOTSUP;
-}
-
-#define MMX_HEAD_CASE_IO(DPV, N, IO, RL, GR)                                                                  \
-    case N:                                                                                                    \
-        return launch_head(attn_bwd_head_kernel<DPV, N, IO, RL, GR>, a, threads, lds, s, "attn_bwd_head_kernel")
-
-template <int DP, bool IOH, bool REL = false, bool GRP = false>
-static int bwd_head_dispatch(const AttnBwdArgs& a, int NTK, int threads, size_t lds, hipStream_t s) {
-    switch (NTK) {
-        MMX_HEAD_CASE_IO(DP, 1, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 2, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 3, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 4, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 5, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 6, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 7, IOH, REL, GRP);
-        MMX_HEAD_CASE_IO(DP, 8, IOH, REL, GRP);
-    }
-    return MMX_ENOTSUP;
+template <bool IOH, bool REL, bool GRP>
+static int bwd_head_dispatch(const AttnBwdArgs& a, int NTK, dim3 grid, int threads, size_t lds, hipStream_t s) {
+    return by_head_dim(a.D, [&](auto dp) {
+        return by_key_tiles(NTK, [&](auto ntk) {
+            return launch_attn(attn_bwd_head_kernel<decltype(dp)::value, decltype(ntk)::value, IOH, REL, GRP>, grid, threads, lds, s,
+                               "attn_bwd_head_kernel", a);
+        });
+    });
 }
 
 // returns 1 if the kernel was launched (rc in *rc_out), 0 if the shape is not eligible
@@ -776,29 +673,36 @@ int attn_fwd_head_try(const AttnFwdArgs& a_in, hipStream_t s, int* rc_out) {
     a.tile_skip = g_attn_head_tile_skip;
     if (!g_attn_head || a.slab_dt != MMX_F32 || a.D % 4 || a.D > 64 || a.Nk > 128 || a.Nq > 256 || a.Nq < 1 || a.Nk < 1)
         return 0;
-    if (!aligned16(a.q, a.qs.sb, a.qs.sh, a.qs.sn) || !aligned16(a.k, a.ks.sb, a.ks.sh, a.ks.sn) ||
-        !aligned16(a.v, a.vs.sb, a.vs.sh, a.vs.sn))
-        return 0;
+    if (!rows_aligned(a.q, a.qs, 4, 16, true) || !rows_aligned(a.k, a.ks, 4, 16, true) || !rows_aligned(a.v, a.vs, 4, 16, true)) return 0;
     const int DP = a.D <= 32 ? 32 : 64, NTK = (a.Nk + 15) / 16, threads = 64 * ((a.Nq + 15) / 16);
     const size_t lds = fwd_head_lds(DP, NTK);
+    const dim3 grid(a.H, a.B);
     if (a.eot) {
         if (!a.mask || !attn_head_live_shape(a.Nq, a.Nk, a.D)) {
             set_error("attn_fwd_head: no live-length instantiation for Nq=%d Nk=%d D=%d (masked forward, 65 ... 80 tokens; "
                       "option text_live_attn)", a.Nq, a.Nk, a.D);
             *rc_out = MMX_ENOTSUP;
         } else if (a.no_probs) {     // mmx_attn_fwd_live: the same kernel, same launch geometry, no P store
-            *rc_out = DP == 32 ? launch_head(attn_fwd_head_kernel<32, 5, true, true>, a, threads, lds, s, "attn_fwd_head_kernel<nop, live>")
-                               : launch_head(attn_fwd_head_kernel<64, 5, true, true>, a, threads, lds, s, "attn_fwd_head_kernel<nop, live>");
+            *rc_out = by_head_dim(a.D, [&](auto dp) {
+                return launch_attn(attn_fwd_head_kernel<decltype(dp)::value, 5, true, true>, grid, threads, lds, s,
+                                   "attn_fwd_head_kernel<nop, live>", a);
+            });
         } else {
-            *rc_out = DP == 32 ? launch_head(attn_fwd_head_kernel<32, 5, false, true>, a, threads, lds, s, "attn_fwd_head_kernel<live>")
-                               : launch_head(attn_fwd_head_kernel<64, 5, false, true>, a, threads, lds, s, "attn_fwd_head_kernel<live>");
+            *rc_out = by_head_dim(a.D, [&](auto dp) {
+                return launch_attn(attn_fwd_head_kernel<decltype(dp)::value, 5, false, true>, grid, threads, lds, s,
+                                   "attn_fwd_head_kernel<live>", a);
+            });
         }
         return 1;
     }
-    if (a.no_probs)     // mmx_attn_fwd: the same kernel, same launch geometry, no P store
-        *rc_out = DP == 32 ? fwd_head_dispatch_nop<32>(a, NTK, threads, lds, s) : fwd_head_dispatch_nop<64>(a, NTK, threads, lds, s);
-    else
-        *rc_out = DP == 32 ? fwd_head_dispatch<32>(a, NTK, threads, lds, s) : fwd_head_dispatch<64>(a, NTK, threads, lds, s);
+    if (a.no_probs && NTK >= 7 && threads > 512) {
+        // mmx_attn_fwd: the same kernel without the P store; its widest key sides are capped at 8 waves: two workgroups per head
+        *rc_out = fwd_head_dispatch<true>(a, NTK, dim3(a.H, a.B, 2), 64 * ((threads / 64 + 1) / 2), lds, s);
+    } else if (a.no_probs) {
+        *rc_out = fwd_head_dispatch<true>(a, NTK, grid, threads, lds, s);
+    } else {
+        *rc_out = fwd_head_dispatch<false>(a, NTK, grid, threads, lds, s);
+    }
     return 1;
 }
 
@@ -808,49 +712,41 @@ int attn_bwd_head_try(const AttnBwdArgs& a_in, hipStream_t s, int* rc_out) {
     a.tile_skip = g_attn_head_tile_skip;
     if (!g_attn_head || a.slab_dt != MMX_F32 || a.D % 4 || a.D > 64 || a.Nk > 128 || a.Nq > 256 || a.Nq < 1 || a.Nk < 1)
         return 0;
-    // (bf16 gradient I/O: 4-element chunks are 8 bytes -- aligned16 on half the byte strides is the 8-byte test)
+    // gradient rows: fp32 as float4, or (bf16 gradient I/O) 4-element chunks of 8 bytes
     const auto io_ok = [&](const void* p, const Strides& st) {
-        return a.io_bf16 ? ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(st.sb * 2) | static_cast<uintptr_t>(st.sh * 2) |
-                             static_cast<uintptr_t>(st.sn * 2)) & 7u) == 0
-                         : aligned16(p, st.sb, st.sh, st.sn);
+        return a.io_bf16 ? rows_aligned(p, st, 2, 8, true) : rows_aligned(p, st, 4, 16, true);
     };
-    if (!aligned16(a.v, a.vs.sb, a.vs.sh, a.vs.sn) || !io_ok(a.dout, a.os)) return 0;
-    if (a.need_dqkv && (!aligned16(a.q, a.qs.sb, a.qs.sh, a.qs.sn) || !aligned16(a.k, a.ks.sb, a.ks.sh, a.ks.sn)))
-        return 0;
+    if (!rows_aligned(a.v, a.vs, 4, 16, true) || !io_ok(a.dout, a.os)) return 0;
+    if (a.need_dqkv && (!rows_aligned(a.q, a.qs, 4, 16, true) || !rows_aligned(a.k, a.ks, 4, 16, true))) return 0;
     if (a.io_bf16 && a.need_dqkv && (!io_ok(a.dq, a.dqs) || !io_ok(a.dk, a.dks) || !io_ok(a.dv, a.dvs))) return 0;
     const int DP = a.D <= 32 ? 32 : 64, NTK = (a.Nk + 15) / 16, NTQ = (a.Nq + 15) / 16, threads = 64 * NTQ;
     const bool rel = a.rel_v != nullptr;
     const size_t lds = bwd_head_lds(DP, NTK, NTQ, rel);
     if (lds > 160 * 1024 || (NTK >= 7 && NTQ > 8)) return 0;
     if (rel && (a.io_bf16 || a.Nq != a.Nk)) return 0;
+    const dim3 grid(a.H, a.B);
     if (a.eot) {
         if (rel || a.io_bf16 || !attn_head_live_shape(a.Nq, a.Nk, a.D)) {
             set_error("attn_bwd_head: no live-length instantiation for Nq=%d Nk=%d D=%d (fp32 capture backward, 65 ... 80 tokens; "
                       "option text_live_attn)", a.Nq, a.Nk, a.D);
             *rc_out = MMX_ENOTSUP;
         } else {
-            *rc_out = DP == 32
-                ? launch_head(attn_bwd_head_kernel<32, 5, false, false, false, true>, a, threads, lds, s, "attn_bwd_head_kernel<live>")
-                : launch_head(attn_bwd_head_kernel<64, 5, false, false, false, true>, a, threads, lds, s, "attn_bwd_head_kernel<live>");
+            *rc_out = by_head_dim(a.D, [&](auto dp) {
+                return launch_attn(attn_bwd_head_kernel<decltype(dp)::value, 5, false, false, false, true>, grid, threads, lds, s,
+                                   "attn_bwd_head_kernel<live>", a);
+            });
         }
         return 1;
     }
-    if (rel && a.grp_k) {
-        // grouped row mode: the same grid, one workgroup per (target, head), in the order the kernel decodes
-        *rc_out = DP == 32 ? bwd_head_dispatch<32, false, true, true>(a, NTK, threads, lds, s)
-                           : bwd_head_dispatch<64, false, true, true>(a, NTK, threads, lds, s);
-        if (*rc_out == MMX_OK) *rc_out = rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);
-        return 1;
-    }
     if (rel) {
-        *rc_out = DP == 32 ? bwd_head_dispatch<32, false, true>(a, NTK, threads, lds, s) : bwd_head_dispatch<64, false, true>(a, NTK, threads, lds, s);
+        // (grouped row mode: the same grid, one workgroup per (target, head), in the order the kernel decodes)
+        *rc_out = a.grp_k ? bwd_head_dispatch<false, true, true>(a, NTK, grid, threads, lds, s)
+                          : bwd_head_dispatch<false, true, false>(a, NTK, grid, threads, lds, s);
         if (*rc_out == MMX_OK) *rc_out = rel_row_update(a.rel_v, a.rel_part, a.rel_out, a.B, a.H, a.Nk, 1.0f / a.H, s);
         return 1;
     }
-    if (a.io_bf16)
-        *rc_out = DP == 32 ? bwd_head_dispatch<32, true>(a, NTK, threads, lds, s) : bwd_head_dispatch<64, true>(a, NTK, threads, lds, s);
-    else
-        *rc_out = DP == 32 ? bwd_head_dispatch<32, false>(a, NTK, threads, lds, s) : bwd_head_dispatch<64, false>(a, NTK, threads, lds, s);
+    *rc_out = a.io_bf16 ? bwd_head_dispatch<true, false, false>(a, NTK, grid, threads, lds, s)
+                        : bwd_head_dispatch<false, false, false>(a, NTK, grid, threads, lds, s);
     return 1;
 }
 

@@ -8,6 +8,7 @@
 // MFMA v_mfma_f32_16x16x4_f32; the full score row block [16 x Nk] lives in LDS so softmax is one pass.
 #include "mmx_common.h"
 #include "attention_args.h"
+#include "attention_launch.h"
 
 namespace mmx {
 
@@ -284,21 +285,14 @@ static size_t attn_lds_bytes(int DP, int Nk) {
     return sizeof(float) * (static_cast<size_t>(kTQ + kTK) * (DP + 2) + static_cast<size_t>(kTQ) * (NKP + 2));
 }
 
+// the first-generation kernels keep a [16 x Nk] score row block in LDS: refused where it does not fit (`name` is in the message)
 template <typename K, typename A>
-static int launch_dyn(K kern, const A& args, dim3 grid, size_t lds, hipStream_t s, const char* name) {
+static int launch_row_block(K kern, const A& args, dim3 grid, size_t lds, hipStream_t s, const char* name) {
     if (lds > 160 * 1024) {
         set_error("%s: Nk too large for the LDS row block (%zu bytes > 160 KiB)", name, lds);
         return MMX_ENOTSUP;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    kern<<<grid, 256, lds, s>>>(args);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, name);
-    return MMX_OK;
+    return launch_attn(kern, grid, 256, lds, s, name, args);
 }
 
 }  // namespace mmx
@@ -332,7 +326,7 @@ static void set_slabs(AttnBwdArgs& a, const void* probs, int64_t probs_sb, const
     a.dout = static_cast<const float*>(dout); a.os = os;
     a.dprobs = static_cast<float*>(dprobs);
     a.o = static_cast<const float*>(o); a.oos = oos;
-    if (reinterpret_cast<uintptr_t>(o) % 16 || oos.sb % 4 || oos.sh % 4 || oos.sn % 4) a.o = nullptr;   // a hint only
+    if (!rows_aligned(o, oos, 4, 16, true)) a.o = nullptr;   // a hint only
 }
 
 static void set_dqkv(AttnBwdArgs& a, void* dq, Strides dqs, void* dk, Strides dks, void* dv, Strides dvs, int need_dqkv) {
@@ -376,13 +370,17 @@ static int attn_fwd_run(const AttnFwdArgs& a, const char* fn, hipStream_t s) {
     if (attn_fwd_head_try(a, s, &rc)) return rc;    // short sequences: a wave owns 16 query rows, scores in registers
     if (attn_fwd_stream_try(a, s, &rc)) return rc;  // long sequences: K/V streamed, nothing of size Nk on chip
     const dim3 grid((a.Nq + kTQ - 1) / kTQ, a.H, a.B);
-    const size_t lds = attn_lds_bytes(a.D <= 32 ? 32 : 64, a.Nk);
-    if (a.no_probs) {
-        if (a.D <= 32) return launch_dyn(attn_capture_fwd_kernel<32, true>, a, grid, lds, s, "attn_capture_fwd_kernel<32, nop>");
-        return launch_dyn(attn_capture_fwd_kernel<64, true>, a, grid, lds, s, "attn_capture_fwd_kernel<64, nop>");
-    }
-    if (a.D <= 32) return launch_dyn(attn_capture_fwd_kernel<32>, a, grid, lds, s, "attn_capture_fwd_kernel<32>");
-    return launch_dyn(attn_capture_fwd_kernel<64>, a, grid, lds, s, "attn_capture_fwd_kernel<64>");
+    if (a.no_probs)
+        return by_head_dim(a.D, [&](auto dp) {
+            constexpr int DP = decltype(dp)::value;
+            return launch_row_block(attn_capture_fwd_kernel<DP, true>, a, grid, attn_lds_bytes(DP, a.Nk), s,
+                                    DP == 32 ? "attn_capture_fwd_kernel<32, nop>" : "attn_capture_fwd_kernel<64, nop>");
+        });
+    return by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_row_block(attn_capture_fwd_kernel<DP>, a, grid, attn_lds_bytes(DP, a.Nk), s,
+                                DP == 32 ? "attn_capture_fwd_kernel<32>" : "attn_capture_fwd_kernel<64>");
+    });
 }
 
 extern "C" int mmx_attn_capture_fwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,
@@ -594,17 +592,13 @@ static int attn_bwd_run(AttnBwdArgs a, const AttnBwdMode& m, hipStream_t s) {
     }
     if (attn_bwd_stream_try(a, s, &rc)) return rc;  // long sequences
     const dim3 gq((Nq + kTQ - 1) / kTQ, H, B), gk((Nk + 15) / 16, H, B);
-    if (a.D <= 32) {
-        rc = launch_dyn(attn_capture_bwd_q_kernel<32>, a, gq, attn_lds_bytes(32, Nk), s, "attn_capture_bwd_q_kernel<32>");
-        if (rc || !a.need_dqkv) return rc;
-        attn_capture_bwd_kv_kernel<32><<<gk, 256, 0, s>>>(a);
-    } else {
-        rc = launch_dyn(attn_capture_bwd_q_kernel<64>, a, gq, attn_lds_bytes(64, Nk), s, "attn_capture_bwd_q_kernel<64>");
-        if (rc || !a.need_dqkv) return rc;
-        attn_capture_bwd_kv_kernel<64><<<gk, 256, 0, s>>>(a);
-    }
-    MMX_LAUNCH_CHECK("attn_capture_bwd_kv_kernel");
-    return MMX_OK;
+    return by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        const int rc_q = launch_row_block(attn_capture_bwd_q_kernel<DP>, a, gq, attn_lds_bytes(DP, Nk), s,
+                                          DP == 32 ? "attn_capture_bwd_q_kernel<32>" : "attn_capture_bwd_q_kernel<64>");
+        if (rc_q || !a.need_dqkv) return rc_q;
+        return launch_attn(attn_capture_bwd_kv_kernel<DP>, gk, 256, 0, s, "attn_capture_bwd_kv_kernel", a);
+    });
 }
 
 extern "C" int mmx_attn_capture_bwd(const void* q_dev, const void* k_dev, const void* v_dev, int64_t q_sb, int64_t q_sh,

@@ -20,6 +20,8 @@
 // C/D[m = 4g + r][n = i], r = 0..3.  k-slot g of step s in block blk is contraction index 16 blk + 4 g + s.
 #include "mmx_common.h"
 #include "attention_args.h"
+#include "attention_bf16_words.h"
+#include "attention_launch.h"
 
 #include <type_traits>
 
@@ -34,25 +36,14 @@ constexpr int kPS = kTile + 4; // row stride of a wave's private [16][64] P / dS
 int g_attn_stream = 1;
 int g_attn_fwd_split = 1;   // option "attn_fwd_split": the small-grid forward (attn_fwd_split_kernel)
 
-// exp(x) = 2^(x log2 e) on the hardware v_exp_f32 (1 ulp).  The rounding of x * log2(e) adds |x| * 6e-8 of relative
-// error; the ABSOLUTE error of a probability p = exp(x) is then at most max_x |x| e^x * 6e-8 = 2.2e-8, and its relative
-// error stays below the 1e-5 parity bar for every x that does not underflow.  Two instructions instead of libm expf's
-// ~15: PMC showed these kernels issue-bound on VALU work around the MFMAs, not HBM-bound.
-__device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
 // ---- streamed [64 x D] operand tile: global -> registers (prefetch) -> LDS, row stride DP + 4 floats.
 // The prefetch registers hold the RAW loaded words: masking (rows past the end, d >= D), the bf16 -> fp32 widening of a
 // bf16 operand and the scale all happen in tile_store, one iteration later.  Any ALU op on the loaded value at fetch time
 // makes the compiler wait for the load right there (s_waitcnt vmcnt(0) before the tile's MFMAs): PMC showed the bf16-input
 // variant, which widened at fetch time, parked 48 % of its wave cycles against 33 %.
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 widen_bf16x4(u32x2 r) {
-    return f32x4{__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16),
-                 __uint_as_float(r[1] & 0xffff0000u)};
-}
 template <int DP, bool HALF = false>
 struct TileRegs {
-    typename std::conditional<HALF, u32x2, f32x4>::type raw[DP / 16];
+    typename std::conditional<HALF, u32x2v, f32x4>::type raw[DP / 16];
     int row0;
 };
 template <int DP, bool HALF, typename T>
@@ -68,7 +59,7 @@ __device__ __forceinline__ void tile_fetch(TileRegs<DP, HALF>& reg, const T* bas
         const bool ok = row < rows_total && c < D;
         // unconditional (clamped) load: a conditional load would serialise on vmcnt(0) per element
         const T* src = base + (ok ? static_cast<int64_t>(row) * sn + c : 0);
-        if constexpr (HALF) reg.raw[e] = *reinterpret_cast<const u32x2*>(src);
+        if constexpr (HALF) reg.raw[e] = *reinterpret_cast<const u32x2v*>(src);
         else reg.raw[e] = *reinterpret_cast<const f32x4*>(src);
     }
 }
@@ -108,7 +99,7 @@ __device__ __forceinline__ void load_a_rows_h(f32x4 (&a)[DP / 16], const unsigne
     for (int blk = 0; blk < DP / 16; ++blk) {
         const int d0 = 16 * blk + 4 * g;
         const bool ok = d0 < D;
-        const u32x2 v = *reinterpret_cast<const u32x2*>(base + static_cast<int64_t>(row) * sn + (ok ? d0 : 0));
+        const u32x2v v = *reinterpret_cast<const u32x2v*>(base + static_cast<int64_t>(row) * sn + (ok ? d0 : 0));
         a[blk] = ok ? widen_bf16x4(v) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 }
@@ -118,13 +109,6 @@ __device__ __forceinline__ void load_a_rows_h(f32x4 (&a)[DP / 16], const unsigne
 // r = 0, 2 and the odd lane rows r = 1, 3 as (column, column + 1) PAIRS: 4-byte stores, half as many.
 __device__ __forceinline__ float dpp_swap1(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false));   // quad_perm:[1,0,3,2]
-}
-__device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    bf2 r;
-    r[0] = static_cast<__bf16>(lo);
-    r[1] = static_cast<__bf16>(hi);
-    return __builtin_bit_cast(unsigned, r);
 }
 // v[r]: this lane's 4 row values of column `col`; row_ok(r) / row_idx(r) describe row r.  All lanes must call it.
 template <typename RowOk, typename RowIdx>
@@ -1030,28 +1014,12 @@ __global__ __launch_bounds__(kThreads) void attn_bwd_kv_stream_kernel(const Attn
     }
 }
 
-bool aligned16(const float* p, const Strides& s) {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && s.sb % 4 == 0 && s.sh % 4 == 0 && s.sn % 4 == 0;
-}
-
-template <typename K, typename A>
-int launch_stream(K kern, const A& args, dim3 grid, size_t lds, hipStream_t s, const char* name) {
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
-    kern<<<grid, kThreads, lds, s>>>(args);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, name);
-    return MMX_OK;
-}
-
 template <int DT, bool MM>
 int launch_fwd_mm(const AttnFwdArgs& a, dim3 grid, hipStream_t s) {
-    return a.D <= 32
-        ? launch_stream(attn_fwd_stream_kernel<32, DT, MM>, a, grid, stream_lds_bytes<32>(2), s, "attn_fwd_stream_kernel<32>")
-        : launch_stream(attn_fwd_stream_kernel<64, DT, MM>, a, grid, stream_lds_bytes<64>(2), s, "attn_fwd_stream_kernel<64>");
+    return by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_fwd_stream_kernel<DP, DT, MM>, grid, kThreads, stream_lds_bytes<DP>(2), s, "attn_fwd_stream_kernel", a);
+    });
 }
 
 template <int DT>
@@ -1061,56 +1029,51 @@ int launch_fwd_dt(const AttnFwdArgs& a, dim3 grid, hipStream_t s) {
 
 template <int DT, bool MM>
 int launch_bwd_mm(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
-    const bool small_d = a.D <= 32;
-    int rc = small_d ? launch_stream(attn_bwd_q_stream_kernel<32, DT, MM>, a, gq, stream_lds_bytes<32>(2), s,
-                                     "attn_bwd_q_stream_kernel<32>")
-                     : launch_stream(attn_bwd_q_stream_kernel<64, DT, MM>, a, gq, stream_lds_bytes<64>(2), s,
-                                     "attn_bwd_q_stream_kernel<64>");
-    if (rc == MMX_OK && a.need_dqkv) {
-        // the key-side kernel's LDS: two operand tiles + 64 deltas (the 4 x 16 x 68 floats of the wave tiles cover it)
-        rc = small_d ? launch_stream(attn_bwd_kv_stream_kernel<32, DT, MM>, a, gk, stream_lds_bytes<32>(2), s,
-                                     "attn_bwd_kv_stream_kernel<32>")
-                     : launch_stream(attn_bwd_kv_stream_kernel<64, DT, MM>, a, gk, stream_lds_bytes<64>(2), s,
-                                     "attn_bwd_kv_stream_kernel<64>");
-    }
-    return rc;
+    int rc = by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_bwd_q_stream_kernel<DP, DT, MM>, gq, kThreads, stream_lds_bytes<DP>(2), s, "attn_bwd_q_stream_kernel", a);
+    });
+    if (rc != MMX_OK || !a.need_dqkv) return rc;
+    // the key-side kernel's LDS: two operand tiles + 64 deltas (the 4 x 16 x 68 floats of the wave tiles cover it)
+    return by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_bwd_kv_stream_kernel<DP, DT, MM>, gk, kThreads, stream_lds_bytes<DP>(2), s, "attn_bwd_kv_stream_kernel", a);
+    });
 }
 
 // bf16-MFMA kernels with the optional modes: REL (row relevancy) and IOH (bf16 gradient stream)
 template <int DT, bool REL, bool IOH>
 int launch_bwd_bf16(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
-    const bool small_d = a.D <= 32;
     constexpr size_t kRel = REL ? sizeof(float) * 16 * kTile : 0;
-    int rc = small_d ? launch_stream(attn_bwd_q_stream_kernel<32, DT, true, REL, IOH>, a, gq, stream_lds_bytes<32>(2) + kRel, s,
-                                     "attn_bwd_q_stream_kernel<32, bf16>")
-                     : launch_stream(attn_bwd_q_stream_kernel<64, DT, true, REL, IOH>, a, gq, stream_lds_bytes<64>(2) + kRel, s,
-                                     "attn_bwd_q_stream_kernel<64, bf16>");
-    if (rc == MMX_OK && a.need_dqkv) {
-        rc = small_d ? launch_stream(attn_bwd_kv_stream_kernel<32, DT, true, IOH>, a, gk, stream_lds_bytes<32>(2), s,
-                                     "attn_bwd_kv_stream_kernel<32, bf16>")
-                     : launch_stream(attn_bwd_kv_stream_kernel<64, DT, true, IOH>, a, gk, stream_lds_bytes<64>(2), s,
-                                     "attn_bwd_kv_stream_kernel<64, bf16>");
-    }
-    return rc;
+    int rc = by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_bwd_q_stream_kernel<DP, DT, true, REL, IOH>, gq, kThreads, stream_lds_bytes<DP>(2) + kRel, s,
+                           "attn_bwd_q_stream_kernel<bf16>", a);
+    });
+    if (rc != MMX_OK || !a.need_dqkv) return rc;
+    return by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_bwd_kv_stream_kernel<DP, DT, true, IOH>, gk, kThreads, stream_lds_bytes<DP>(2), s,
+                           "attn_bwd_kv_stream_kernel<bf16>", a);
+    });
 }
 
 // exact-fp32 kernels in row-relevancy mode (mmx_attn_capture_bwd_rowrel_f32): the query-side kernel with REL, the key-side
 // kernel as without it; fp32 slabs only
 template <bool GRP>
 static int launch_bwd_rel_f32_kernels(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
-    const bool small_d = a.D <= 32;
     constexpr size_t kRel = sizeof(float) * 16 * kTile;
-    int rc = small_d ? launch_stream(attn_bwd_q_stream_kernel<32, MMX_F32, false, true, false, GRP>, a, gq,
-                                     stream_lds_bytes<32>(2) + kRel, s, "attn_bwd_q_stream_kernel<32, rel>")
-                     : launch_stream(attn_bwd_q_stream_kernel<64, MMX_F32, false, true, false, GRP>, a, gq,
-                                     stream_lds_bytes<64>(2) + kRel, s, "attn_bwd_q_stream_kernel<64, rel>");
-    if (rc == MMX_OK && a.need_dqkv) {
-        rc = small_d ? launch_stream(attn_bwd_kv_stream_kernel<32, MMX_F32, false, false, GRP>, a, gk, stream_lds_bytes<32>(2), s,
-                                     "attn_bwd_kv_stream_kernel<32>")
-                     : launch_stream(attn_bwd_kv_stream_kernel<64, MMX_F32, false, false, GRP>, a, gk, stream_lds_bytes<64>(2), s,
-                                     "attn_bwd_kv_stream_kernel<64>");
-    }
-    return rc;
+    int rc = by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_bwd_q_stream_kernel<DP, MMX_F32, false, true, false, GRP>, gq, kThreads, stream_lds_bytes<DP>(2) + kRel, s,
+                           "attn_bwd_q_stream_kernel<rel>", a);
+    });
+    if (rc != MMX_OK || !a.need_dqkv) return rc;
+    return by_head_dim(a.D, [&](auto dp) {
+        constexpr int DP = decltype(dp)::value;
+        return launch_attn(attn_bwd_kv_stream_kernel<DP, MMX_F32, false, false, GRP>, gk, kThreads, stream_lds_bytes<DP>(2), s,
+                           "attn_bwd_kv_stream_kernel", a);
+    });
 }
 
 int launch_bwd_rel_f32(const AttnBwdArgs& a, dim3 gq, dim3 gk, hipStream_t s) {
@@ -1140,33 +1103,31 @@ void attn_fwd_split_enable(int on) { g_attn_fwd_split = on & 1; }
 // Slabs in fp16 / bf16 (slab_dt) exist on this path only: they ignore the "attn_stream" switch.
 int attn_fwd_stream_try(const AttnFwdArgs& a, hipStream_t s, int* rc_out) {
     if ((!g_attn_stream && a.slab_dt == MMX_F32 && !a.mma_bf16) || a.D % 4 || a.D > 64) return 0;
-    if (!aligned16(a.q, a.qs) || !aligned16(a.k, a.ks) || !aligned16(a.v, a.vs)) return 0;
+    if (!rows_aligned(a.q, a.qs, 4, 16, true) || !rows_aligned(a.k, a.ks, 4, 16, true) || !rows_aligned(a.v, a.vs, 4, 16, true)) return 0;
     dim3 grid(((a.Nq + kRows - 1) / kRows) * a.H * a.B);
+    const dim3 g16(((a.Nq + 15) / 16) * a.H * a.B);
     if (a.no_probs) {   // mmx_attn_fwd: the same eligibility and grid rules, kernels that write no slab
-        if (g_attn_fwd_split && grid.x < 160 && a.Nk > kTile) {
-            const dim3 g16(((a.Nq + 15) / 16) * a.H * a.B);
-            *rc_out = a.D <= 32 ? launch_stream(attn_fwd_split_kernel<32, true>, a, g16, split_lds_bytes<32>(), s, "attn_fwd_split_kernel<32, nop>")
-                                : launch_stream(attn_fwd_split_kernel<64, true>, a, g16, split_lds_bytes<64>(), s, "attn_fwd_split_kernel<64, nop>");
-            return 1;
-        }
-        *rc_out = a.D <= 32 ? launch_stream(attn_fwd_stream1_kernel<32>, a, grid, stream_lds_bytes<32>(2), s, "attn_fwd_stream1_kernel<32>")
-                            : launch_stream(attn_fwd_stream1_kernel<64>, a, grid, stream_lds_bytes<64>(2), s, "attn_fwd_stream1_kernel<64>");
+        if (g_attn_fwd_split && grid.x < 160 && a.Nk > kTile)
+            *rc_out = by_head_dim(a.D, [&](auto dp) {
+                constexpr int DP = decltype(dp)::value;
+                return launch_attn(attn_fwd_split_kernel<DP, true>, g16, kThreads, split_lds_bytes<DP>(), s, "attn_fwd_split_kernel<nop>", a);
+            });
+        else
+            *rc_out = by_head_dim(a.D, [&](auto dp) {
+                constexpr int DP = decltype(dp)::value;
+                return launch_attn(attn_fwd_stream1_kernel<DP>, grid, kThreads, stream_lds_bytes<DP>(2), s, "attn_fwd_stream1_kernel", a);
+            });
         return 1;
     }
     // a grid that leaves most of the chip idle (one shared forward): 16-row workgroups whose waves split the keys
     if (g_attn_fwd_split && grid.x < 160 && a.slab_dt == MMX_F32 && !a.mma_bf16 && a.Nk > kTile) {
-        const dim3 g16(((a.Nq + 15) / 16) * a.H * a.B);
-        *rc_out = a.D <= 32 ? launch_stream(attn_fwd_split_kernel<32>, a, g16, split_lds_bytes<32>(), s, "attn_fwd_split_kernel<32>")
-                            : launch_stream(attn_fwd_split_kernel<64>, a, g16, split_lds_bytes<64>(), s, "attn_fwd_split_kernel<64>");
+        *rc_out = by_head_dim(a.D, [&](auto dp) {
+            constexpr int DP = decltype(dp)::value;
+            return launch_attn(attn_fwd_split_kernel<DP>, g16, kThreads, split_lds_bytes<DP>(), s, "attn_fwd_split_kernel", a);
+        });
         return 1;
     }
-    switch (a.slab_dt) {
-        case MMX_F32: *rc_out = launch_fwd_dt<MMX_F32>(a, grid, s); break;
-        case MMX_F16: *rc_out = launch_fwd_dt<MMX_F16>(a, grid, s); break;
-        case MMX_BF16: *rc_out = launch_fwd_dt<MMX_BF16>(a, grid, s); break;
-        default: return 0;
-    }
-    return 1;
+    return by_slab_dtype(a.slab_dt, [&](auto dt) { *rc_out = launch_fwd_dt<decltype(dt)::value>(a, grid, s); });
 }
 
 int attn_bwd_stream_try(const AttnBwdArgs& a, hipStream_t s, int* rc_out) {
@@ -1174,20 +1135,15 @@ int attn_bwd_stream_try(const AttnBwdArgs& a, hipStream_t s, int* rc_out) {
     if (a.io_bf16 && !a.mma_bf16) return 0;
     if (a.rel_v && !a.mma_bf16 && a.slab_dt != MMX_F32) return 0;
     if (a.mma_bf16 && attn_bwd_bf16_try(a, s, rc_out)) return 1;      // second-generation bf16 kernels (attention_bf16.hip)
-    if (!aligned16(a.v, a.vs) || !aligned16(a.dout, a.os)) return 0;
-    if (a.need_dqkv && (!aligned16(a.q, a.qs) || !aligned16(a.k, a.ks))) return 0;
+    // (dout is tested as fp32 rows whatever its element type: a bf16 gradient stream that the second generation declined)
+    if (!rows_aligned(a.v, a.vs, 4, 16, true) || !rows_aligned(a.dout, a.os, 4, 16, true)) return 0;
+    if (a.need_dqkv && (!rows_aligned(a.q, a.qs, 4, 16, true) || !rows_aligned(a.k, a.ks, 4, 16, true))) return 0;
     dim3 gq(((a.Nq + kRows - 1) / kRows) * a.H * a.B), gk(((a.Nk + kRows - 1) / kRows) * a.H * a.B);
     if (a.rel_v && !a.mma_bf16) {
         *rc_out = launch_bwd_rel_f32(a, gq, gk, s);
         return 1;
     }
-    switch (a.slab_dt) {
-        case MMX_F32: *rc_out = launch_bwd_dt<MMX_F32>(a, gq, gk, s); break;
-        case MMX_F16: *rc_out = launch_bwd_dt<MMX_F16>(a, gq, gk, s); break;
-        case MMX_BF16: *rc_out = launch_bwd_dt<MMX_BF16>(a, gq, gk, s); break;
-        default: return 0;
-    }
-    return 1;
+    return by_slab_dtype(a.slab_dt, [&](auto dt) { *rc_out = launch_bwd_dt<decltype(dt)::value>(a, gq, gk, s); });
 }
 
 }  // namespace mmx
