@@ -534,10 +534,19 @@ int mmx_selfattn_ours_row(const void* const* attn_table, const void* const* grad
  * On-device post-processing of relevancy maps (one workgroup per map, no host round trip):
  *  mmx_heatmap_bilinear_minmax: [B, g, g] patch maps -> bilinear upsample to [B, S, S] (torch interpolate semantics,
  *    align_corners=False) + min-max normalisation; replaces CLIP_explainability.ipynb cell 7:14-18 and
- *    Transformer_MM_explainability_ViT.ipynb cell 8:25-28.  g <= 64.
+ *    Transformer_MM_explainability_ViT.ipynb cell 8:25-28.  MMX_ENOTSUP, nothing launched: g > 64 (the patch map is staged in LDS),
+ *    S > 46340 (the S * S pixels of a map are counted in int).  B * S * S is not limited: offsets across maps are 64-bit.
  *  mmx_otsu_masks: [K, n] maps -> min-max to [0,255], truncate to 8 bit, Otsu threshold (OpenCV getThreshVal_Otsu_8u),
- *    masks [K, n] fp32 in {0, 255}; thresholds_dev: optional int32 [K]; replaces DETR/mask_generator.py:116-121
- *    (D2H copy + cv2.threshold per kept query).
+ *    masks [K, n] fp32 in {0, 255}; thresholds_dev: optional int32 [K] (NULL: not written); replaces
+ *    DETR/mask_generator.py:116-121 (D2H copy + cv2.threshold per kept query).  MMX_ENOTSUP, nothing launched: n > 2^31 - 1 - 256 (the
+ *    pixel index is an int stepped by 256).  K * n is not limited.
+ *  Both: MMX_EINVAL for a null in / out pointer or a non-positive size.
+ *  Special values.  The extremes are taken with fminf / fmaxf, so a NaN pixel does not move them: a heat-map pixel with a NaN among its
+ *    four taps (a tap of weight 0 included) is NaN and no other pixel changes; an Otsu NaN pixel is level 0, mask 0.  (The reference's
+ *    numpy min / max would make the whole map NaN: a deliberate deviation.)  A map whose upsampled range is 0 gives an all-NaN heat
+ *    map (0 / 0, as in the reference); a constant map gives Otsu levels 0, threshold 0 and an all-zero mask.  A +-inf pixel: heat map
+ *    NaN where it is tapped with weight 0, and where the blend itself is infinite the range is, so every finite pixel is 0 (+inf) or
+ *    NaN (-inf); Otsu all levels 0, threshold 0, mask 0.  tests/postprocess_bounds.py restates all of it.
  */
 int mmx_heatmap_bilinear_minmax(const void* in_dev, void* out_dev, int B, int g, int S, void* stream);
 int mmx_otsu_masks(const void* cam_dev, void* masks_dev, void* thresholds_dev, int K, int n, void* stream);

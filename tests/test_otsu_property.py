@@ -10,27 +10,13 @@ import numpy as np
 import pytest
 
 from oracle import relevancy_np as onp
+from postprocess_bounds import between_class_variance as _between_class_variance
 
 
 def _levels(cam):
     cam = np.asarray(cam, dtype=np.float32)
     cam = (cam - cam.min()) / (cam.max() - cam.min()) * np.float32(255)      # mask_generator.py:116-117
     return cam.astype(np.uint8)
-
-
-def _between_class_variance(img):
-    """sigma_b^2(t) for t = 0..255, classes {<= t} / {> t}, float64; -inf where a class is empty."""
-    hist = np.bincount(img.reshape(-1), minlength=256).astype(np.float64)
-    p = hist / hist.sum()
-    lv = np.arange(256, dtype=np.float64)
-    out = np.full(256, -np.inf)
-    for t in range(256):
-        q1, q2 = p[:t + 1].sum(), p[t + 1:].sum()
-        if q1 <= 0 or q2 <= 0:
-            continue
-        mu1, mu2 = (lv[:t + 1] * p[:t + 1]).sum() / q1, (lv[t + 1:] * p[t + 1:]).sum() / q2
-        out[t] = q1 * q2 * (mu1 - mu2) ** 2
-    return out
 
 
 def _cases():

@@ -11,7 +11,13 @@ from ._lib import MMXError, check, lib
 def image_heatmaps(image_relevance, size=224):
     """``[B, P]`` (or ``[P]``) patch relevancies (``P = g*g``) -> ``[B, size, size]`` heat maps: bilinear upsample
     (``interpolate(..., mode='bilinear')``) + min-max normalisation, one kernel launch for the whole batch.
-    Reference: CLIP_explainability.ipynb cell 7:14-18 (``size=224``), ViT notebook cell 8:25-28 (``scale_factor=16``)."""
+    Reference: CLIP_explainability.ipynb cell 7:14-18 (``size=224``), ViT notebook cell 8:25-28 (``scale_factor=16``).
+
+    ``g <= 64`` and ``size <= 46340``, else ``MMXError``.  Special values: the extremes ignore a NaN patch (``fmin`` / ``fmax``), so only the
+    pixels that tap it -- with a weight of 0 included -- are NaN, where the reference's numpy ``min`` / ``max`` would make the whole map
+    NaN (a deliberate deviation); a map whose upsampled range is 0 (a constant map at ``size == g``, an all-zero map) is all NaN, as
+    ``0 / 0`` is in the reference; an infinite patch gives NaN where it is tapped with weight 0, and where a blend is infinite every finite
+    pixel becomes 0 (``+inf``) or NaN (``-inf``)."""
     squeeze = image_relevance.dim() == 1
     rel = image_relevance.reshape(1, -1) if squeeze else image_relevance
     ops._dev(rel)
@@ -28,7 +34,11 @@ def image_heatmaps(image_relevance, size=224):
 
 def otsu_masks(cams, return_thresholds=False):
     """``[K, ...]`` relevancy maps (one per kept query) -> ``[K, ...]`` fp32 masks in {0, 255}: min-max to [0, 255],
-    8-bit truncation, Otsu threshold, ``THRESH_BINARY`` -- DETR/mask_generator.py:116-121 for all K queries in one launch."""
+    8-bit truncation, Otsu threshold, ``THRESH_BINARY`` -- DETR/mask_generator.py:116-121 for all K queries in one launch.
+
+    Special values: a NaN pixel does not move the extremes and is level 0, mask 0 (the reference's numpy ``min`` / ``max`` would wipe the
+    map: a deliberate deviation); a constant map, a single pixel or a map with an infinite pixel has every level 0, threshold 0 and an
+    all-zero mask."""
     ops._dev(cams)
     c = ops._f32c(cams).reshape(cams.shape[0], -1)
     K, n = c.shape
