@@ -52,6 +52,11 @@ BATCHED_BASELINES = {"rollout", "raw_attn", "attn_gradcam"}       # of OTHER_MET
 BATCHED_LRP = {"ours_with_lrp", "ours_with_lrp_no_normalization", "transformer_att", "partial_lrp"}   # --batch-lrp 1: one eager pass per batch
 
 
+# --text-groups: the default follows the measurement in profiles/lxmert_text_perturbation_probe.txt (non-zero only if the grouped,
+# captured text test is faster than the current route by more than the larger A/A spread there)
+TEXT_GROUPS_DEFAULT = 0
+
+
 class ItemUsage:
     """``ModelUsage`` of the reference for one item (lxmert/lxmert/perturbation.py:45-83): ``forward`` runs the body and leaves
     the item's text / region counts where the generators read them."""
@@ -95,6 +100,9 @@ def main():
     ap.add_argument("--resume-dir", default=None, help="per-rank partial score files; finished samples are skipped on restart")
     ap.add_argument("--eager-perturbation", action="store_true",
                     help="round-5 path: the 9-step image test as eager PyTorch launches instead of one hipGraph replay")
+    ap.add_argument("--text-groups", type=int, choices=(0, 1, 2, 3), default=TEXT_GROUPS_DEFAULT,
+                    help="text test: 0 = perturbation_text (eager, full padded width, one host read per batch); 1-3 = device-built step "
+                         "groups (max_groups of LxmertPerturbation.text_step_groups) replayed from one hipGraph (GraphedTextPerturbation)")
     ap.add_argument("--no-prefetch", action="store_true",
                     help="round-5 host path: batch assembly and blocking host-to-device copies on the launching thread")
     ap.add_argument("--bucket-by-length", action="store_true",
@@ -185,6 +193,11 @@ def main():
             if "pert" not in graphed:          # the image test of a fixed-shape batch: one more hipGraph (see GraphedImagePerturbation)
                 graphed["pert"] = lp.GraphedImagePerturbation(pert, batch, R_t_t, R_t_i, labels, args.positive)
             return graphed["pert"](batch, R_t_t, R_t_i, labels)[:n].clone()
+        if args.text and args.text_groups and not per_item and not args.bucket_by_length and not args.eager_perturbation:
+            if "pert" not in graphed:          # the text test of a fixed-shape batch, lengths read on the device (GraphedTextPerturbation)
+                graphed["pert"] = lp.GraphedTextPerturbation(pert, batch, R_t_t, R_t_i, labels, args.positive,
+                                                             max_groups=args.text_groups)
+            return graphed["pert"](batch, R_t_t, R_t_i, labels)[:n].clone()
         cam_image, cam_text = lp.normalize_cams_batch(R_t_t, R_t_i, batch["attention_mask"])
         scores = pert.perturbation_text(batch, cam_text, args.positive) if args.text else \
             pert.perturbation_image(batch, cam_image, args.positive)
@@ -209,7 +222,8 @@ def main():
     if rank == 0:
         print(json.dumps({"samples": len(indices), "n_gpus": world, "seconds": round(elapsed, 3),
                           "samples_per_s": round(len(indices) / elapsed, 1), "test": "text" if args.text else "image",
-                          "method": args.method, "positive": bool(args.positive), "host_path": "inline" if args.no_prefetch else "prefetch thread + side-stream copies",
+                          "method": args.method, "positive": bool(args.positive),
+                          "text_groups": args.text_groups if args.text else None, "host_path": "inline" if args.no_prefetch else "prefetch thread + side-stream copies",
                           # the first batch holds the hipGraph capture and the library warm-up: the rate of the remaining batches
                           "samples_per_s_after_first_batch": round((len(indices) - min(args.max_batch, len(indices))) / max(elapsed - (stats.get("first_batch_s") or 0.0), 1e-9) / world, 1) * world
                           if stats.get("batches", 0) > 1 else None,

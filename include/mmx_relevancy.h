@@ -765,6 +765,34 @@ int mmx_selfattn_perturb_text(const void* ids_dev, const void* segments_dev, con
                               const void* counts_dev, void* out_ids_dev, void* out_segments_dev, void* out_mask_dev, void* new_len_dev,
                               int B, int T, int V, int S, int positive, void* stream);
 
+/* Text perturbation test of the two-stream (LXMERT) model for a PADDED batch of ragged questions (evaluator: lxmert_perturbation.py;
+ * lxmert/lxmert/perturbation.py:160-178): [CLS] and [SEP] always stay, the int((1 - step) * W) top-scoring words stay in their original
+ * order, left-aligned so that the position embeddings see 0, 1, 2, ..., the rest is dropped.  One launch builds the S perturbed copies
+ * of B questions and writes each step's sequences where the caller wants them, at the caller's width:
+ *   ids / types [B, T] int64, cam [B, T] fp32 (one score per POSITION), text_len [B] int32 ON THE DEVICE, CLAMPED inside the kernel to
+ *   2 .. T before any use, counts [S, T - 1] int32 ON THE DEVICE with counts[s][w] = int((1 - step_s) * w) in host arithmetic (:168),
+ *   place [S][3] int64 IN HOST MEMORY: base_s, stride_s, width_s (copied into the kernel's arguments: S <= 64).
+ * Per question, n = the clamped length: the words are the positions 1 .. n - 2 (W = n - 2 of them), positions 0 and n - 1 always stay;
+ * rank[p] = position of word p in ONE stable descending order of the words' scores, the total order of mmx_patch_ranks (lower index
+ * first among equals, +0.0 == -0.0, NaN before +inf); positive != 0 ranks the negated scores; scores outside the words are never
+ * read.  Step s keeps word p iff rank[p] < counts[s][W].
+ *   -> out_ids / out_types int64 and out_mask fp32 (LXMERT's attention_mask is float), out_elems elements each: sequence (s, b)
+ *      occupies the elements base_s + b * stride_s + [0, width_s) of each and holds the kept positions in ascending order, then zeros
+ *      (mask 1.0 at the kept).  The kernel writes all width_s elements and nothing outside them; a sequence longer than width_s is
+ *      TRUNCATED there, never overrun.  2 + int((1 - step_s) * (T - 2)) bounds the new length of every question of the batch;
+ *      new_len [S, B] int64 = 2 + kept, untruncated (new_len > width_s: the caller's width was too small);
+ *      ranks [B, T] int32 (or NULL): the rank at the words, -1 elsewhere.
+ * One wave per question on the key / counting / compaction code of mmx_perturb_tokens; no atomics, no workspace, nothing read back,
+ * workgroups independent.  MMX_EINVAL with a message, before any HIP call, for: a null pointer (ranks may be NULL); T outside
+ * 2 .. 256, S outside 1 .. 64, B < 1, out_elems outside 1 .. 2^40; width_s outside 1 .. T, stride_s < width_s, base_s < 0; a last
+ * sequence that ends past out_elems; two steps whose sequences may overlap -- two steps are accepted only if (a) they have the same
+ * stride and their windows [base mod stride, + width) are disjoint within a period without wrapping, or (b) their overall ranges
+ * [base_s, base_s + (B - 1) * stride_s + width_s) are disjoint; an output that overlaps an input or another output. */
+int mmx_lxmert_perturb_text(const void* ids_dev, const void* types_dev, const void* cam_dev, const void* text_len_dev,
+                            const void* counts_dev, const int64_t* place_host, void* out_ids_dev, void* out_types_dev,
+                            void* out_mask_dev, void* new_len_dev, void* ranks_dev, int64_t out_elems, int B, int T, int S, int positive,
+                            void* stream);
+
 /* Row-relevancy mode of the backward (BASELINE config 5; CLIP `interpret`, CLIP/clip/... notebook cell 7:27-37, returns
  * only `R[:, 0, 1:]` of the image tower): row 0 of  R_final = (I + A_L) ... (I + A_start)  is  e_0^T (I + A_L) ... , i.e.
  * a ROW vector carried from the top layer down -- the order the backward visits the layers anyway:

@@ -94,6 +94,7 @@ _PROTOTYPES = {
     "mmx_perturb_patches": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mmx_selfattn_perturb_regions": (_i, [_vp] * 8 + [_i, _i, _i, _i, _i, _i64, _i, _vp]),
     "mmx_selfattn_perturb_text": (_i, [_vp] * 9 + [_i, _i, _i, _i, _i, _vp]),
+    "mmx_lxmert_perturb_text": (_i, [_vp] * 11 + [_i64, _i, _i, _i, _i, _vp]),      # (the 6th pointer: place, in HOST memory)
     "mmx_attn_capture_bwd_ex": (_i, _BWD_EX + _WS),
     "mmx_attn_capture_bwd_rowrel": (_i, _BWD_EX + [_vp, _vp] + _WS),                              # rel_in, rel_out
     "mmx_attn_capture_bwd_rowrel_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -30,7 +30,15 @@
 //     into the group's packed rows (16-byte loads / stores when E % 4 == 0), with the additive key mask and the pooled row index.
 //   * mmx_selfattn_perturb_text: mmx_perturb_tokens on the '?'-pooler convention (positions 0, n - 2, n - 1 stay, the words are
 //     1 .. n - 3) for ids and segments at once; the three wave-level steps are shared with perturb_tokens_kernel.
+//
+// Text perturbation test of LXMERT on a padded batch (lxmert_perturbation.py; lxmert/lxmert/perturbation.py:160-178):
+//   * mmx_lxmert_perturb_text: the same three wave-level steps on the [CLS] ... [SEP] convention (positions 0 and n - 1 stay, the words
+//     are 1 .. n - 2, lengths from a device array clamped to 2 .. T) for ids and token types at once, with a float mask.  Every step's
+//     sequences are written where a host placement table (base, stride, width per step, passed by value) puts them, so that groups of
+//     steps leave the kernel at their own width: [B * n_g, Q_g] blocks the body embeds as they are.  A sequence writes exactly its
+//     width -- the kept positions, zeros behind them, truncated at the width -- and nothing else.
 #include "mmx_common.h"
+#include "text_placement.h"
 
 namespace mmx {
 namespace {
@@ -310,6 +318,62 @@ __global__ __launch_bounds__(64) void selfattn_perturb_text_kernel(const long lo
     }
 }
 
+// place.v[s] = {base, stride, width} of step s (text_placement.h; validated by the entry): 64 x 3 x 8 bytes of kernel arguments
+struct TextPlacement {
+    long long v[kMaxTokenSteps][3];
+};
+
+// grid B, one wave: question b -> for every step s the width_s elements at base_s + b * stride_s of out_ids / out_types / out_mask,
+// new_len[s][b] (untruncated) and ranks[b][.] (optional).  The length comes from text_len clamped to 2 .. T; the words are 1 .. n - 2.
+template <bool NEGATE>
+__global__ __launch_bounds__(64) void lxmert_perturb_text_kernel(const long long* __restrict__ ids, const long long* __restrict__ types,
+                                                                 const float* __restrict__ cam, const int* __restrict__ text_len,
+                                                                 const int* __restrict__ counts, long long* __restrict__ out_ids,
+                                                                 long long* __restrict__ out_types, float* __restrict__ out_mask,
+                                                                 long long* __restrict__ new_len, int* __restrict__ ranks,
+                                                                 const TextPlacement place, int B, int T, int S) {
+    __shared__ __attribute__((aligned(16))) unsigned keys[kMaxPositions];
+    __shared__ long long idrow[kMaxPositions];
+    __shared__ long long typerow[kMaxPositions];
+    __shared__ int src[kMaxPositions];
+    __shared__ int rk[kMaxPositions];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int chunks = (T + 63) >> 6;
+    int n = text_len[b];
+    n = n < 2 ? 2 : (n > T ? T : n);
+    const int e = n - 1, W = n - 2;                         // [SEP] sits at e; the words are 1 .. e - 1
+    for (int k = 0; k < chunks; ++k) {
+        const int p = k * 64 + lane;
+        if (p < T) {
+            idrow[p] = ids[static_cast<int64_t>(b) * T + p];
+            typerow[p] = types[static_cast<int64_t>(b) * T + p];
+        }
+    }
+    wave_word_keys<NEGATE>(cam + static_cast<int64_t>(b) * T, 1, e, T, lane, keys);
+    __syncthreads();
+    wave_word_ranks(keys, 1, e, T, lane, rk, ranks ? ranks + static_cast<int64_t>(b) * T : nullptr);
+    __syncthreads();
+
+    for (int s = 0; s < S; ++s) {
+        const int keep_n = counts[static_cast<int64_t>(s) * (T - 1) + W];        // W <= T - 2
+        const int total = wave_compact(T, lane, [&](int p) { return p == 0 || p == e || (p < e && rk[p] < keep_n); }, src);
+        __syncthreads();
+        const int64_t o = place.v[s][0] + static_cast<int64_t>(b) * place.v[s][1];
+        const int width = static_cast<int>(place.v[s][2]);                      // 1 .. T: the entry refuses anything else
+        for (int k = 0; k < chunks; ++k) {
+            const int p = k * 64 + lane;
+            if (p < width) {
+                const bool live = p < total;
+                out_ids[o + p] = live ? idrow[src[p]] : 0ll;
+                out_types[o + p] = live ? typerow[src[p]] : 0ll;
+                out_mask[o + p] = live ? 1.0f : 0.0f;
+            }
+        }
+        if (lane == 0) new_len[static_cast<int64_t>(s) * B + b] = total;
+        __syncthreads();                                    // the next step rewrites src
+    }
+}
+
 }  // namespace
 }  // namespace mmx
 
@@ -423,5 +487,55 @@ extern "C" int mmx_selfattn_perturb_text(const void* ids_dev, const void* segmen
     else MMX_TEXT_LAUNCH(false);
 #undef MMX_TEXT_LAUNCH
     MMX_LAUNCH_CHECK("selfattn_perturb_text_kernel");
+    return MMX_OK;
+}
+
+extern "C" int mmx_lxmert_perturb_text(const void* ids_dev, const void* types_dev, const void* cam_dev, const void* text_len_dev,
+                                       const void* counts_dev, const int64_t* place_host, void* out_ids_dev, void* out_types_dev,
+                                       void* out_mask_dev, void* new_len_dev, void* ranks_dev, int64_t out_elems, int B, int T, int S,
+                                       int positive, void* stream) {
+    const char* me = "mmx_lxmert_perturb_text";
+    MMX_CHECK_ARG(ids_dev && types_dev && cam_dev && text_len_dev && counts_dev && place_host && out_ids_dev && out_types_dev &&
+                      out_mask_dev && new_len_dev, "%s: null pointer", me);
+    MMX_CHECK_ARG(B >= 1, "%s: batch %d < 1", me, B);
+    MMX_CHECK_ARG(T >= 2 && T <= kMaxPositions, "%s: %d positions outside 2 .. %d", me, T, kMaxPositions);
+    MMX_CHECK_ARG(S >= 1 && S <= kMaxTokenSteps, "%s: %d steps outside 1 .. %d", me, S, kMaxTokenSteps);
+    MMX_CHECK_ARG(out_elems >= 1 && out_elems <= (static_cast<int64_t>(1) << 40), "%s: %lld output elements outside 1 .. 2^40", me,
+                  static_cast<long long>(out_elems));
+    int s0 = -1, s1 = -1;
+    switch (check_text_placement(place_host, S, B, T, out_elems, &s0, &s1)) {
+        case TEXT_PLACE_OK: break;
+        case TEXT_PLACE_WIDTH:
+            MMX_CHECK_ARG(false, "%s: step %d: width %lld outside 1 .. T = %d", me, s0, static_cast<long long>(place_host[3 * s0 + 2]), T);
+        case TEXT_PLACE_STRIDE:
+            MMX_CHECK_ARG(false, "%s: step %d: stride %lld < width %lld", me, s0, static_cast<long long>(place_host[3 * s0 + 1]),
+                          static_cast<long long>(place_host[3 * s0 + 2]));
+        case TEXT_PLACE_BASE: MMX_CHECK_ARG(false, "%s: step %d: base %lld < 0", me, s0, static_cast<long long>(place_host[3 * s0]));
+        case TEXT_PLACE_OVERRUN:
+            MMX_CHECK_ARG(false, "%s: step %d: its last sequence ends past the %lld output elements", me, s0,
+                          static_cast<long long>(out_elems));
+        case TEXT_PLACE_OVERLAP: MMX_CHECK_ARG(false, "%s: the sequences of steps %d and %d overlap", me, s0, s1);
+    }
+    const size_t ll = sizeof(long long), nb = static_cast<size_t>(B), nt = static_cast<size_t>(T), ns = static_cast<size_t>(S),
+                 ne = static_cast<size_t>(out_elems);
+    const Span ins[5] = {{ids_dev, ll * nb * nt}, {types_dev, ll * nb * nt}, {cam_dev, sizeof(float) * nb * nt},
+                         {text_len_dev, sizeof(int) * nb}, {counts_dev, sizeof(int) * ns * (nt - 1)}};
+    const Span outs[5] = {{out_ids_dev, ll * ne}, {out_types_dev, ll * ne}, {out_mask_dev, sizeof(float) * ne}, {new_len_dev, ll * ns * nb},
+                          {ranks_dev, sizeof(int) * nb * nt}};
+    MMX_CHECK_ARG(!spans_alias(outs, 5, ins, 5), "%s: an output may not alias an input or another output", me);
+    TextPlacement place = {};
+    for (int s = 0; s < S; ++s)
+        for (int k = 0; k < 3; ++k) place.v[s][k] = place_host[3 * s + k];
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define MMX_LXMERT_TEXT_LAUNCH(NEG)                                                                                                  \
+    lxmert_perturb_text_kernel<NEG><<<dim3(B), 64, 0, st>>>(                                                                         \
+        static_cast<const long long*>(ids_dev), static_cast<const long long*>(types_dev), static_cast<const float*>(cam_dev),        \
+        static_cast<const int*>(text_len_dev), static_cast<const int*>(counts_dev), static_cast<long long*>(out_ids_dev),            \
+        static_cast<long long*>(out_types_dev), static_cast<float*>(out_mask_dev), static_cast<long long*>(new_len_dev),             \
+        static_cast<int*>(ranks_dev), place, B, T, S)
+    if (positive) MMX_LXMERT_TEXT_LAUNCH(true);
+    else MMX_LXMERT_TEXT_LAUNCH(false);
+#undef MMX_LXMERT_TEXT_LAUNCH
+    MMX_LAUNCH_CHECK("lxmert_perturb_text_kernel");
     return MMX_OK;
 }

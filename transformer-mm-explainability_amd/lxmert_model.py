@@ -303,7 +303,8 @@ class LxmertEncoder(nn.Module):                                        # lxmert_
     # ---- tape path of the explainability pass (bert_tape.py): no autograd graph, no weight gradients
     overlap_modalities = True     # tape path: the image chain of every layer group on a side stream beside the text chain
 
-    def forward_tape(self, lang, lang_mask, visual_feats, visual_pos, visn_mask=None, lang_repeat=1, visn_repeat=1, lang_encoded=False):
+    def forward_tape(self, lang, lang_mask, visual_feats, visual_pos, visn_mask=None, lang_repeat=1, visn_repeat=1, lang_encoded=False,
+                     visn_encoded=False):
         """``lang_repeat`` / ``visn_repeat`` (forward-only callers): the single-modality layers run on the batch as given and
         their output (and mask) is repeated that many times, sample-major, before the cross-modality layers -- the perturbation
         evaluator re-runs a sample 9 times with only ONE modality changed, so the other modality's own layers (9 language / 5
@@ -318,11 +319,13 @@ class LxmertEncoder(nn.Module):                                        # lxmert_
         tapes = {"l": [], "r": [], "x": [], "side": side}
         if side is not None:
             side.wait_stream(main)
-        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            visn = self.visn_fc(visual_feats, visual_pos)
-            for blk in self.r_layers:
-                visn, t = bt.layer_fwd(blk, visn, visn_mask)
-                tapes["r"].append(t)
+        visn = visual_feats       # (``visn_encoded``: it already IS the output of the object-relationship layers -- ``encode_vision``)
+        if not visn_encoded:
+            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+                visn = self.visn_fc(visual_feats, visual_pos)
+                for blk in self.r_layers:
+                    visn, t = bt.layer_fwd(blk, visn, visn_mask)
+                    tapes["r"].append(t)
         if not lang_encoded:      # (``lang_encoded``: ``lang`` already IS the output of the language layers -- ``encode_language``)
             for blk in self.layer:
                 lang, t = bt.layer_fwd(blk, lang, lang_mask)
@@ -493,17 +496,33 @@ class LxmertForQuestionAnswering(nn.Module):                           # lxmert_
         return emb
 
     @torch.no_grad()
+    def encode_vision(self, visual_feats, visual_pos, visual_attention_mask=None):
+        """Output of ``visn_fc`` + the 5 object-relationship layers, grad-free (tape forward): what ``scores_no_grad(visn_encoded=...)``
+        takes when SEVERAL question sets are scored against the same regions (the text perturbation test's step groups) -- the
+        counterpart of ``encode_language``."""
+        enc = self.lxmert.encoder
+        visn = enc.visn_fc(visual_feats, visual_pos)
+        visn_mask = _extended_mask(visual_attention_mask, visn.dtype)
+        for blk in enc.r_layers:
+            visn, _ = bt.layer_fwd(blk, visn, visn_mask)
+        return visn
+
+    @torch.no_grad()
     def scores_no_grad(self, input_ids=None, visual_feats=None, visual_pos=None, attention_mask=None,
                        visual_attention_mask=None, token_type_ids=None, inputs_embeds=None, lang_repeat=1, visn_repeat=1,
-                       lang_encoded=None, **unused):
+                       lang_encoded=None, visn_encoded=None, **unused):
         """``forward(...).question_answering_score`` through the tape forward (packed q / k / v GEMMs, fused bias / add /
         LayerNorm, the two modalities side by side) without keeping anything for a backward -- what the perturbation evaluator's
         re-runs need (lxmert/lxmert/perturbation.py:119-131).  An empty region set takes the module forward.
         ``lang_repeat`` / ``visn_repeat``: the text (visual) inputs are given ONCE per sample and their own layers' output is
         repeated for the cross-modality layers (``LxmertEncoder.forward_tape``); the other modality comes already repeated.
-        ``lang_encoded``: the output of ``encode_language`` for these questions -- the embeddings and language layers are skipped."""
+        ``lang_encoded``: the output of ``encode_language`` for these questions -- the embeddings and language layers are skipped.
+        ``visn_encoded``: the output of ``encode_vision`` for these regions -- ``visn_fc`` and the object-relationship layers are
+        skipped, ``visual_feats`` / ``visual_pos`` are not read (``visual_attention_mask`` still masks the regions as keys)."""
+        if visn_encoded is not None:
+            visual_feats, visual_pos = visn_encoded, None
         if visual_feats.shape[1] == 0 or (input_ids is None and lang_encoded is None):
-            if lang_repeat != 1 or visn_repeat != 1 or lang_encoded is not None:
+            if lang_repeat != 1 or visn_repeat != 1 or lang_encoded is not None or visn_encoded is not None:
                 raise ValueError("scores_no_grad: the repeat hints need a non-empty region set and token ids")
             return self.forward(input_ids, visual_feats, visual_pos, attention_mask, visual_attention_mask, token_type_ids,
                                 inputs_embeds).question_answering_score
@@ -513,7 +532,7 @@ class LxmertForQuestionAnswering(nn.Module):                           # lxmert_
             attention_mask = torch.ones(emb.shape[:2], device=emb.device)
         lang, _, _ = m.encoder.forward_tape(emb, _extended_mask(attention_mask, emb.dtype), visual_feats, visual_pos,
                                             _extended_mask(visual_attention_mask, emb.dtype), lang_repeat, visn_repeat,
-                                            lang_encoded=lang_encoded is not None)
+                                            lang_encoded=lang_encoded is not None, visn_encoded=visn_encoded is not None)
         return self.answer_head(m.pooler(lang))
 
     @torch.no_grad()

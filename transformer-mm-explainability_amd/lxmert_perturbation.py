@@ -29,10 +29,11 @@ of the same order.  With distinct scores (any real relevancy map) this equals th
 from __future__ import annotations
 
 import contextlib
+import types
 
 import torch
 
-from . import graphed, tuned_gemms
+from . import graphed, ops, tuned_gemms
 
 PERT_STEPS = (0, 0.25, 0.5, 0.75, 0.8, 0.85, 0.9, 0.95, 1)
 
@@ -144,7 +145,7 @@ class LxmertPerturbation:
     def _image_constants(self, I, device):
         """Per (region count, device): the steps' keep counts, the live / region-free step indices -- built ONCE from host
         arithmetic (as the reference does per call), so that a call creates no tensor from a host list (hipGraph-capturable)."""
-        key = (I, str(device))
+        key = (I, str(device), self.steps, self.grouped)
         if key not in self._const:
             counts = [int((1 - step) * I) for step in self.steps]
             live = [s for s, c in enumerate(counts) if c > 0]
@@ -257,6 +258,106 @@ class LxmertPerturbation:
         out = out.reshape(B, S, -1)
         return out[0] if single else out
 
+    def text_step_groups(self, T, max_groups=2, device=None):
+        """Host only: the steps of the text test on questions padded to ``T`` tokens, in at most ``max_groups`` GROUPS that each run
+        at their own width.  Step s keeps ``2 + int((1 - step_s) * (n - 2))`` tokens of a question of n tokens, left-aligned, and
+        ``int((1 - step) * w)`` does not decrease with w: ``P_s = 2 + int((1 - step_s) * (T - 2))`` bounds the new length of EVERY
+        question of the padded batch, from ``T`` alone.  The steps, sorted by descending ``P_s``, are cut into contiguous groups of
+        width ``Q_g = max P_s``; of all cuts the one with the fewest rows ``sum n_g * Q_g`` per sample is taken -- (20, 15, 11 | 6, 5,
+        4, 3, 2, 2) at T = 20: 96 text rows per sample against 180 at full width, 86 with three groups.
+
+        -> a namespace, cached per ``(T, device, steps, max_groups)``: ``rows`` (per sample); ``counts [S, T - 1]`` int32 on the device
+        (``counts[s][w] = int((1 - step_s) * w)``, host arithmetic as ``perturbation.py:168``); ``groups``: a list of ``(step index
+        tensor, n_g, Q_g)``; ``layout(B)`` (host, kept per B): ``table``, the placement table of ``ops.lxmert_perturb_text`` for a
+        batch of B, ``offsets``, the element at which every group's block starts, and ``elems``, the length of the buffers.  Group g
+        is a contiguous ``[B * n_g, Q_g]`` block with the n_g steps of a sample adjacent (sample-major, so that ``visn_repeat = n_g``
+        lines up): its steps share the stride ``n_g * Q_g`` and sit in the windows ``j * Q_g`` of a period, which is why a block
+        starts at a multiple of its stride (the entry's rule for interleaved steps; the few elements skipped are never touched)."""
+        T, max_groups = int(T), int(max_groups)
+        if T < 2 or max_groups < 1:
+            raise ValueError("text_step_groups: needs T >= 2 and max_groups >= 1 (got T=%d, max_groups=%d)" % (T, max_groups))
+        key = ("text", T, str(device), self.steps, max_groups)
+        if key in self._const:
+            return self._const[key]
+        S = len(self.steps)
+        bound = [2 + int((1 - step) * (T - 2)) for step in self.steps]
+        order = sorted(range(S), key=lambda s: -bound[s])                     # stable: equal bounds keep their step order
+        # cheapest cut of the sorted steps into at most max_groups contiguous groups: cost[g][i] = fewest rows for the first i steps in
+        # g groups (a group a .. i - 1 costs (i - a) * its first, i.e. largest, bound); S^2 * groups steps of host arithmetic
+        G, inf = min(max_groups, S), float("inf")
+        cost = [[inf] * (S + 1) for _ in range(G + 1)]
+        back = [[0] * (S + 1) for _ in range(G + 1)]
+        cost[0][0] = 0
+        for g in range(1, G + 1):
+            for i in range(1, S + 1):
+                for a in range(g - 1, i):
+                    rows = cost[g - 1][a] + (i - a) * bound[order[a]]
+                    if rows < cost[g][i]:
+                        cost[g][i], back[g][i] = rows, a
+        g = min(range(1, G + 1), key=lambda n: (cost[n][S], n))                # the fewest groups among equally cheap cuts
+        rows, edges, i = cost[g][S], [S], S
+        while g > 0:
+            i = back[g][i]
+            edges.append(i)
+            g -= 1
+        edges = edges[::-1]
+        parts = [(order[a:b], b - a, bound[order[a]]) for a, b in zip(edges, edges[1:])]
+        layouts = {}
+
+        def layout(B):
+            if B not in layouts:
+                table, offsets, at = [None] * S, [], 0
+                for steps_g, n, width in parts:
+                    at = -(-at // (n * width)) * (n * width)
+                    offsets.append(at)
+                    for j, s in enumerate(steps_g):
+                        table[s] = (at + j * width, n * width, width)
+                    at += B * n * width
+                layouts[B] = types.SimpleNamespace(table=ops.text_placement(table), offsets=offsets, elems=at)
+            return layouts[B]
+
+        counts = torch.tensor([[int((1 - step) * w) for w in range(T - 1)] for step in self.steps], dtype=torch.int32, device=device)
+        groups = [(torch.tensor(steps_g, dtype=torch.long, device=device), n, width) for steps_g, n, width in parts]
+        self._const[key] = types.SimpleNamespace(rows=rows, counts=counts, groups=groups, layout=layout, bounds=bound,
+                                                 steps=[list(p[0]) for p in parts])
+        return self._const[key]
+
+    def perturbation_text_grouped(self, inputs, cam_text, is_positive_pert=False, max_groups=2):
+        """The text test of a padded batch on device-built step groups: ``cam_text [B, T]`` -> answer scores ``[B, S, answers]``, the
+        ones ``perturbation_text`` gives.  The question lengths stay on the device (``attention_mask.sum``; ``T`` without a mask), ONE
+        ``ops.lxmert_perturb_text`` launch writes every step's questions into its group's block at the group's width
+        (``text_step_groups``), the regions' own layers run once (``encode_vision``) and every group is one ``scores_no_grad``.  No
+        host read, and after the first call of a shape no tensor built from a host list: capturable (``GraphedTextPerturbation``)."""
+        with tuned_gemms.scope("lxmert_pert") if self.tuned else contextlib.nullcontext():
+            return self._perturbation_text_grouped(inputs, cam_text, is_positive_pert, max_groups)
+
+    @torch.no_grad()
+    def _perturbation_text_grouped(self, inputs, cam_text, is_positive_pert=False, max_groups=2):
+        if cam_text.dim() != 2 or cam_text.shape != inputs["input_ids"].shape:
+            raise ValueError("perturbation_text_grouped: cam_text must be [B, T] like input_ids, got %s / %s"
+                             % (tuple(cam_text.shape), tuple(inputs["input_ids"].shape)))
+        if inputs["visual_feats"].shape[1] == 0:
+            raise ValueError("perturbation_text_grouped: needs a non-empty region set")
+        B, T = cam_text.shape
+        S = len(self.steps)
+        plan = self.text_step_groups(T, max_groups, cam_text.device)
+        mask = inputs.get("attention_mask")
+        text_len = mask.sum(dim=1).to(torch.int32) if mask is not None else \
+            torch.full((B,), T, dtype=torch.int32, device=cam_text.device)
+        where = plan.layout(B)
+        ids, types_, keep, _ = ops.lxmert_perturb_text(inputs["input_ids"], inputs["token_type_ids"], cam_text.to(torch.float32), text_len,
+                                                       plan.counts, where.table, where.elems, is_positive_pert)
+        visn = self.model.encode_vision(inputs["visual_feats"], inputs["visual_pos"])
+        scores = None
+        for (steps_g, n, width), offset in zip(plan.groups, where.offsets):
+            block = slice(offset, offset + B * n * width)
+            out = self.model.scores_no_grad(input_ids=ids[block].view(B * n, width), attention_mask=keep[block].view(B * n, width),
+                                            token_type_ids=types_[block].view(B * n, width), visn_encoded=visn, visn_repeat=n)
+            if scores is None:
+                scores = out.new_empty(B, S, out.shape[-1])
+            scores[:, steps_g] = out.reshape(B, n, -1)
+        return scores
+
     @staticmethod
     def accuracy(scores, label_scores):
         """``label_scores [num_answers]`` (or ``[B, num_answers]`` for batched scores): the item's soft VQA scores per
@@ -276,7 +377,8 @@ class GraphedImagePerturbation:
         acc = run(batch, R_t_t, R_t_i, labels)                                    # [B, S] per-step soft accuracies (graph output)
 
     The library GEMMs inside run with the DEFAULT selection (a tuned selection is not switched under a capture, ``tuned_gemms.scope``).
-    Image test only: the text test reads the question lengths on the host (``perturbation_text``)."""
+    Image test only: ``perturbation_text`` reads the question lengths on the host; the text test that is captured is
+    ``perturbation_text_grouped`` (``GraphedTextPerturbation``)."""
 
     def __init__(self, pert, batch, R_t_t, R_t_i, labels, is_positive_pert=False, warmup=2):
         self.pert, self.positive = pert, bool(is_positive_pert)
@@ -288,6 +390,36 @@ class GraphedImagePerturbation:
         cam_image, _ = normalize_cams_batch(self.R_t_t, self.R_t_i, self.static["attention_mask"])
         scores = self.pert._perturbation_image(self.static, cam_image, self.positive)
         return LxmertPerturbation.accuracy(scores, self.labels)
+
+    def __call__(self, batch, R_t_t, R_t_i, labels):
+        graphed.copy_inputs(self.static, batch)
+        self.R_t_t.copy_(R_t_t)
+        self.R_t_i.copy_(R_t_i)
+        self.labels.copy_(labels)
+        self.graph.replay()
+        return self.out
+
+
+class GraphedTextPerturbation:
+    """``normalize_cams_batch`` + ``LxmertPerturbation.perturbation_text_grouped`` + ``accuracy`` of a fixed-shape batch captured ONCE
+    into a hipGraph and replayed for any ragged batch of that shape -- ``GraphedImagePerturbation`` for the text test:
+
+        run = GraphedTextPerturbation(pert, batch, R_t_t, R_t_i, labels)        # example tensors of the shapes to come
+        acc = run(batch, R_t_t, R_t_i, labels)                                    # [B, S] per-step soft accuracies (graph output)
+
+    The question lengths are read from ``attention_mask`` on the device inside the graph; the step groups' widths depend on the padded
+    length alone.  The library GEMMs inside run with the DEFAULT selection.  ``max_groups``: see ``text_step_groups``."""
+
+    def __init__(self, pert, batch, R_t_t, R_t_i, labels, is_positive_pert=False, warmup=2, max_groups=2):
+        self.pert, self.positive, self.max_groups = pert, bool(is_positive_pert), int(max_groups)
+        self.static = {k: v.clone() for k, v in batch.items()}
+        self.R_t_t, self.R_t_i, self.labels = R_t_t.clone(), R_t_i.clone(), labels.clone()
+        self.graph, (self.out, self.scores), self._pinned = graphed.capture(self._call, warmup, pert.model)
+
+    def _call(self):
+        _, cam_text = normalize_cams_batch(self.R_t_t, self.R_t_i, self.static["attention_mask"])
+        scores = self.pert._perturbation_text_grouped(self.static, cam_text, self.positive, self.max_groups)
+        return LxmertPerturbation.accuracy(scores, self.labels), scores      # (``scores [B, S, answers]``: a graph output too)
 
     def __call__(self, batch, R_t_t, R_t_i, labels):
         graphed.copy_inputs(self.static, batch)

@@ -1577,6 +1577,67 @@ def selfattn_perturb_text(ids, segments, cam, text_len, counts, positive=False, 
     return o_ids, o_seg, o_mask, new_len
 
 
+def text_placement(place):
+    """A placement table of ``lxmert_perturb_text`` -- S rows ``(base, stride, width)`` -- as the HOST int64 array the entry reads
+    (build it once per shape and pass it again: a call then creates nothing)."""
+    rows = [tuple(int(v) for v in row) for row in place]
+    if not rows or any(len(row) != 3 for row in rows):
+        raise MMXError("text_placement: S >= 1 rows of (base, stride, width) expected")
+    return (C.c_int64 * (3 * len(rows)))(*[v for row in rows for v in row])
+
+
+def lxmert_perturb_text(ids, types, cam, text_len, counts, place, out_elems, positive=False, want_ranks=False, out=None):
+    """The S perturbed copies of B padded questions of a two-stream batch in one launch, written where ``place`` puts them
+    (``mmx_lxmert_perturb_text``).  ``ids`` / ``types [B, T]`` int64, ``cam [B, T]`` fp32, ``text_len [B]`` int32 and ``counts
+    [S, T - 1]`` int32 on the device (``counts[s][w] = int((1 - step_s) * w)``), ``place``: S rows ``(base, stride, width)`` on the
+    host (a list, or what ``text_placement`` made of one) -> ``(ids, types [out_elems] int64, mask [out_elems] fp32, new_len [S, B]
+    int64)``, with ``want_ranks`` also ``ranks [B, T]`` int32.  With ``n`` the length of question b (clamped to 2 .. T): positions 0
+    and n - 1 always stay, step s keeps the ``counts[s][n - 2]`` best of the words 1 .. n - 2 (the stable order of ``patch_ranks``;
+    ``positive`` ranks the negated scores) in their original order; sequence (s, b) is the ``width_s`` elements at ``base_s + b *
+    stride_s``: the kept positions, zeros behind, truncated at the width; ``new_len = 2 + kept`` is not truncated.  Elements no
+    sequence covers are not written.  ``2 <= T <= 256``, ``S <= 64``.  ``out``: the contiguous tensors to write to."""
+    what = "lxmert_perturb_text"
+    _dev(ids, types, cam, text_len, counts, *(out or ()))
+    if ids.dim() != 2 or ids.dtype != torch.int64 or types.dtype != torch.int64 or types.shape != ids.shape:
+        raise MMXError("%s: ids and types must be [B, T] int64, got %s %s / %s %s"
+                       % (what, tuple(ids.shape), ids.dtype, tuple(types.shape), types.dtype))
+    B, T = ids.shape
+    if not 2 <= T <= 256 or B < 1:
+        raise MMXError("%s: needs B >= 1 and 2 <= T <= 256 (got B=%d, T=%d)" % (what, B, T))
+    if cam.dtype != torch.float32 or tuple(cam.shape) != (B, T):
+        raise MMXError("%s: cam must be [%d, %d] fp32, got %s %s" % (what, B, T, tuple(cam.shape), cam.dtype))
+    if text_len.dtype != torch.int32 or tuple(text_len.shape) != (B,):
+        raise MMXError("%s: text_len must be [%d] int32 on the device, got %s %s" % (what, B, tuple(text_len.shape), text_len.dtype))
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != T - 1 or not 1 <= counts.shape[0] <= 64:
+        raise MMXError("%s: counts must be [S, %d] int32 with 1 <= S <= 64, got %s %s" % (what, T - 1, tuple(counts.shape), counts.dtype))
+    S, out_elems = counts.shape[0], int(out_elems)
+    if not isinstance(place, C.Array):
+        place = text_placement(place)
+    if len(place) != 3 * S:
+        raise MMXError("%s: %d placement rows for %d steps" % (what, len(place) // 3, S))
+    if out_elems < 1:
+        raise MMXError("%s: out_elems = %d < 1" % (what, out_elems))
+    ids, types, cam, text_len, counts = ids.contiguous(), types.contiguous(), cam.contiguous(), text_len.contiguous(), counts.contiguous()
+    shapes = (((out_elems,), torch.int64), ((out_elems,), torch.int64), ((out_elems,), torch.float32), ((S, B), torch.int64),
+              ((B, T), torch.int32))
+    if out is not None:
+        if len(out) != (5 if want_ranks else 4):
+            raise MMXError("%s: out must be (ids, types, mask, new_len%s)" % (what, ", ranks" if want_ranks else ""))
+        for t, (shape, dt) in zip(out, shapes):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                raise MMXError("%s: out needs contiguous ids / types [out_elems] int64, mask [out_elems] fp32, new_len [S, B] int64, "
+                               "ranks [B, T] int32" % what)
+        o_ids, o_types, o_mask, new_len, ranks = tuple(out) + (() if want_ranks else (None,))
+    else:
+        o_ids, o_types, o_mask, new_len, ranks = (torch.empty(shape, dtype=dt, device=ids.device) for shape, dt in shapes)
+        if not want_ranks:
+            ranks = None
+    check(lib().mmx_lxmert_perturb_text(_p(ids), _p(types), _p(cam), _p(text_len), _p(counts), place, _p(o_ids), _p(o_types), _p(o_mask),
+                                        _p(new_len), _p(ranks), out_elems, B, T, S, int(bool(positive)), _stream()),
+          "mmx_lxmert_perturb_text")
+    return (o_ids, o_types, o_mask, new_len, ranks) if want_ranks else (o_ids, o_types, o_mask, new_len)
+
+
 def head_kernel_shape(n_q, n_k, head_dim, slab_dtype=torch.float32):
     """Does the register-resident whole-head backward (``attention_head.hip``) serve this shape?  (Its eligibility test, host side:
     what decides whether a bf16 gradient stream can pass through an exact-fp32 attention without conversion passes.)"""
